@@ -27,7 +27,10 @@
 //     workgroup's: every stage's largest |x| (thread max -> wave max -> four LDS slots read after the stage's barrier) is
 //     compared with the reference exponent; a stage more than 2^6 above it multiplies the accumulators by 2^(E - E') first
 //     (exact), the output epilogue undoes 2^(8 - E + eW) with v_ldexp.  (conv_wino6.hip's fp16 form scales per tile: there a
-//     lane's operand column is its own.)
+//     lane's operand column is its own.)  The price of a workgroup-wide scale: a value more than ~2^10 below the workgroup's
+//     largest has a subnormal low plane, its error is ~2^-33 of that largest instead of 2^-24 of itself, and an output whose
+//     window holds only such values is not fp32-class per element (tests/test_hip_precision.py) -- an experiment switch, the
+//     engine runs conv_down on TERMS = 6 (refid_amd/engine.py DOWN_SPLIT).
 //
 // Mapping (one workgroup = 256 threads = 4 waves, one per SIMD; two workgroups per CU cover each other's staging,
 // barriers, prologue and epilogue -- the regime the trace of the Winograd tile showed to work on this chip):
@@ -588,11 +591,13 @@ int refid_launch_split3x3(const ConvKArgs& a, int terms, int mode, int cus, int 
         REFID_CHECK(wbytes < 0x7fffffffLL, "conv2d: packed weights too large for the split tile's 32-bit offsets");
     }
     const bool wide = a.Cout > 32;
-    // 8-row tiles when they still give every CU its two workgroups, 4-row tiles otherwise
-    // (split policy 1, "sample": decided as if the batch held 8 samples, so that a sample's bits do not depend on the batch it
-    //  is in -- with the fp16 form the workgroup's tile decides its scale, and the scale the rounding of values whose low plane
-    //  is subnormal; the exact-split bf16 forms give the same bits on either tile)
-    const int wg8 = cdiv(a.Wo, TW) * cdiv(a.Ho, 8) * (split_mode == 1 ? 8 : a.N) * cdiv(a.Cout, wide ? 64 : 32) * (mode == 2 ? 4 : 1);
+    // 8-row tiles when they still give every CU its two workgroups, 4-row tiles otherwise.  The exact-split bf16 forms give the
+    // same bits on either tile; with the fp16 form the workgroup's tile decides its scale, and the scale the rounding of values
+    // whose low plane is subnormal -- so there (and under split policy 1, "sample") the choice is made as if the batch held 8
+    // samples, whatever the policy: a sample's bits do not depend on the batch it is in
+    // (tests/test_hip_precision.py::test_fp16_forms_give_a_sample_the_same_bits_in_any_batch)
+    const bool per_sample = split_mode == 1 || terms == 19;
+    const int wg8 = cdiv(a.Wo, TW) * cdiv(a.Ho, 8) * (per_sample ? 8 : a.N) * cdiv(a.Cout, wide ? 64 : 32) * (mode == 2 ? 4 : 1);
     const bool tall = wg8 >= 2 * cus;
 #define SPLIT_DISPATCH(PLN)                                                          \
     (mode == 0 ? launch_split_pl<PLN, 0>(a, wide, tall, st)                          \

@@ -250,10 +250,12 @@ WINO6_THIN = os.environ.get("REFID_WINO6_THIN", "1") != "0"        # pred's forw
 # conv_down (4x4 / stride 2) and its input gradient have no Winograd form; on the split tile with six bf16 products per
 # fp32 product they run 1.6-2x faster than on the fp32 MFMA tile at the same distance from the float64 result (the operand
 # split is exact: tests/test_hip_conv.py::test_split_tile_conv_down_*).  0 = keep them on the fp32 MFMA tile.
-# (round 6: 19 = THREE fp16 products on two-plane operands scaled by exact powers of two -- the weights per tensor, the
-#  activations per workgroup and online along K, csrc/conv_split.hip --: half of 6's MFMAs in the same error class; the default.
-#  6 = six bf16 products on exact three-plane operands, round 2-5's form.)
-DOWN_SPLIT = int(os.environ.get("REFID_DOWN_SPLIT", "19"))
+# 6 (the default) = six bf16 products on exact three-plane operands: per element as close to float64 as the fp32 tile, at any
+# magnitude (tests/test_hip_precision.py).  19 = THREE fp16 products on two-plane operands scaled by exact powers of two -- the
+# weights per tensor, the activations per WORKGROUP (8 x 32 output pixels x all of K) and online along K, csrc/conv_split.hip --:
+# half of 6's MFMAs, a 0.8-1.0 % faster B=8 step, but a value 2^10 below its workgroup's largest keeps only part of its low plane (its
+# error is ~2^-33 of that largest), so a small output next to a large one in the same workgroup loses bits; an experiment switch.
+DOWN_SPLIT = int(os.environ.get("REFID_DOWN_SPLIT", "6"))
 # 1x1 convolutions on the pointwise tile's six-product form (refid_conv2d algo 3, mfma_terms 6).  Measured
 # (tools/bench_pw6.py, profiles/r03_pw6_bench.txt): 1.03-1.26x the fp32-MFMA form when the launch is repeated on warm
 # operands, NO gain inside the train step (676 launches: 39.8 vs 39.2 ms; the squeeze-excite fused conv3 is slower, 116
