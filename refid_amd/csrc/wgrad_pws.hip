@@ -176,11 +176,14 @@ struct PwsPlan { int ow, wi; };
 bool pws_plan(const refid_wgrad_desc* d, PwsPlan& p) {
     const int ci_geo = (d->phase != 0) ? d->i_total - d->i_base : d->c_a + d->c_b;
     const int ci = ci_geo > d->c_a + d->c_b ? ci_geo : d->c_a + d->c_b;
+    // two sources -- or, in a phased call, a second source still to come (the first recurrent step has none yet): the tile must
+    // not depend on it, or the first step's slabs would be split differently from the later steps' (lost / unreduced slabs)
+    const bool two = d->c_b || (d->phase != 0 && ci > d->c_a);
     p.ow = d->c_o >= 128 ? 4 : 2;
     p.wi = ci >= 128 ? 4 : (ci >= 64 ? 2 : 1);
-    while (d->c_b && p.wi > 1 && d->c_a % (32 * p.wi)) p.wi /= 2;     // an input-channel tile must lie in one source
+    while (two && p.wi > 1 && d->c_a % (32 * p.wi)) p.wi /= 2;        // an input-channel tile must lie in one source
     if (p.ow == 4 && p.wi == 1) {                          // (instantiated: 2x1 2x2 2x4 4x2 4x4)
-        if (d->c_b && d->c_a % 64) return false;
+        if (two && d->c_a % 64) return false;
         p.wi = 2;
     }
     return true;

@@ -820,10 +820,11 @@ class ConvOp:
     def _pws_plan_ok(co, ca, cb, ci):
         if co < 64 or co % 32 or ca % 32 or cb % 32 or ci % 32:
             return False
+        two = cb or ci > ca                 # (a phased call: the second source may only be missing at the first step)
         wi = 4 if ci >= 128 else (2 if ci >= 64 else 1)
-        while cb and wi > 1 and ca % (32 * wi):
+        while two and wi > 1 and ca % (32 * wi):
             wi //= 2
-        return not (co >= 128 and wi == 1 and cb and ca % 64)
+        return not (co >= 128 and wi == 1 and two and ca % 64)
 
     def _slab_layout(self, algo):
         """The partial-sum slabs persist over the calls of one backward pass, and their layout belongs to the algorithm
