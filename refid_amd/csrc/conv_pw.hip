@@ -21,7 +21,7 @@
 // 16 x 64 = 1024, at the fp32 tile's distance from the float64 result.  The waves of a workgroup run their load / MFMA /
 // store phases in lockstep, so the MFMA phase is a third of the kernel's time when the operands are warm (1.03-1.26x then,
 // tools/bench_pw6.py); inside the train step, on cold operands, the two forms time the same (39.8 vs 39.2 ms per step): the
-// engine keeps the fp32 form (REFID_PW6=1 switches).
+// engine keeps the fp32 form (this one is reached through the C ABI only).
 #include "common.h"
 #include "conv_args.h"
 #include <cstdlib>

@@ -229,11 +229,6 @@ WGRAD_BATCH = int(os.environ.get("REFID_WGRAD_BATCH", "8"))     # deferred launc
 # The weight gradients of up to this many consecutive time steps of one conv are ONE launch (the weights are shared over
 # T: their partial-sum slabs -- 134-537 MB of read-modify-write per launch at B=8 -- are then touched once per group
 # instead of once per step; 3x3 and 4x4/stride-2 convs; 1 = off)
-# Split-bf16 direct 3x3 tile (refid_conv2d algo 4) in the fp32 modes: 0 = never (Winograd fp32 tile), 6 / 3 = that many
-# bf16 products per fp32 product.  compute_dtype "bf16x3" sets 3; "bf16" uses the tile with one product wherever it
-# beats the LDS-staged bf16 tile (single-source convs and every input gradient).  6 is an experiment switch: measured
-# equal to the Winograd tile at best (the bf16 matrix pipe is power limited with real data: DESIGN.md).
-MFMA_SPLIT = int(os.environ.get("REFID_MFMA_SPLIT", "0"))
 # Winograd-domain GEMMs of the 3x3 convs with more than 32 output channels on the bf16 matrix cores, six exact-split
 # bf16 products per fp32 product (refid_conv2d algo 5, csrc/conv_wino6.hip): same error class as the fp32 Winograd tile at
 # 2.67x fewer matrix-pipe cycles.  0 = fp32 Winograd tile everywhere.
@@ -256,15 +251,6 @@ WINO6_THIN = os.environ.get("REFID_WINO6_THIN", "1") != "0"        # pred's forw
 # half of 6's MFMAs, a 0.8-1.0 % faster B=8 step, but a value 2^10 below its workgroup's largest keeps only part of its low plane (its
 # error is ~2^-33 of that largest), so a small output next to a large one in the same workgroup loses bits; an experiment switch.
 DOWN_SPLIT = int(os.environ.get("REFID_DOWN_SPLIT", "6"))
-# 1x1 convolutions on the pointwise tile's six-product form (refid_conv2d algo 3, mfma_terms 6).  Measured
-# (tools/bench_pw6.py, profiles/r03_pw6_bench.txt): 1.03-1.26x the fp32-MFMA form when the launch is repeated on warm
-# operands, NO gain inside the train step (676 launches: 39.8 vs 39.2 ms; the squeeze-excite fused conv3 is slower, 116
-# vs 90 us) -- on cold operands these tiles wait for HBM, not for the matrix pipe, and the six-product form runs 3 instead of
-# 4 waves per SIMD (144 registers).  Off; the form stays reachable through the C ABI and is tested.
-# six bf16 products on the pointwise tile: "1" every 1x1 layer (round 3: flat in the step), "2" only where the reduction runs over
-# 128 channels or more (those layers are bound by the fp32 matrix pipe), "0" never
-PW6 = int(os.environ.get("REFID_PW6", "0") or 0)
-PW6_MIN_K = 128
 # smallest output-channel count whose 3x3 weight gradient goes to the Winograd tile (64 x 32 channel tiles)
 WGRAD_WINO_MIN_CO = int(os.environ.get("REFID_WGRAD_WINO_MIN_CO", "32"))
 # Time steps per weight-gradient launch (the ABI takes up to 24): all T steps of a sweep in ONE launch write the partial-sum slabs
@@ -345,15 +331,61 @@ def _batch_step(n, *tensors):
     return max(1, (2 ** 31 - 2) // per)
 
 
+def _sub_batches(n, *tensors):
+    """The tiles address their tensors with 32-bit byte offsets (hardware range-checked buffer loads): a batch whose
+    tensors reach 2 GiB is issued in sub-batches -- samples are independent (no cross-sample op on the path).  Returns
+    the tensors' slices, sub-batch by sub-batch."""
+    step = _batch_step(n, *tensors)
+    return [tuple(None if t is None else t[i:i + step] for t in tensors) for i in range(0, n, step)]
+
+
+class _Packing:
+    """One packed copy of a conv's weights: the ConvOp attribute that holds the buffer (by name: _Egaca re-binds conv5.wp and
+    side.wp to halves of one buffer), the packer ("pack": the fp32 / bf16 tile layouts, "split": bf16 / fp16 planes of the
+    direct tile, "wino6": planes of U = G g G^T) and that packer's arguments after the weight; `flag` is bf16 for "pack",
+    f16 for the plane forms.  lazy: a fallback layout the batched repack leaves out (ConvOp._packed writes it on demand)."""
+    __slots__ = ("attr", "form", "args", "flag", "lazy", "epoch")
+
+    def __init__(self, attr, form, args, flag=False):
+        self.attr, self.form, self.args, self.flag, self.lazy, self.epoch = attr, form, args, flag, False, -1
+
+    def alloc(self, device):
+        if self.form == "pack":
+            return torch.empty(ops.packed_weight_floats(*self.args), dtype=torch.bfloat16 if self.flag else torch.float32, device=device)
+        return torch.empty(self.nbytes() // 2, dtype=torch.bfloat16, device=device)
+
+    def nbytes(self):
+        """Size of a plane-form packing (also what its 2 GiB guard looks at)."""
+        size = ops.packed_weight_split_bytes if self.form == "split" else ops.packed_weight_wino6_bytes
+        return size(*self.args, self.flag)
+
+    def pack(self, op):
+        out = getattr(op, self.attr)
+        if self.form == "pack":
+            (ops.pack_conv_weights_bf16 if self.flag else ops.pack_conv_weights)(op.w, *self.args, out=out, oscale=op.scale)
+        elif self.form == "split":
+            ops.pack_conv_weights_split(op.w, *self.args[:-1], planes=self.args[-1], out=out, oscale=op.scale, f16=self.flag)
+        else:
+            ops.pack_conv_weights_wino6(op.w, *self.args, out=out, oscale=op.scale, f16=self.flag)
+        self.epoch = op.arena.pack_epoch
+
+    def plan(self, op, plan):
+        out = getattr(op, self.attr)
+        if self.form == "pack":
+            plan.add_pack(op.w, *self.args, out, oscale=op.scale, bf16=self.flag)
+        elif self.form == "split":
+            plan.add_split(op.w, *self.args, out, oscale=op.scale, f16=self.flag)
+        else:
+            plan.add_wino6(op.w, *self.args, out, oscale=op.scale, f16=self.flag)
+
+
 class ConvOp:
     """One convolution of the network: geometry + packed weights + the three kernels."""
-    default_split = 0                         # set by Engine.__init__ for the convs it builds (compute_dtype "bf16x3")
 
-    def __init__(self, arena, name, kind="conv", need_dgrad=True, scale_name=None, bf16=False, split=0):
+    def __init__(self, arena, name, kind="conv", need_dgrad=True, scale_name=None, compute_dtype="fp32"):
         self.arena, self.name, self.kind = arena, name, kind
-        self.bf16 = bf16
+        bf16 = self.bf16 = compute_dtype == "bf16"
         self.split = 0                        # product terms of the split-bf16 tile (algo 4) this conv may use
-        self.s_f16 = False                    # ... as three fp16 products (terms 19: the packings hold two fp16 planes)
         self.w = arena.p(name + ".weight")
         self.gw = arena.g(name + ".weight")
         self.has_bias = (name + ".bias") in arena.shapes
@@ -372,32 +404,26 @@ class ConvOp:
         else:
             self.co, self.ci, self.k = s[0], s[1], s[2]
         self.need_dgrad = need_dgrad
-        k = self.k
+        k, co, ci = self.k, self.co, self.ci
+        # (kh, kw, stride, mode) of the forward / input-gradient launch, and the input gradient's padding
         if kind == "conv":
-            self.stride, self.pad, self.mode = 1, k // 2, 0
-            self.f_geo = (k, k, 1, 0)
-            self.f_role, self.f_rows = ops.ROLE_FWD, self.co
-            self.d_geo = (k, k, 1, 0)
-            self.d_role, self.d_rows = ops.ROLE_DGRAD, self.ci
+            self.stride, self.pad = 1, k // 2
+            f_geo, f_role, self.f_rows = (k, k, 1, 0), ops.ROLE_FWD, co
+            d_geo, d_padding, self.d_role, self.d_rows = (k, k, 1, 0), k - 1 - self.pad, ops.ROLE_DGRAD, ci
         elif kind == "down":
-            self.stride, self.pad, self.mode = 2, 1, 0
-            self.f_geo = (4, 4, 2, 0)
-            self.f_role, self.f_rows = ops.ROLE_FWD, self.co
-            self.d_geo = (4, 4, 2, 2)
-            self.d_role, self.d_rows = ops.ROLE_DOWN_DGRAD, self.ci
+            self.stride, self.pad = 2, 1
+            f_geo, f_role, self.f_rows = (4, 4, 2, 0), ops.ROLE_FWD, co
+            d_geo, d_padding, self.d_role, self.d_rows = (4, 4, 2, 2), 1, ops.ROLE_DOWN_DGRAD, ci
         elif kind == "convT":
-            self.stride, self.pad, self.mode = 1, 0, 1
-            self.f_geo = (1, 1, 1, 1)
-            self.f_role, self.f_rows = ops.ROLE_CONVT, 4 * self.co
-            self.d_geo = (2, 2, 2, 0)
-            self.d_role, self.d_rows = ops.ROLE_CONVT_DGRAD, self.ci
+            self.stride, self.pad = 1, 0
+            f_geo, f_role, self.f_rows = (1, 1, 1, 1), ops.ROLE_CONVT, 4 * co
+            d_geo, d_padding, self.d_role, self.d_rows = (2, 2, 2, 0), 0, ops.ROLE_CONVT_DGRAD, ci
         else:
             raise ValueError(kind)
-        kh, kw, st, md = self.f_geo
-        self.f_kc = ops.conv_kc(kh, kw, st, md)
-        self.f_bn = ops.conv_bn(kh, kw, st, md, self.f_rows)
+        self.f_kc = ops.conv_kc(*f_geo)
+        self.f_bn = ops.conv_bn(*f_geo, self.f_rows)
         self.f_algo = self.d_algo = 0
-        pointwise = USE_POINTWISE and kind == "conv" and k == 1 and self.ci % 16 == 0 and self.co % 16 == 0
+        pointwise = USE_POINTWISE and kind == "conv" and k == 1 and ci % 16 == 0 and co % 16 == 0
         if bf16 and pointwise:
             # the 1x1 layers are bandwidth bound on fp32 tensors either way: the register-operand fp32 tile (no LDS,
             # no conversion pass) beats the LDS-staged bf16 tile on them (39.5 -> 34 ms / step), at full precision
@@ -408,32 +434,28 @@ class ConvOp:
             self.f_algo = self.d_algo = 2
             self.f_kc *= 2
         elif USE_WINOGRAD and kind == "conv" and k == 3:
-            if self.co >= 16:                  # pred (3 channels) stays on the direct tile
-                self.f_algo, self.f_role, self.f_kc, self.f_bn = 1, ops.ROLE_WINO_FWD, 8, 64
+            if co >= 16:                       # pred (3 channels) stays on the direct tile
+                self.f_algo, f_role, self.f_kc, self.f_bn = 1, ops.ROLE_WINO_FWD, 8, 64
             self.d_algo, self.d_role = 1, ops.ROLE_WINO_DGRAD
         elif pointwise:
             self.f_algo = self.d_algo = 3
             self.f_kc, self.f_bn = 8, 32
-        elif kind == "convT" and USE_POINTWISE and CONVT_PW and self.ci % 16 == 0 and self.co % 4 == 0 and 4 * self.co > 32:
+        elif kind == "convT" and USE_POINTWISE and CONVT_PW and ci % 16 == 0 and co % 4 == 0 and 4 * co > 32:
             # ConvTranspose2d(2,2) forward = a 1x1 GEMM over 4 Co columns: the register-operand pointwise tile with a
             # pixel-shuffle store (the LDS-staged direct tile ran it at 0.24 of the fp32 pipe with 0.78 LDS bank conflicts)
             self.f_algo = 3
             self.f_kc, self.f_bn = 8, 32
         self.f_pad = -(-self.f_rows // self.f_bn) * self.f_bn
-        dev = self.w.device
-        pdt = torch.bfloat16 if bf16 else torch.float32
-        self.wp = torch.empty(ops.packed_weight_floats(self.f_role, self.f_bn, self.f_kc, k, k, self.co, self.ci),
-                              dtype=pdt, device=dev)
-        self.wd = None
-        self.d_bn_cache = {}
+        # The packed copies of the weights, in the order repack() / plan_repack() write them (the batched launch's entry order)
+        wp = _Packing("wp", "pack", (f_role, self.f_bn, self.f_kc, k, k, co, ci), bf16)
+        wd = wp6 = wd6 = wps = wds = None
         if need_dgrad:
-            kh, kw, st, md = self.d_geo
-            self.d_kc = ops.conv_kc(kh, kw, st, md)
+            self.d_kc = ops.conv_kc(*d_geo)
             # a dgrad may be issued for a row range (two-source convs): tile width follows the range
-            self.d_bn = ops.conv_bn(kh, kw, st, md, self.d_rows if self.d_rows <= 128 else 128)
-            if kind == "conv" and self.ci == 2 * self.co and self.k in (1, 3):
-                self.d_bn = ops.conv_bn(kh, kw, st, md, self.co)     # issued as two halves of co rows
-            if kind == "convT" and self.f_algo == 3 and (2 * self.co) % 8 == 0:
+            self.d_bn = ops.conv_bn(*d_geo, self.d_rows if self.d_rows <= 128 else 128)
+            if kind == "conv" and ci == 2 * co and k in (1, 3):
+                self.d_bn = ops.conv_bn(*d_geo, co)                  # issued as two halves of co rows
+            if kind == "convT" and self.f_algo == 3 and (2 * co) % 8 == 0:
                 # its input gradient (2x2 stride 2: non-overlapping patches) as ONE GEMM with K = 4 Co on the pointwise tile: a
                 # pixel's patch is two contiguous runs of 2 Co floats (the direct tile fetched 3.3-4.4x its bytes, 0.29 of HBM)
                 self.d_algo, self.d_role = 3, ops.ROLE_CONVT_DGRAD_PW
@@ -444,76 +466,91 @@ class ConvOp:
             if bf16:
                 self.d_kc *= 2
             self.d_pad = -(-self.d_rows // self.d_bn) * self.d_bn
-            self.wd = torch.empty(ops.packed_weight_floats(self.d_role, self.d_bn, self.d_kc, k, k, self.co, self.ci),
-                                  dtype=pdt, device=dev)
-        # pointwise tile, six bf16 products per fp32 product: second packing (three bf16 planes, 16-channel chunks)
-        self.wpp6 = self.wdp6 = None
-        if PW6 and self.kind == "conv" and self.f_algo == 3 and self.ci % 16 == 0 and self.co % 16 == 0:
-            if self.co > 32 and (PW6 == 1 or self.ci >= PW6_MIN_K):
-                self.wpp6 = torch.empty(ops.packed_weight_split_bytes(ops.ROLE_FWD, 32, 1, 1, self.co, self.ci, 3) // 2,
-                                        dtype=torch.bfloat16, device=dev)
-            if need_dgrad and self.ci > 32 and (PW6 == 1 or self.co >= PW6_MIN_K):
-                self.wdp6 = torch.empty(ops.packed_weight_split_bytes(ops.ROLE_DGRAD, 32, 1, 1, self.co, self.ci, 3) // 2,
-                                        dtype=torch.bfloat16, device=dev)
+            wd = _Packing("wd", "pack", (self.d_role, self.d_bn, self.d_kc, k, k, co, ci), bf16)
         # Winograd x six bf16 products (algo 5): third packing -- three bf16 planes of U = G g G^T.  From 32 output channels
         # on (round 4: the tile's 32-channel form; REFID_WINO6_MIN_CO=33 restores round 3's choice for an A/B)
-        self.wp6 = self.wd6 = None
         # ... and thin outputs (pred, 32 -> 3): the direct fp32 tile pads them to 32 GEMM columns and is bound by the fp32
         # matrix pipe (100 us per launch at B=8); on the 32-channel Winograd x six form the padding costs cheap bf16 MFMAs
-        thin6 = WINO6_THIN and kind == "conv" and k == 3 and self.co <= 4 and self.ci % 16 == 0 and USE_WINOGRAD
+        thin6 = WINO6_THIN and kind == "conv" and k == 3 and co <= 4 and ci % 16 == 0 and USE_WINOGRAD
         # the packings' form: two fp16 planes + header (mfma_terms 3) or three bf16 planes (0)
-        self.w6_f16_f, self.w6_f16_d = WINO_F16_FWD, WINO_F16_DGRAD
-        if WINO6 and not bf16 and ((self.f_algo == 1 and self.co >= WINO6_MIN_CO) or thin6) and self.ci % 4 == 0 and \
-                ops.packed_weight_wino6_bytes(ops.ROLE_WINO_FWD, self.co, self.ci) < 2 ** 31 - 1:
-            self.wp6 = torch.empty(ops.packed_weight_wino6_bytes(ops.ROLE_WINO_FWD, self.co, self.ci, self.w6_f16_f) // 2,
-                                   dtype=torch.bfloat16, device=dev)
-        if WINO6 and not bf16 and need_dgrad and self.d_algo == 1 and self.ci >= WINO6_MIN_CO and self.co % 4 == 0 and \
-                ops.packed_weight_wino6_bytes(ops.ROLE_WINO_DGRAD, self.co, self.ci) < 2 ** 31 - 1:
-            self.wd6 = torch.empty(ops.packed_weight_wino6_bytes(ops.ROLE_WINO_DGRAD, self.co, self.ci, self.w6_f16_d) // 2,
-                                   dtype=torch.bfloat16, device=dev)
-        # split-bf16 direct tile (algo 4): second packing next to the default one
-        terms = 1 if bf16 else (split or ConvOp.default_split or MFMA_SPLIT)
-        self.wps = self.wds = None
-        if terms and kind == "conv" and k == 3 and self.ci % 8 == 0 and self.co >= 16:
+        if WINO6 and not bf16 and ((self.f_algo == 1 and co >= WINO6_MIN_CO) or thin6) and ci % 4 == 0:
+            wp6 = _Packing("wp6", "wino6", (ops.ROLE_WINO_FWD, co, ci), WINO_F16_FWD)
+        if WINO6 and not bf16 and need_dgrad and self.d_algo == 1 and ci >= WINO6_MIN_CO and co % 4 == 0:
+            wd6 = _Packing("wd6", "wino6", (ops.ROLE_WINO_DGRAD, co, ci), WINO_F16_DGRAD)
+        if wp6 is not None and wp6.nbytes() >= 2 ** 31 - 1:
+            wp6 = None
+        if wd6 is not None and wd6.nbytes() >= 2 ** 31 - 1:
+            wd6 = None
+        # split-bf16 direct tile (algo 4): second packing next to the default one.  Product terms per fp32 product: 1 = plain
+        # bf16 operands ("bf16"), 3 = two bf16 planes ("bf16x3": 2^-16 relative per product, 64x finer than TF32), 6 = three
+        # exact planes, ops.TERMS_F16X3 = two fp16 planes (conv_down only: DOWN_SPLIT)
+        terms = 1 if bf16 else (3 if compute_dtype == "bf16x3" else 0)
+        sf_pad = sd_pad = 0
+        if terms and kind == "conv" and k == 3 and ci % 8 == 0 and co >= 16:
             self.split = terms
-            planes = {1: 1, 3: 2, 6: 3}[terms]
-            self.s_planes = planes
-            self.sf_bn = ops.conv_bn(3, 3, 1, 0, self.co)
-            self.sf_pad = -(-self.co // self.sf_bn) * self.sf_bn
-            self.wps = torch.empty(ops.packed_weight_split_bytes(ops.ROLE_FWD, self.sf_bn, 3, 3, self.co, self.ci, planes) // 2,
-                                   dtype=torch.bfloat16, device=dev)
-            if need_dgrad and self.co % 8 == 0:
-                self.sd_bn = self.d_bn if self.d_algo != 1 else ops.conv_bn(3, 3, 1, 0, min(self.ci, 128))
-                if self.ci == 2 * self.co:
-                    self.sd_bn = ops.conv_bn(3, 3, 1, 0, self.co)
-                self.sd_pad = -(-self.ci // self.sd_bn) * self.sd_bn
-                self.wds = torch.empty(ops.packed_weight_split_bytes(ops.ROLE_DGRAD, self.sd_bn, 3, 3, self.co, self.ci, planes) // 2,
-                                       dtype=torch.bfloat16, device=dev)
-        if kind == "down" and self.ci % 8 == 0 and self.co % 8 == 0 and (bf16 or DOWN_SPLIT or ConvOp.default_split):
-            self.split = terms = 1 if bf16 else (ConvOp.default_split or DOWN_SPLIT)
-            self.s_planes = planes = {1: 1, 3: 2, 6: 3, ops.TERMS_F16X3: 2}[terms]
-            self.s_f16 = f16 = terms == ops.TERMS_F16X3
+            planes = {1: 1, 3: 2}[terms]
+            sf_bn = ops.conv_bn(3, 3, 1, 0, co)
+            sf_pad = -(-co // sf_bn) * sf_bn
+            wps = _Packing("wps", "split", (ops.ROLE_FWD, sf_bn, 3, 3, co, ci, planes))
+            if need_dgrad and co % 8 == 0:
+                sd_bn = self.d_bn if self.d_algo != 1 else ops.conv_bn(3, 3, 1, 0, min(ci, 128))
+                if ci == 2 * co:
+                    sd_bn = ops.conv_bn(3, 3, 1, 0, co)
+                sd_pad = -(-ci // sd_bn) * sd_bn
+                wds = _Packing("wds", "split", (ops.ROLE_DGRAD, sd_bn, 3, 3, co, ci, planes))
+        if kind == "down" and ci % 8 == 0 and co % 8 == 0 and (terms or DOWN_SPLIT):
+            self.split = terms = terms or DOWN_SPLIT
+            planes = {1: 1, 3: 2, 6: 3, ops.TERMS_F16X3: 2}[terms]
+            f16 = terms == ops.TERMS_F16X3
             if not bf16:                      # (plain bf16 operands: the LDS-staged tile is as fast on the forward conv)
-                self.sf_bn = ops.conv_bn(4, 4, 2, 0, self.co)
-                self.sf_pad = -(-self.co // self.sf_bn) * self.sf_bn
-                self.wps = torch.empty(ops.packed_weight_split_bytes(ops.ROLE_FWD, self.sf_bn, 4, 4, self.co, self.ci, planes, f16) // 2,
-                                       dtype=torch.bfloat16, device=dev)
+                sf_bn = ops.conv_bn(4, 4, 2, 0, co)
+                sf_pad = -(-co // sf_bn) * sf_bn
+                wps = _Packing("wps", "split", (ops.ROLE_FWD, sf_bn, 4, 4, co, ci, planes), f16)
             if need_dgrad:
-                self.sd_bn = ops.conv_bn(4, 4, 2, 2, self.ci)
-                self.sd_pad = -(-self.ci // self.sd_bn) * self.sd_bn
-                self.wds = torch.empty(ops.packed_weight_split_bytes(ops.ROLE_DOWN_DGRAD, self.sd_bn, 4, 4, self.co, self.ci,
-                                                                     planes, f16) // 2, dtype=torch.bfloat16, device=dev)
+                sd_bn = ops.conv_bn(4, 4, 2, 2, ci)
+                sd_pad = -(-ci // sd_bn) * sd_bn
+                wds = _Packing("wds", "split", (ops.ROLE_DOWN_DGRAD, sd_bn, 4, 4, co, ci, planes), f16)
+        # A conv with Winograd x six planes runs on them wherever its shapes allow (_fwd_route / _dgrad_route): its fp32 Winograd
+        # packing (wp / wd, algo 1) is a FALLBACK layout (two sources whose first is not a multiple of 16 channels, input-
+        # gradient row ranges below 32 rows) -- 159 MB of the model's 463 MB of packed weights that the batched repack of
+        # every optimiser step does not write; whoever needs one packs it on demand (_packed), stamped with the arena's
+        # pack epoch.  The one-by-one repack() writes everything.
+        self.wp_lazy = wp.lazy = LAZY_FALLBACK_PACKS and wp6 is not None and self.f_algo == 1
+        self.wd_lazy = LAZY_FALLBACK_PACKS and wd6 is not None and self.d_algo == 1
+        if wd is not None:
+            wd.lazy = self.wd_lazy
+        self.packings = [p for p in (wp, wd, wp6, wd6, wps, wds) if p is not None]
+        self._lazy = {p.attr: p for p in self.packings if p.lazy}
+        self.wd = self.wp6 = self.wd6 = self.wps = self.wds = None
+        for p in self.packings:
+            setattr(self, p.attr, p.alloc(self.w.device))
         self.b_eff = self.b
         if self.scale is not None and self.has_bias:
             self.b_eff = torch.empty_like(self.b)
-        # A conv with Winograd x six planes runs on them wherever its shapes allow (fwd / dgrad below): its fp32 Winograd
-        # packing (wp / wd, algo 1) is a FALLBACK layout (two sources whose first is not a multiple of 16 channels, input-
-        # gradient row ranges below 32 rows) -- 159 MB of the model's 463 MB of packed weights that the batched repack of
-        # every optimiser step does not write; whoever needs one packs it on demand (_fallback_wp / _fallback_wd), stamped
-        # with the arena's pack epoch.  The one-by-one repack() writes everything.
-        self.wp_lazy = LAZY_FALLBACK_PACKS and self.wp6 is not None and self.f_algo == 1
-        self.wd_lazy = LAZY_FALLBACK_PACKS and self.wd6 is not None and self.d_algo == 1
-        self._wp_epoch = self._wd_epoch = -1
+        # The tiles a call can take -- fwd / dgrad pick one by the call's shapes (_fwd_route / _dgrad_route):
+        #   (attribute of the packed weights, conv2d keywords, writes the second output (add2 / out2) itself?,
+        #    fwd: takes the fused pointwise extras (pw) / dgrad: its mask epilogue can apply GELU')
+        kh, kw, st, md = f_geo
+        self._f_split = self._f_wino6 = self._d_split = self._d_wino6 = self._d_plain = None
+        if wps is not None:
+            self._f_split = ("wps", dict(kh=kh, kw=kw, stride=st, pad=1, mode=0, cout_pad=sf_pad, algo=4, terms=self.split), True, False)
+        if wp6 is not None and self.split == 0:
+            self._f_wino6 = ("wp6", dict(kh=3, kw=3, stride=1, pad=1, mode=0, cout_pad=-(-self.f_rows // 64) * 64, algo=5,
+                                     terms=3 if wp6.flag else 0), True, False)
+        # (the pointwise tile has no second output)
+        self._f_plain = ("wp", dict(kh=kh, kw=kw, stride=st, pad=self.pad, mode=md, cout_pad=self.f_pad, algo=self.f_algo),
+                         self.f_algo != 3, True)
+        if need_dgrad:
+            kh, kw, st, md = d_geo
+            if wds is not None:
+                self._d_split = ("wds", dict(kh=kh, kw=kw, stride=st, pad=1, mode=md, cout_pad=sd_pad, algo=4, terms=self.split), True, False)
+            if wd6 is not None and self.split == 0:
+                self._d_wino6 = ("wd6", dict(kh=3, kw=3, stride=1, pad=1, mode=0, cout_pad=self.d_pad, algo=5,
+                                         terms=3 if wd6.flag else 0), True, False)
+            # the pointwise tile: the patch GEMM of ConvTranspose2d writes the second output, the 1x1 layers keep their separate
+            # skip-sum launch.  GELU' rides only in the fp32 pointwise tile of a 1x1 conv (refid_conv_desc.mask_mode = 1)
+            self._d_plain = ("wd", dict(kh=kh, kw=kw, stride=st, pad=d_padding, mode=md, cout_pad=self.d_pad, algo=self.d_algo),
+                             self.d_algo != 3 or kind == "convT", self.d_algo == 3 and kind == "conv")
         # weight-gradient partial sums of the T recurrent steps accumulate in a private slab buffer
         # and are reduced into the parameter gradient once per step (finish_wgrad)
         self.wslab = None
@@ -528,73 +565,44 @@ class ConvOp:
 
     def plan_repack(self, plan):
         """The same packings as repack(), as entries of an ops.PackPlan (one launch for the whole model)."""
-        k = self.k
-        if not self.wp_lazy:
-            plan.add_pack(self.w, self.f_role, self.f_bn, self.f_kc, k, k, self.co, self.ci, self.wp, oscale=self.scale, bf16=self.bf16)
-        if self.wd is not None and not self.wd_lazy:
-            plan.add_pack(self.w, self.d_role, self.d_bn, self.d_kc, k, k, self.co, self.ci, self.wd, oscale=self.scale, bf16=self.bf16)
-        if self.wpp6 is not None:
-            plan.add_split(self.w, ops.ROLE_FWD, 32, 1, 1, self.co, self.ci, 3, self.wpp6, oscale=self.scale)
-        if self.wdp6 is not None:
-            plan.add_split(self.w, ops.ROLE_DGRAD, 32, 1, 1, self.co, self.ci, 3, self.wdp6, oscale=self.scale)
-        if self.wp6 is not None:
-            plan.add_wino6(self.w, ops.ROLE_WINO_FWD, self.co, self.ci, self.wp6, oscale=self.scale, f16=self.w6_f16_f)
-        if self.wd6 is not None:
-            plan.add_wino6(self.w, ops.ROLE_WINO_DGRAD, self.co, self.ci, self.wd6, oscale=self.scale, f16=self.w6_f16_d)
-        if self.wps is not None:
-            plan.add_split(self.w, ops.ROLE_FWD, self.sf_bn, k, k, self.co, self.ci, self.s_planes, self.wps, oscale=self.scale, f16=self.s_f16)
-        if self.wds is not None:
-            plan.add_split(self.w, ops.ROLE_DOWN_DGRAD if self.kind == "down" else ops.ROLE_DGRAD, self.sd_bn, k, k, self.co,
-                           self.ci, self.s_planes, self.wds, oscale=self.scale, f16=self.s_f16)
+        for p in self.packings:
+            if not p.lazy:
+                p.plan(self, plan)
         if self.scale is not None and self.has_bias:
             plan.add_mul_vec(self.b, self.scale, self.b_eff)
 
-    def _fallback_wp(self):
-        """The fp32 Winograd forward packing, written now if the batched repack left it out (wp_lazy)."""
-        if self.wp_lazy and self._wp_epoch != self.arena.pack_epoch:
-            ops.pack_conv_weights(self.w, self.f_role, self.f_bn, self.f_kc, self.k, self.k, self.co, self.ci, out=self.wp,
-                                  oscale=self.scale)
-            self._wp_epoch = self.arena.pack_epoch
-        return self.wp
-
-    def _fallback_wd(self):
-        if self.wd_lazy and self._wd_epoch != self.arena.pack_epoch:
-            ops.pack_conv_weights(self.w, self.d_role, self.d_bn, self.d_kc, self.k, self.k, self.co, self.ci, out=self.wd,
-                                  oscale=self.scale)
-            self._wd_epoch = self.arena.pack_epoch
-        return self.wd
+    def _packed(self, attr):
+        """The packed weights `attr`; a lazily packed fallback layout is written now if the batched repack left it stale."""
+        p = self._lazy.get(attr)
+        if p is not None and p.epoch != self.arena.pack_epoch:
+            p.pack(self)
+        return getattr(self, attr)
 
     def pack_fallbacks(self):
         """Bring the lazily packed layouts up to date (tests that read wp / wd directly)."""
-        self._fallback_wp()
-        if self.wd is not None:
-            self._fallback_wd()
+        for attr in self._lazy:
+            self._packed(attr)
 
     def repack(self):
-        k = self.k
-        pack = ops.pack_conv_weights_bf16 if self.bf16 else ops.pack_conv_weights
-        pack(self.w, self.f_role, self.f_bn, self.f_kc, k, k, self.co, self.ci, out=self.wp, oscale=self.scale)
-        if self.wd is not None:
-            pack(self.w, self.d_role, self.d_bn, self.d_kc, k, k, self.co, self.ci, out=self.wd, oscale=self.scale)
-        self._wp_epoch = self._wd_epoch = self.arena.pack_epoch
-        if self.wpp6 is not None:
-            ops.pack_conv_weights_split(self.w, ops.ROLE_FWD, 32, 1, 1, self.co, self.ci, planes=3, out=self.wpp6, oscale=self.scale)
-        if self.wdp6 is not None:
-            ops.pack_conv_weights_split(self.w, ops.ROLE_DGRAD, 32, 1, 1, self.co, self.ci, planes=3, out=self.wdp6, oscale=self.scale)
-        if self.wp6 is not None:
-            ops.pack_conv_weights_wino6(self.w, ops.ROLE_WINO_FWD, self.co, self.ci, out=self.wp6, oscale=self.scale, f16=self.w6_f16_f)
-        if self.wd6 is not None:
-            ops.pack_conv_weights_wino6(self.w, ops.ROLE_WINO_DGRAD, self.co, self.ci, out=self.wd6, oscale=self.scale, f16=self.w6_f16_d)
-        if self.wps is not None:
-            ops.pack_conv_weights_split(self.w, ops.ROLE_FWD, self.sf_bn, k, k, self.co, self.ci, planes=self.s_planes,
-                                        out=self.wps, oscale=self.scale, f16=self.s_f16)
-        if self.wds is not None:
-            ops.pack_conv_weights_split(self.w, ops.ROLE_DOWN_DGRAD if self.kind == "down" else ops.ROLE_DGRAD, self.sd_bn,
-                                        k, k, self.co, self.ci, planes=self.s_planes, out=self.wds, oscale=self.scale, f16=self.s_f16)
+        for p in self.packings:
+            p.pack(self)
         if self.scale is not None and self.has_bias:
             ops.mul_vec(self.b, self.scale, out=self.b_eff)
 
     # ---- forward ---------------------------------------------------------------------------
+    def _fwd_route(self, n, ho, wo, a, b, pw):
+        """Which tile takes this forward call?  (one of the tuples built in __init__)"""
+        r = self._f_split
+        if r is not None and (self.split > 1 or b is None) and a.shape[3] % 8 == 0 and pw is None and \
+                (self.kind == "conv" or (b is None and _fills_gpu(n, ho, wo, self.co, 1))):
+            # (one product = plain bf16 operands: only where this tile beats the LDS-staged one -- single-source convs;
+            #  conv_down: only when the grid gives every CU a workgroup -- the fp32 MFMA tile has a split-K form for less)
+            return r
+        r = self._f_wino6
+        if r is not None and (b is None or a.shape[3] % 16 == 0):
+            return r
+        return self._f_plain
+
     def fwd(self, a, b=None, res=None, slope_pre=1.0, slope_post=1.0, out=None, pw=None, bias=True, plus=None):
         """out = post(pre(conv([a|b]) + bias) + res).  bias=False leaves the bias out (a conv is linear: where one operand of
         an input sum does not depend on the time step, W (a_t + c) + bias is issued as W a_t + (W c + bias) with the second
@@ -614,46 +622,28 @@ class ConvOp:
                 out.zero_()
                 out = out[..., :oc]
         o2 = torch.empty_like(out) if plus is not None else None
-        two = dict(add2=plus, out2=o2) if plus is not None else {}
+        parts = ((a, b, res, out),)
         if n * a.stride(0) >= _LIM4 or n * out.stride(0) >= _LIM4 or (b is not None and n * b.stride(0) >= _LIM4):
-            step = _batch_step(n, a, b, res, out)
-            # the tiles address their tensors with 32-bit byte offsets (hardware range-checked buffer loads): a batch whose
-            # tensors reach 2 GiB is issued in sub-batches -- samples are independent (no cross-sample op on the path)
             if pw is not None:
                 raise RefidHipError(f"{self.name}: fused pointwise extras cannot be issued in sub-batches (tensor >= 2 GiB)")
-            for i in range(0, n, step):
-                j = min(n, i + step)
-                self.fwd(a[i:j], None if b is None else b[i:j], None if res is None else res[i:j], slope_pre, slope_post,
-                         out[i:j], bias=bias)
-            return out if plus is None else (out, ops.add(out, plus, out=o2))
-        kh, kw, st, md = self.f_geo
-        if self.wps is not None and (self.split > 1 or b is None) and a.shape[3] % 8 == 0 and pw is None and \
-                (self.kind == "conv" or (b is None and _fills_gpu(n, ho, wo, self.co, 1))):
-            # (one product = plain bf16 operands: only where this tile beats the LDS-staged one -- single-source convs;
-            #  conv_down: only when the grid gives every CU a workgroup -- the fp32 MFMA tile has a split-K form for less)
-            ops.conv2d(a, self.wps, out, kh=kh, kw=kw, stride=st, pad=1, mode=0, cout=self.co, cout_pad=self.sf_pad, in_b=b,
-                       bias=bv, res=res, slope_pre=slope_pre, slope_post=slope_post, algo=4, terms=self.split, **two)
-            return out if plus is None else (out, o2)
-        if self.wp6 is not None and self.split == 0 and (b is None or a.shape[3] % 16 == 0):
-            ops.conv2d(a, self.wp6, out, kh=3, kw=3, stride=1, pad=1, mode=0, cout=self.f_rows, cout_pad=-(-self.f_rows // 64) * 64, in_b=b,
-                       bias=bv, res=res, slope_pre=slope_pre, slope_post=slope_post, algo=5, terms=3 if self.w6_f16_f else 0, **two)
-            return out if plus is None else (out, o2)
-        if self.wpp6 is not None and a.shape[3] % 16 == 0 and (b is None or b.shape[3] % 16 == 0):
-            ops.conv2d(a, self.wpp6, out, kh=1, kw=1, stride=1, pad=0, mode=0, cout=self.f_rows, cout_pad=self.f_pad, in_b=b,
-                       bias=bv, res=res, slope_pre=slope_pre, slope_post=slope_post, algo=3, pw=pw, terms=6)
-            return out if plus is None else (out, ops.add(out, plus, out=o2))
-        if self.f_algo == 3:                                      # (the pointwise tile has no second output)
-            two = {}
-        ops.conv2d(a, self._fallback_wp(), out, kh=kh, kw=kw, stride=st, pad=self.pad, mode=md, cout=self.f_rows,
-                   cout_pad=self.f_pad, in_b=b, bias=bv, res=res, slope_pre=slope_pre, slope_post=slope_post,
-                   algo=self.f_algo, pw=pw, **two)
-        if plus is not None and not two:
+            parts = _sub_batches(n, a, b, res, out)
+        for a_i, b_i, res_i, out_i in parts:
+            attr, geo, fused, takes_pw = self._fwd_route(a_i.shape[0], ho, wo, a_i, b_i, pw)
+            fused = fused and plus is not None and len(parts) == 1
+            extra = dict(add2=plus, out2=o2) if fused else {}
+            if takes_pw:
+                extra["pw"] = pw
+            ops.conv2d(a_i, self._packed(attr), out_i, cout=self.f_rows, in_b=b_i, bias=bv, res=res_i, slope_pre=slope_pre,
+                       slope_post=slope_post, **geo, **extra)
+        if plus is None:
+            return out
+        if not fused:
             ops.add(out, plus, out=o2)
-        return out if plus is None else (out, o2)
+        return out, o2
 
     def can_fwd_from(self):
         """Can fwd_from() address a block of input channels of this conv directly?  (fp32 pointwise tile, chunk-major packing)"""
-        return self.kind == "conv" and self.k == 1 and self.f_algo == 3 and self.wpp6 is None and not self.bf16
+        return self.kind == "conv" and self.k == 1 and self.f_algo == 3 and not self.bf16
 
     def fwd_from(self, a, k_base):
         """conv over the input channels k_base .. k_base + C_a only (+ bias): the packing is [chunk][row][kc], so the block's
@@ -668,6 +658,20 @@ class ConvOp:
         return out
 
     # ---- input gradient ----------------------------------------------------------------------
+    def _dgrad_route(self, g, cnt):
+        """Which tile takes the input gradient of `cnt` rows from g?  (one of the tuples built in __init__)"""
+        r = self._d_split
+        if r is not None and (self.kind == "conv" or _fills_gpu(g.shape[0], g.shape[1], g.shape[2], cnt, 4)):
+            return r
+        r = self._d_wino6
+        if r is not None and cnt >= WINO6_MIN_CO:
+            return r
+        return self._d_plain
+
+    def gelu_mask_ok(self, g, rows=None):
+        """Would dgrad(g, rows, gelu_mask=True) be honoured?  (Does the tile that call goes to apply GELU' in its mask epilogue?)"""
+        return self.wd is not None and self._dgrad_route(g, rows[1] if rows is not None else self.d_rows)[3]
+
     def dgrad(self, g, rows=None, res=None, mask=None, slope_mask=1.0, out=None, plus=None, gelu_mask=False):
         """Input gradient (+ res, masked).  plus: returns (out, out + plus) -- see fwd.  gelu_mask: multiply by GELU'(mask)
         instead of the leaky-step derivative (pointwise tile; elsewhere a separate gelu_bwd launch does it)."""
@@ -684,50 +688,27 @@ class ConvOp:
         if out is None:
             out = torch.empty((n, ho, wo, cnt), dtype=torch.float32, device=g.device)
         o2 = torch.empty_like(out) if plus is not None else None
-        two = dict(add2=plus, out2=o2) if plus is not None else {}
-        if n * g.stride(0) >= _LIM4 or n * out.stride(0) >= _LIM4:      # (see fwd)
-            step = _batch_step(n, g, res, mask, out)
-            for i in range(0, n, step):
-                j = min(n, i + step)
-                self.dgrad(g[i:j], rows, None if res is None else res[i:j], None if mask is None else mask[i:j], slope_mask,
-                           out[i:j], gelu_mask=gelu_mask)
-            return out if plus is None else (out, ops.add(out, plus, out=o2))
-        kh, kw, st, md = self.d_geo
-        pad = self.pad if self.kind == "conv" else (1 if self.kind == "down" else 0)
-        if self.kind == "conv":
-            pad = self.k - 1 - self.pad
-        # GELU' rides only in the fp32 pointwise tile (refid_conv_desc.mask_mode = 1); every other tile would silently apply
-        # the leaky-step mask instead, so a request that cannot be honoured is an error, never a wrong gradient
-        gelu_ok = self.kind == "conv" and self.d_algo == 3 and self.wds is None and not (self.wd6 is not None and self.split == 0 and cnt >= WINO6_MIN_CO) \
-            and not (self.wdp6 is not None and cnt > 32 and g.shape[3] % 16 == 0)
-        if gelu_mask and not gelu_ok:
-            raise RefidHipError(f"{self.name}: gelu_mask needs the fp32 pointwise input-gradient tile (d_algo {self.d_algo}); "
-                                f"apply ops.gelu_bwd separately")
-        if self.wds is not None and (self.kind == "conv" or _fills_gpu(n, h, w, cnt, 4)):
-            ops.conv2d(g, self.wds, out, kh=kh, kw=kw, stride=st, pad=1, mode=md, cout=cnt, cout_pad=self.sd_pad, co_base=base,
-                       res=res, mask=mask, slope_mask=slope_mask, algo=4, terms=self.split, **two)
-            return out if plus is None else (out, o2)
-        if self.wd6 is not None and self.split == 0 and cnt >= WINO6_MIN_CO:
-            ops.conv2d(g, self.wd6, out, kh=3, kw=3, stride=1, pad=1, mode=0, cout=cnt, cout_pad=self.d_pad, co_base=base,
-                       res=res, mask=mask, slope_mask=slope_mask, algo=5, terms=3 if self.w6_f16_d else 0, **two)
-            return out if plus is None else (out, o2)
-        if self.wdp6 is not None and cnt > 32 and g.shape[3] % 16 == 0:
-            ops.conv2d(g, self.wdp6, out, kh=1, kw=1, stride=1, pad=0, mode=0, cout=cnt, cout_pad=self.d_pad, co_base=base,
-                       res=res, mask=mask, slope_mask=slope_mask, algo=3, terms=6)
-            return out if plus is None else (out, ops.add(out, plus, out=o2))
-        fused_two = bool(two)                                    # was the second output handed to the tile?
-        if self.d_algo == 3 and self.kind == "convT":            # the patch GEMM: dense pixels; second output supported
-            if g.stride(2) != g.shape[3]:
-                g = g.contiguous()
-        elif self.d_algo == 3:                                    # (the 1x1 layers keep their separate skip-sum launch)
-            two, fused_two = {}, False
-            if gelu_mask:
-                two = dict(mask_mode=1)
-        ops.conv2d(g, self._fallback_wd(), out, kh=kh, kw=kw, stride=st, pad=pad, mode=md, cout=cnt, cout_pad=self.d_pad,
-                   co_base=base, res=res, mask=mask, slope_mask=slope_mask, algo=self.d_algo, **two)
-        if plus is not None and not fused_two:
+        parts = ((g, res, mask, out),)
+        if n * g.stride(0) >= _LIM4 or n * out.stride(0) >= _LIM4:
+            parts = _sub_batches(n, g, res, mask, out)
+        for g_i, res_i, mask_i, out_i in parts:
+            attr, geo, fused, gelu_ok = self._dgrad_route(g_i, cnt)
+            # every tile whose mask epilogue cannot apply GELU' would silently apply the leaky-step mask instead, so a request
+            # that cannot be honoured is an error, never a wrong gradient
+            if gelu_mask and not gelu_ok:
+                raise RefidHipError(f"{self.name}: gelu_mask needs the fp32 pointwise input-gradient tile (d_algo {self.d_algo}); "
+                                    f"apply ops.gelu_bwd separately")
+            fused = fused and plus is not None and len(parts) == 1
+            extra = dict(add2=plus, out2=o2) if fused else (dict(mask_mode=1) if gelu_mask else {})
+            if self.d_role == ops.ROLE_CONVT_DGRAD_PW and g_i.stride(2) != g_i.shape[3]:
+                g_i = g_i.contiguous()                           # the patch GEMM reads dense pixels
+            ops.conv2d(g_i, self._packed(attr), out_i, cout=cnt, co_base=base, res=res_i, mask=mask_i, slope_mask=slope_mask,
+                       **geo, **extra)
+        if plus is None:
+            return out
+        if not fused:
             ops.add(out, plus, out=o2)
-        return out if plus is None else (out, o2)
+        return out, o2
 
     # ---- weight / bias gradient ----------------------------------------------------------------
     def wgrad(self, g, a, b=None, bias=True, i_base=0):
@@ -771,7 +752,6 @@ class ConvOp:
                 # the output gradient (refid_wgrad_desc.algo 8); the direct 2x2 tile sat at 0.30 of the fp32 pipe
                 return self._wgrad_issue(g, a, None, False, 8)
             return self._wgrad_issue(g, a, None, False, 0)
-        gb = self.gb if bias else None
         algo = 1 if (USE_WINOGRAD and self.kind == "conv" and self.k == 3 and self.co >= WGRAD_WINO_MIN_CO and self.ci >= 32) else 0
         if algo == 1 and b is not None and a.shape[3] % 32 != 0:
             algo = 0          # the Winograd weight-gradient tile picks the source per 32-channel tile (base 24, 40, 48 ...)
@@ -893,12 +873,12 @@ class _Trunk:
     """ConvResidualBlocks (rsm:719-726): conv3x3 + LeakyReLU(.1), then num_block ResidualBlockNoBN (rsm:755-758; every shipped
     YAML: one)."""
 
-    def __init__(self, arena, prefix, bf16=False):
-        self.c0 = ConvOp(arena, prefix + ".0", bf16=bf16)
+    def __init__(self, arena, prefix, compute_dtype="fp32"):
+        self.c0 = ConvOp(arena, prefix + ".0", compute_dtype=compute_dtype)
         self.blocks = []
         k = 0
         while f"{prefix}.2.{k}.conv1.weight" in arena.shapes:
-            self.blocks.append((ConvOp(arena, f"{prefix}.2.{k}.conv1", bf16=bf16), ConvOp(arena, f"{prefix}.2.{k}.conv2", bf16=bf16)))
+            self.blocks.append((ConvOp(arena, f"{prefix}.2.{k}.conv1", compute_dtype=compute_dtype), ConvOp(arena, f"{prefix}.2.{k}.conv2", compute_dtype=compute_dtype)))
             k += 1
         self.c1, self.c2 = self.blocks[0]
         self.C = self.c0.co
@@ -908,15 +888,15 @@ class _Trunk:
 
 
 class _Egaca:
-    def __init__(self, arena, a, bf16=False):
+    def __init__(self, arena, a, compute_dtype="fp32"):
         self.a = a
         P, G = arena.p, arena.g
-        self.conv1 = ConvOp(arena, a + ".conv1", bf16=bf16)
-        self.conv1_e = ConvOp(arena, a + ".conv1_e", bf16=bf16)
-        self.conv3 = ConvOp(arena, a + ".conv3", scale_name=a + ".beta", bf16=bf16)
-        self.conv4 = ConvOp(arena, a + ".conv4", bf16=bf16)
-        self.conv5 = ConvOp(arena, a + ".conv5", scale_name=a + ".gamma", bf16=bf16)
-        self.side = ConvOp(arena, a + ".conv_y_side", bf16=bf16)
+        self.conv1 = ConvOp(arena, a + ".conv1", compute_dtype=compute_dtype)
+        self.conv1_e = ConvOp(arena, a + ".conv1_e", compute_dtype=compute_dtype)
+        self.conv3 = ConvOp(arena, a + ".conv3", scale_name=a + ".beta", compute_dtype=compute_dtype)
+        self.conv4 = ConvOp(arena, a + ".conv4", compute_dtype=compute_dtype)
+        self.conv5 = ConvOp(arena, a + ".conv5", scale_name=a + ".gamma", compute_dtype=compute_dtype)
+        self.side = ConvOp(arena, a + ".conv_y_side", compute_dtype=compute_dtype)
         self.c = self.conv1.ci
         # conv_y_side(y) + gamma * conv5(f4) (fm:331) as ONE 1x1 conv over the concatenated operand [f4 | y]: the two packed
         # weights are chunk-major ([chunk][row][8]) with the same row padding, so conv5's chunks followed by side's ARE the
@@ -946,13 +926,13 @@ class _Egaca:
 
 
 class _EvrLevel:
-    def __init__(self, arena, prefix, level, fuse, dead_down=False, bf16=False):
+    def __init__(self, arena, prefix, level, fuse, dead_down=False, compute_dtype="fp32"):
         self.level = level
-        self.conv = ConvOp(arena, prefix + ".conv.conv2d", bf16=bf16) if level != 1 else None
-        self.att = _Egaca(arena, prefix + ".atten_fuse", bf16=bf16) if level == 1 else None
-        self.trunk = _Trunk(arena, prefix + ".recurrent_block.forward_trunk.main", bf16=bf16)
-        self.fuse = ConvOp(arena, prefix + ".fuse_two_dir.conv2d", bf16=bf16) if fuse else None
-        self.down = None if dead_down else ConvOp(arena, prefix + ".down", kind="down", bf16=bf16)
+        self.conv = ConvOp(arena, prefix + ".conv.conv2d", compute_dtype=compute_dtype) if level != 1 else None
+        self.att = _Egaca(arena, prefix + ".atten_fuse", compute_dtype=compute_dtype) if level == 1 else None
+        self.trunk = _Trunk(arena, prefix + ".recurrent_block.forward_trunk.main", compute_dtype=compute_dtype)
+        self.fuse = ConvOp(arena, prefix + ".fuse_two_dir.conv2d", compute_dtype=compute_dtype) if fuse else None
+        self.down = None if dead_down else ConvOp(arena, prefix + ".down", kind="down", compute_dtype=compute_dtype)
         self.C = self.trunk.C
         self.q_const = self.p_fuse = self.zero_s = None     # per-forward constants of the linearity split (Engine.forward)
 
@@ -985,35 +965,32 @@ class Engine:
         # "bf16x3": fp32 tensors, fp32 accumulation; the 3x3 forward / input-gradient convs multiply on the bf16 matrix
         # cores with every operand split in two bf16 numbers and three products per fp32 product (2^-16 relative per
         # product, 64x finer than TF32); weight gradients and everything else as in "fp32".  Explicit opt-in.
-        ConvOp.default_split = 3 if compute_dtype == "bf16x3" else 0
         # "bf16": BASELINE config 3 -- conv forward / input-gradient operands in bf16 on the matrix cores,
         # fp32 accumulation, fp32 master weights, activations, weight gradients, loss, grad-norm, optimizer
-        self.compute_dtype = compute_dtype
-        bf = compute_dtype == "bf16"
+        self.compute_dtype = cd = compute_dtype
         self.img_chn, self.ev_chn, self.out_chn, self.base = img_chn, ev_chn, out_chn, base
         self.nres = num_residual_blocks
         self.device = torch.device(device)
         self.shapes = param_shapes(img_chn, ev_chn, out_chn, base, num_residual_blocks, num_block, NL)
         self.arena = A = ParamArena(self.shapes, self.device)
-        self.head_ev = ConvOp(A, "head.conv2d", need_dgrad=False, bf16=bf)
-        self.head_img = ConvOp(A, "head_img.conv2d", need_dgrad=False, bf16=bf)
-        self.enc_b = [_EvrLevel(A, f"encoders_backward.{i}", i, False, dead_down=(i == NL - 1), bf16=bf) for i in range(NL)]
-        self.enc_f = [_EvrLevel(A, f"encoders_forward.{i}", i, True, bf16=bf) for i in range(NL)]
+        self.head_ev = ConvOp(A, "head.conv2d", need_dgrad=False, compute_dtype=cd)
+        self.head_img = ConvOp(A, "head_img.conv2d", need_dgrad=False, compute_dtype=cd)
+        self.enc_b = [_EvrLevel(A, f"encoders_backward.{i}", i, False, dead_down=(i == NL - 1), compute_dtype=cd) for i in range(NL)]
+        self.enc_f = [_EvrLevel(A, f"encoders_forward.{i}", i, True, compute_dtype=cd) for i in range(NL)]
         self.img = []
         for i in range(NL):
             p = f"img_encoders.{i}"
-            self.img.append(dict(identity=ConvOp(A, p + ".identity", bf16=bf), conv_1=ConvOp(A, p + ".conv_1", bf16=bf),
-                                 conv_2=ConvOp(A, p + ".conv_2", bf16=bf),
-                                 down=ConvOp(A, p + ".down", kind="down", bf16=bf)))
-        self.res = [(ConvOp(A, f"resblocks.{i}.conv1", bf16=bf), ConvOp(A, f"resblocks.{i}.conv2", bf16=bf))
+            self.img.append(dict(identity=ConvOp(A, p + ".identity", compute_dtype=cd), conv_1=ConvOp(A, p + ".conv_1", compute_dtype=cd),
+                                 conv_2=ConvOp(A, p + ".conv_2", compute_dtype=cd),
+                                 down=ConvOp(A, p + ".down", kind="down", compute_dtype=cd)))
+        self.res = [(ConvOp(A, f"resblocks.{i}.conv1", compute_dtype=cd), ConvOp(A, f"resblocks.{i}.conv2", compute_dtype=cd))
                     for i in range(self.nres)]
         self.dec = []
         for j in range(NL):
             p = f"decoders.{j}"
-            self.dec.append(dict(t2=ConvOp(A, p + ".transposed_conv2d", kind="convT", bf16=bf),
-                                 trunk=_Trunk(A, p + ".forward_trunk.main", bf16=bf)))
-        self.pred = ConvOp(A, "pred.conv2d", bf16=bf)
-        ConvOp.default_split = 0                   # (a construction-time context, not a setting other engines inherit)
+            self.dec.append(dict(t2=ConvOp(A, p + ".transposed_conv2d", kind="convT", compute_dtype=cd),
+                                 trunk=_Trunk(A, p + ".forward_trunk.main", compute_dtype=cd)))
+        self.pred = ConvOp(A, "pred.conv2d", compute_dtype=cd)
         self.all_ops = [self.head_ev, self.head_img, self.pred]
         for lv in self.enc_b + self.enc_f:
             self.all_ops += lv.ops()
@@ -1166,7 +1143,7 @@ class Engine:
         it to that list (summed once per sweep: Engine.backward_early / backward_late)."""
         e = st["eg"]
         A.conv5.wgrad(g_u, e["f4"])
-        if A.conv5.d_algo == 3 and A.conv5.wdp6 is None and LINEAR_SPLIT:
+        if LINEAR_SPLIT and A.conv5.gelu_mask_ok(g_u):
             g_c4 = A.conv5.dgrad(g_u, mask=e["c4"], gelu_mask=True)      # GELU' rides in the tile's mask epilogue
         else:
             g_f4 = A.conv5.dgrad(g_u)

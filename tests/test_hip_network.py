@@ -389,7 +389,7 @@ def test_batched_weight_packing_equals_the_one_by_one_calls(dtype):
     net = FinalBidirectionAttenfusion(img_chn=6, ev_chn=2, out_chn=3, num_encoders=3, base_num_channels=16, num_block=1,
                                       num_residual_blocks=2, compute_dtype=dtype).cuda()
     eng = net.engine
-    names = ("wp", "wd", "wpp6", "wdp6", "wp6", "wd6", "wps", "wds", "b_eff")
+    names = ("wp", "wd", "wp6", "wd6", "wps", "wds", "b_eff")
 
     def snapshot():
         out = []

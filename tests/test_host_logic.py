@@ -436,6 +436,58 @@ def test_batched_finish_always_flushes_and_fallback_packs_stay_out_of_the_plan(m
     assert eng.pred.wp6 is not None and eng.pred.f_algo == 0 and not eng.pred.wp_lazy      # thin output on the Winograd x six form
 
 
+def test_convop_gelu_mask_and_skip_sum_follow_the_tile_route(monkeypatch):
+    """Every conv of Engine(26), launches recorded instead of issued: dgrad(..., gelu_mask=True) is ONE conv2d on the fp32
+    pointwise tile with mask_mode 1 where ConvOp.gelu_mask_ok() says yes, and an error without a launch where it says no (never
+    the leaky-step mask in GELU's place); a fwd / dgrad call with `plus` is followed by ops.add exactly when the tile was not
+    handed the second output.  conv5 of every EGACA level answers as Engine._egaca_bwd's former `d_algo == 3` did."""
+    import torch
+    from refid_amd import engine, ops
+    from refid_amd._lib import RefidHipError
+    calls = []
+    monkeypatch.setattr(ops, "conv2d", lambda a, w, out, **kw: calls.append(("conv2d", kw)))
+    monkeypatch.setattr(ops, "add", lambda a, b, out=None: calls.append(("add", out)) or out)
+    for nm in ("pack_conv_weights", "pack_conv_weights_bf16", "pack_conv_weights_split", "pack_conv_weights_wino6", "mul_vec"):
+        monkeypatch.setattr(ops, nm, lambda *a, **kw: None)
+    eng = engine.Engine(26, device="cpu")
+    answers = set()
+    for o in eng.all_ops:
+        n, h, w = 1, 8, 32
+        sc = {"conv": 1, "down": 2, "convT": 0.5}[o.kind]
+        src = torch.zeros(n, h, w, o.ci)
+        y = torch.zeros(n, int(h / sc), int(w / sc), o.co)
+        calls.clear()
+        out, o2 = o.fwd(src, plus=y)
+        assert [c[0] for c in calls] == ["conv2d"] + ["add"] * ("out2" not in calls[0][1]), o.name
+        assert o2 is (calls[0][1]["out2"] if len(calls) == 1 else calls[1][1])
+        if o.wd is None:
+            continue
+        for rows in [None] + ([(0, o.co), (o.co, o.co)] if o.kind == "conv" and o.ci == 2 * o.co else []):
+            x = torch.zeros(n, h, w, o.d_rows if rows is None else rows[1])
+            calls.clear()
+            out, o2 = o.dgrad(y, rows=rows, plus=x)
+            assert [c[0] for c in calls] == ["conv2d"] + ["add"] * ("out2" not in calls[0][1]), o.name
+            assert o2 is (calls[0][1]["out2"] if len(calls) == 1 else calls[1][1])
+            calls.clear()
+            ok = o.gelu_mask_ok(y, rows)
+            answers.add(ok)
+            if ok:
+                o.dgrad(y, rows=rows, mask=x, gelu_mask=True)
+                assert [c[0] for c in calls] == ["conv2d"], o.name
+                kw = calls[0][1]
+                assert (kw["algo"], kw.get("terms", 0), kw["mask_mode"]) == (3, 0, 1), o.name
+            else:
+                with pytest.raises(RefidHipError, match="gelu_mask"):
+                    o.dgrad(y, rows=rows, mask=x, gelu_mask=True)
+                assert calls == [], o.name
+    assert answers == {True, False}
+    atts = [lv.att for lv in eng.enc_b + eng.enc_f if lv.att is not None]
+    assert len(atts) == 2
+    for A in atts:
+        g = torch.zeros(1, 8, 32, A.conv5.co)
+        assert A.conv5.gelu_mask_ok(g) == (A.conv5.d_algo == 3) and A.conv5.gelu_mask_ok(g)
+
+
 def test_weight_gradient_group_is_capped_by_free_memory():
     """engine.wgrad_group_cap: a waiting weight-gradient call keeps its step's tensors alive (~4.9 KB per pixel and
     step); the group shrinks when the operands of `n` steps would not fit into half of the free HBM instead of running out of
