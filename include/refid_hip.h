@@ -140,7 +140,10 @@ typedef struct refid_conv_desc {
                                                    refid_pack_conv_weights_wino6): the fp32 Winograd tile's result to
                                                    fp32 rounding at 2.67x fewer matrix-pipe cycles -- or, with
                                                    mfma_terms = 3, THREE fp16 products on two-plane operands (22 bits;
-                                                   w_packed from refid_pack_conv_weights_wino3h): half the MFMAs again  */
+                                                   w_packed from refid_pack_conv_weights_wino3h): half the MFMAs again -- or, with
+                                                   mfma_terms = 1, ONE fp16 product on one-plane operands (11 bits: a reduced-
+                                                   precision form; w_packed from refid_pack_conv_weights_wino1h): a third of
+                                                   those MFMAs, half the weight bytes  */
     int split_k;                                /* small problems (few output tiles, long K): split K over the grid into
                                                    `ws` partial sums + a finishing pass.  0 = never; 1 = decided by the
                                                    per-sample geometry (a sample's bits do not depend on the batch
@@ -332,10 +335,16 @@ int refid_pack_conv_weights_wino6(const float* w, const float* oscale, void* pac
 size_t refid_packed_weight_wino3h_bytes(int role, int o, int i, int bn);
 int refid_pack_conv_weights_wino3h(const float* w, const float* oscale, void* packed, int role, int o, int i, int bn,
                                    void* stream);
+/* The same U for refid_conv2d algo 5 with mfma_terms = 1: the same 64-byte header and scale, followed by the high plane only,
+ *   [chunk of 16 input channels][xi = 0..15][rows padded to bn = 64][16]  (fp16),  rne16(U 2^eU).
+ * Half the bytes of the two-plane packing after the header.  `packed` must be 16-byte aligned. */
+size_t refid_packed_weight_wino1h_bytes(int role, int o, int i, int bn);
+int refid_pack_conv_weights_wino1h(const float* w, const float* oscale, void* packed, int role, int o, int i, int bn,
+                                   void* stream);
 /* All packings of a model in ONE launch.  The caller builds a table of refid_pack_entry_bytes()-sized records in host
  * memory with refid_pack_entry_fill (kind 0: refid_pack_conv_weights[_scaled / _bf16] -- `planes` = 1 selects bf16 output;
  * 1: refid_pack_conv_weights_split, 3x3 / 4x4; 2: the same, 1x1; 3: refid_pack_conv_weights_wino6; 4: dst[e] = w[e] *
- * oscale[e] for e < o (refid_mul_vec); 5: refid_pack_conv_weights_wino3h; 6: refid_pack_conv_weights_split_f16), copies it to
+ * oscale[e] for e < o (refid_mul_vec); 5: refid_pack_conv_weights_wino3h, or -- `planes` = 1 -- refid_pack_conv_weights_wino1h; 6: refid_pack_conv_weights_split_f16), copies it to
  * device memory once, and calls
  * refid_pack_batch whenever the weights have changed -- after refid_pack_batch_prepass on the same stream when the table holds
  * kind-5 / kind-6 records (their scale exponents: one workgroup per record, a no-op for the other kinds).  `blk0` = the sum of the values returned for the records before this one (each call returns its record's

@@ -135,6 +135,9 @@ def _bind_extra(L):
     L.refid_packed_weight_wino3h_bytes.argtypes = [i] * 4
     L.refid_packed_weight_wino3h_bytes.restype = C.c_size_t
     L.refid_pack_conv_weights_wino3h.argtypes = [vp, vp, vp] + [i] * 4 + [vp]
+    L.refid_packed_weight_wino1h_bytes.argtypes = [i] * 4
+    L.refid_packed_weight_wino1h_bytes.restype = C.c_size_t
+    L.refid_pack_conv_weights_wino1h.argtypes = [vp, vp, vp] + [i] * 4 + [vp]
     L.refid_pack_batch_prepass.argtypes = [vp, i, vp]
     L.refid_packed_weight_split_f16_bytes.argtypes = [i] * 6
     L.refid_packed_weight_split_f16_bytes.restype = C.c_size_t

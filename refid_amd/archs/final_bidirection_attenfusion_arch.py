@@ -32,11 +32,13 @@ class FinalBidirectionAttenfusion(nn.Module):
                  use_recurrent_upsample_conv=True, num_block=3, use_first_dcn=False, use_reversed_voxel=False,
                  compute_dtype='fp32'):
         """compute_dtype (extension, keyword-only in practice; YAML: network_g.compute_dtype): 'fp32'
-        (default, the reference's arithmetic) or 'bf16' (BASELINE config 3: bf16 matrix-core operands for
-        the conv forward / input gradients, fp32 everything else)."""
+        (default, the reference's arithmetic), 'bf16' (BASELINE config 3: bf16 matrix-core operands for
+        the conv forward / input gradients, fp32 everything else), 'bf16x3' (three bf16 products per fp32
+        product) or 'fp16' (the bf16 mode with the 3x3 convs on the Winograd tile's one-fp16-product form:
+        11-bit operands on 4/9 of the multiplies)."""
         super().__init__()
-        if compute_dtype not in ('fp32', 'bf16x3', 'bf16'):
-            raise ValueError(f"compute_dtype must be 'fp32', 'bf16x3' or 'bf16', got {compute_dtype!r}")
+        if compute_dtype not in ('fp32', 'bf16x3', 'bf16', 'fp16'):
+            raise ValueError(f"compute_dtype must be 'fp32', 'bf16x3', 'bf16' or 'fp16', got {compute_dtype!r}")
         self.compute_dtype = compute_dtype
         assert ev_chn > 0 and img_chn > 0 and out_chn > 0                      # arch:45-47
         unsupported = []

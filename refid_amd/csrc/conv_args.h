@@ -40,7 +40,8 @@ int refid_launch_splitk_finish(const ConvKArgs& f, const float* ws, int ldW, lon
 // conv_wino6.hip: Winograd F(2x2,3x3) with six bf16 products per fp32 product (algo 5)
 bool refid_wino6_eligible(const ConvKArgs& a);
 size_t refid_wino6_workspace_bytes(const ConvKArgs& a, int split_mode);
-// terms: 0 / 6 = six bf16 products (three planes per operand), 3 = three fp16 products (two planes, scaled operands)
+// terms: 0 / 6 = six bf16 products (three planes per operand), 3 = three fp16 products (two planes, scaled operands),
+//        1 = one fp16 product (one plane, the same scaling)
 int refid_launch_wino6(const ConvKArgs& a, float* ws, size_t ws_bytes, int split_mode, int tile_hint, int terms, hipStream_t st);
 // conv_split.hip: direct 3x3 tile with split-bf16 operands (algo 4); terms = 6 (fp32-class products) or 3
 bool refid_split3x3_eligible(const ConvKArgs& a);

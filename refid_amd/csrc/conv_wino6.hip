@@ -28,6 +28,12 @@
 //     largest keep all 22 bits; smaller ones an ABSOLUTE error of 2^-32 of the largest, far below the 2^-22 of the large terms
 //     they are added to.  The output transform undoes 2^(7 - E + eU) per lane with v_ldexp before the rows meet in LDS.
 //
+// ONE fp16 product (template parameter ONE, refid_conv_desc.mfma_terms = 1; compute_dtype 'fp16'): the same scaling, reference
+// exponent, online rescale and un-scale, but V is rounded ONCE (RNE, v_cvt_pk_f16_f32) and U travels as its high plane only
+// (refid_pack_conv_weights_wino1h: half the U bytes, one 16-byte load per channel tile): one MFMA per (column, channel tile), a
+// third of the three-product form's.  11 significand bits per operand -- a reduced-precision mode, finer than bf16 operands
+// on the direct tile (8 bits) although the transforms amplify the rounding: DESIGN.md section 3.9.
+//
 //   out = mask( post( pre(conv3x3(src) + bias) + res ) ),  src = in_a or [in_a | in_b]
 // (same contract, epilogue, split-K form and XCD-aware work mapping as conv_wino.hip; serves the forward conv and,
 // on the flipped/transposed weights, the input gradient.)
@@ -109,16 +115,30 @@ __device__ __forceinline__ void split8h(const f32x4& v0, const f32x4& v1, f32x4 
     pl[1] = __builtin_bit_cast(f32x4, l);
 }
 
+// v (8 fp32 channels, already scaled into fp16's range) -> ONE fp16 plane, rounded to nearest even (4 VALU)
+__device__ __forceinline__ void round8h(const f32x4& v0, const f32x4& v1, f32x4 (&pl)[3]) {
+    f16x8 h;
+#pragma unroll
+    for (int k = 0; k < 8; k += 2) {
+        const f32x2 ab = {k < 4 ? v0[k] : v1[k - 4], k < 4 ? v0[k + 1] : v1[k - 3]};
+        const f16x2 hh = __builtin_convertvector(ab, f16x2);                  // v_cvt_pk_f16_f32 (RNE)
+        h[k] = hh[0]; h[k + 1] = hh[1];
+    }
+    pl[0] = __builtin_bit_cast(f32x4, h);
+}
+
 // NT = 2: 64 output channels per workgroup (8 accumulators per wave, two workgroups per CU).
 // NT = 1: the 32-output-channel layers (decoder 2's trunk, the input gradient of level 0's first conv; round 4 -- they ran
 //         on the fp32 Winograd tile at 0.36 of the fp32 roof): 4 accumulators per wave, three workgroups per CU; every V
 //         split feeds 6 instead of 12 MFMAs, so this form is vector-issue bound -- and still well ahead of 64 fp32 MFMAs.
 // F16: the three-fp16-product form (two planes per operand, online power-of-two scaling: see the top of the file)
-template <int NT, bool F16>
+// ONE (with F16): its one-product form -- one fp16 plane per operand, no residual split
+template <int NT, bool F16, bool ONE = false>
 __global__ __launch_bounds__(256, NT == 2 ? 2 : 3) void conv_wino6_kernel(const ConvKArgs a) {
     constexpr int BN = 32 * NT;
-    constexpr int NPL = F16 ? 2 : 3;                        // planes per operand
-    constexpr int NPR = (REFID_WINO6_ABLATE == 14 || REFID_WINO6_ABLATE == 15) ? 3 : (F16 ? 3 : 6);   // products kept
+    static_assert(F16 || !ONE, "the one-product form is an fp16 form");
+    constexpr int NPL = ONE ? 1 : (F16 ? 2 : 3);            // planes per operand
+    constexpr int NPR = ONE ? 1 : ((REFID_WINO6_ABLATE == 14 || REFID_WINO6_ABLATE == 15) ? 3 : (F16 ? 3 : 6));   // products kept
     extern __shared__ __attribute__((aligned(16))) char smem[];
     f32x4* sR = reinterpret_cast<f32x4*>(smem);            // two raw halo buffers
 
@@ -222,7 +242,7 @@ __global__ __launch_bounds__(256, NT == 2 ? 2 : 3) void conv_wino6_kernel(const 
         const bool in = ch < kc1;
         const int so = (REFID_WINO6_ABLATE == 1 ? 0 : ch) * uChunk + j * uXi;
 #pragma unroll
-        for (int p = 0; p < ((REFID_WINO6_ABLATE == 14 || REFID_WINO6_ABLATE == 15) ? 2 : NPL); ++p)
+        for (int p = 0; p < ((REFID_WINO6_ABLATE == 14 || REFID_WINO6_ABLATE == 15) && !ONE ? 2 : NPL); ++p)
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
                 if (REFID_WINO6_ABLATE == 13 && nt == 1) { dst[p][nt] = dst[p][0]; continue; }
@@ -314,6 +334,7 @@ __global__ __launch_bounds__(256, NT == 2 ? 2 : 3) void conv_wino6_kernel(const 
                       : (j == 2) ? t[qq][2] - t[qq][1] : t[qq][1] - t[qq][3];
             if (REFID_WINO6_ABLATE == 2 || REFID_WINO6_ABLATE == 15) { pl[0] = v[0]; pl[1] = v[1]; pl[2] = t[0][j]; }
             else if (F16 && REFID_WINO6_ABLATE == 18) { pl[0] = v[0]; pl[1] = v[1]; }
+            else if constexpr (ONE) round8h(v[0], v[1], pl);
             else if constexpr (F16) split8h(v[0], v[1], pl);
             else split8(v[0], v[1], pl);
 #pragma unroll
@@ -518,18 +539,19 @@ Wino6Plan wino6_plan(ConvKArgs& a, int split_mode, int tile_hint = 0) {
     return p;
 }
 
-template <int NT, bool F16>
+template <int NT, bool F16, bool ONE = false>
 int launch_wino6_t(const ConvKArgs& a, dim3 grid, hipStream_t st, const char* what) {
     static std::atomic<unsigned long long> done{0};
-    if (int rc = refid_lds_attr_once(done, &conv_wino6_kernel<NT, F16>, lds_bytes(NT), "conv_wino6")) return rc;
-    hipLaunchKernelGGL((conv_wino6_kernel<NT, F16>), grid, dim3(256), lds_bytes(NT), st, a);
+    if (int rc = refid_lds_attr_once(done, &conv_wino6_kernel<NT, F16, ONE>, lds_bytes(NT), "conv_wino6")) return rc;
+    hipLaunchKernelGGL((conv_wino6_kernel<NT, F16, ONE>), grid, dim3(256), lds_bytes(NT), st, a);
     REFID_LAUNCH_CHECK(what);
     return 0;
 }
 
 template <int NT>
-int launch_wino6(const ConvKArgs& a, bool f16, dim3 grid, hipStream_t st, const char* what) {
-    return f16 ? launch_wino6_t<NT, true>(a, grid, st, what) : launch_wino6_t<NT, false>(a, grid, st, what);
+int launch_wino6(const ConvKArgs& a, int terms, dim3 grid, hipStream_t st, const char* what) {
+    if (terms == 1) return launch_wino6_t<NT, true, true>(a, grid, st, what);
+    return terms == 3 ? launch_wino6_t<NT, true>(a, grid, st, what) : launch_wino6_t<NT, false>(a, grid, st, what);
 }
 
 }  // namespace
@@ -555,9 +577,10 @@ size_t refid_wino6_workspace_bytes(const ConvKArgs& ka, int split_mode) {
 
 int refid_launch_wino6(const ConvKArgs& ka, float* ws, size_t ws_bytes, int split_mode, int tile_hint, int terms, hipStream_t st) {
     ConvKArgs a = ka;
-    REFID_CHECK(terms == 0 || terms == 6 || terms == 3, "conv2d: algo 5 takes mfma_terms 0 / 6 (six bf16 products) or 3 (three fp16 "
-                "products, w_packed from refid_pack_conv_weights_wino3h), got %d", terms);
-    const bool f16 = terms == 3;
+    REFID_CHECK(terms == 0 || terms == 6 || terms == 3 || terms == 1, "conv2d: algo 5 takes mfma_terms 0 / 6 (six bf16 products), 3 "
+                "(three fp16 products, w_packed from refid_pack_conv_weights_wino3h) or 1 (one fp16 product, w_packed from "
+                "refid_pack_conv_weights_wino1h), got %d", terms);
+    const bool f16 = terms == 3 || terms == 1;
     REFID_CHECK(!f16 || (reinterpret_cast<uintptr_t>(a.w) & 15) == 0, "conv2d: the fp16 Winograd packing must be 16-byte aligned");
     REFID_CHECK(refid_wino6_eligible(a),
                 "conv2d: the Winograd six-product tile needs input-channel counts that are multiples "
@@ -567,7 +590,7 @@ int refid_launch_wino6(const ConvKArgs& ka, float* ws, size_t ws_bytes, int spli
     const Wino6Plan pl = wino6_plan(a, ws ? split_mode : 0, tile_hint);
     dim3 grid = pl.grid;
     const int ks = pl.ks;
-    if (ks == 1) return pl.nt == 2 ? launch_wino6<2>(a, f16, grid, st, "conv_wino6") : launch_wino6<1>(a, f16, grid, st, "conv_wino6/32");
+    if (ks == 1) return pl.nt == 2 ? launch_wino6<2>(a, terms, grid, st, "conv_wino6") : launch_wino6<1>(a, terms, grid, st, "conv_wino6/32");
     const long long npix = (long long)a.N * a.Ho * a.Wo;
     const int ldW = round_up(a.Cout, 4);
     const size_t need = (size_t)ks * npix * ldW * sizeof(float);
@@ -579,7 +602,7 @@ int refid_launch_wino6(const ConvKArgs& ka, float* ws, size_t ws_bytes, int spli
     ConvKArgs p = a;                       // partial pass: raw sums into the workspace (the finishing pass writes out / out2)
     p.ksplit = ks; p.wsStride = npix * ldW; p.out = ws; p.ldO = ldW; p.out2 = nullptr;
     grid.y = ks;
-    if (int rc = pl.nt == 2 ? launch_wino6<2>(p, f16, grid, st, "conv_wino6/splitk") : launch_wino6<1>(p, f16, grid, st, "conv_wino6/32/splitk"))
+    if (int rc = pl.nt == 2 ? launch_wino6<2>(p, terms, grid, st, "conv_wino6/splitk") : launch_wino6<1>(p, terms, grid, st, "conv_wino6/32/splitk"))
         return rc;
     ConvKArgs f = a;
     f.ksplit = ks; f.wsStride = npix * ldW;

@@ -426,6 +426,8 @@ __device__ __forceinline__ void pack_absmax_block(const PackArgs& p) {       // 
 __global__ __launch_bounds__(1024) void pack_absmax_kernel(const PackArgs p) { pack_absmax_block(p); }
 
 // one thread per WEIGHT, as pack_wino6_weight: nine loads, the 16 transform points once, 32 two-byte stores
+// NPL = 1: the high plane only ([chunk16][xi][rowsPad][16]: conv_wino6.hip's one-product form, mfma_terms 1), 16 stores
+template <int NPL = 2>
 __device__ __forceinline__ void pack_wino3h_weight(const PackArgs& p, unsigned f) {
     const unsigned k16 = f & 15, r = f >> 4;
     const unsigned row = r % (unsigned)p.rowsPad, chunk = r / (unsigned)p.rowsPad;
@@ -456,13 +458,13 @@ __device__ __forceinline__ void pack_wino3h_weight(const PackArgs& p, unsigned f
     }
     const long long plane = (long long)p.rowsPad * 16;
     _Float16* dst = reinterpret_cast<_Float16*>(reinterpret_cast<char*>(p.dst) + W3H_HEADER) +
-                    ((long long)chunk * 32 * p.rowsPad + row) * 16 + k16;
+                    ((long long)chunk * (16 * NPL) * p.rowsPad + row) * 16 + k16;
 #pragma unroll
     for (int xi = 0; xi < 16; ++xi) {
         const float v = u[xi];
         const _Float16 h = (_Float16)v;
-        dst[(xi * 2 + 0) * plane] = h;
-        dst[(xi * 2 + 1) * plane] = (_Float16)(v - (float)h);
+        dst[(xi * NPL + 0) * plane] = h;
+        if (NPL == 2) dst[(xi * NPL + 1) * plane] = (_Float16)(v - (float)h);
     }
 }
 
@@ -471,12 +473,17 @@ __global__ __launch_bounds__(256) void pack_wino3h_kernel(const PackArgs p) {
     for (unsigned f = blockIdx.x * 256u + threadIdx.x; f < total; f += gridDim.x * 256u) pack_wino3h_weight(p, f);
 }
 
+__global__ __launch_bounds__(256) void pack_wino1h_kernel(const PackArgs p) {
+    const unsigned total = (unsigned)p.nchunks * p.rowsPad * 16;
+    for (unsigned f = blockIdx.x * 256u + threadIdx.x; f < total; f += gridDim.x * 256u) pack_wino3h_weight<1>(p, f);
+}
+
 // ---- all packings of a model in ONE launch (refid_pack_batch): the table lives in device memory, a workgroup finds its
 // entry by binary search over the entries' first block.  ~220 dependent 6-20 us launches per optimiser step become one.
 struct PackEntry {
     PackArgs p;
     int kind;                  // 0 pack_kernel (fp32 / bf16), 1 split (modes 0-2), 2 1x1 split, 3 Winograd x six, 4 out = a * b (vectors),
-                               // 5 Winograd x three fp16 products, 6 split tile with two fp16 planes (modes 0-2): both need
+                               // 5 Winograd x three fp16 products (planes = 1: the one-product form's single plane), 6 split tile with two fp16 planes (modes 0-2): both need
                                // refid_pack_batch_prepass before the batch (their scale exponents)
     int planes, mode;
     int blk0, nblk;            // this entry's workgroups: [blk0, blk0 + nblk)
@@ -496,6 +503,8 @@ __global__ __launch_bounds__(256) void pack_batch_kernel(const PackEntry* __rest
     const long long e0 = (long long)(blockIdx.x - en.blk0) * 256 + threadIdx.x;
     if (kind == 3) {                                         // (total = weights, < 2^31: refid_pack_entry_fill)
         for (unsigned f = (unsigned)e0; f < (unsigned)total; f += (unsigned)stride) pack_wino6_weight(p, f);
+    } else if (kind == 5 && planes == 1) {
+        for (unsigned f = (unsigned)e0; f < (unsigned)total; f += (unsigned)stride) pack_wino3h_weight<1>(p, f);
     } else if (kind == 5) {
         for (unsigned f = (unsigned)e0; f < (unsigned)total; f += (unsigned)stride) pack_wino3h_weight(p, f);
     } else if (kind == 6) {
@@ -690,6 +699,30 @@ extern "C" int refid_pack_conv_weights_wino3h(const float* w, const float* oscal
     return 0;
 }
 
+extern "C" size_t refid_packed_weight_wino1h_bytes(int role, int o, int i, int bn) {
+    PackArgs p;
+    if (role != REFID_ROLE_WINO_FWD && role != REFID_ROLE_WINO_DGRAD) return 0;
+    if (pack_geometry(role, o, i, 3, 3, 16, bn, &p)) return 0;
+    return (size_t)W3H_HEADER + (size_t)p.nchunks * 16 * p.rowsPad * 16 * 2;
+}
+
+extern "C" int refid_pack_conv_weights_wino1h(const float* w, const float* oscale, void* packed, int role, int o, int i,
+                                              int bn, void* stream) {
+    PackArgs p;
+    REFID_CHECK(w && packed, "pack_wino1h: null pointer");
+    REFID_CHECK((reinterpret_cast<uintptr_t>(packed) & 15) == 0, "pack_wino1h: the packing must be 16-byte aligned");
+    REFID_CHECK(role == REFID_ROLE_WINO_FWD || role == REFID_ROLE_WINO_DGRAD, "pack_wino1h: Winograd roles only");
+    REFID_CHECK(pack_geometry(role, o, i, 3, 3, 16, bn, &p) == 0, "pack_wino1h: bad geometry");
+    p.w = w; p.dst = reinterpret_cast<float*>(packed); p.oscale = oscale; p.bf16 = 1;
+    const long long total = (long long)p.nchunks * p.rowsPad * 16;                 // one thread per weight
+    REFID_CHECK(total * 16 < 0x7fffffffLL, "pack_wino1h: packing of %lld elements exceeds the 32-bit index range", total * 16);
+    hipLaunchKernelGGL(pack_absmax_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, p);
+    REFID_LAUNCH_CHECK("pack_conv_weights_wino1h/absmax");
+    hipLaunchKernelGGL(pack_wino1h_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, p);
+    REFID_LAUNCH_CHECK("pack_conv_weights_wino1h");
+    return 0;
+}
+
 // ---- batched packing ------------------------------------------------------------------------------------------------
 extern "C" size_t refid_pack_entry_bytes(void) { return sizeof(PackEntry); }
 
@@ -752,9 +785,10 @@ extern "C" int refid_pack_entry_fill(void* entry_host, int kind, const float* w,
     } else if (kind == 5) {
         REFID_FILL_CHECK((role == REFID_ROLE_WINO_FWD || role == REFID_ROLE_WINO_DGRAD) && kh == 3 && kw == 3, "pack_entry_fill: Winograd roles, 3x3");
         REFID_FILL_CHECK((reinterpret_cast<uintptr_t>(dst) & 15) == 0, "pack_entry_fill: the fp16 Winograd packing must be 16-byte aligned");
+        REFID_FILL_CHECK(planes == 1 || planes == 2, "pack_entry_fill: kind 5 takes planes = 2 (three fp16 products) or 1 (one), got %d", planes);
         REFID_FILL_CHECK(pack_geometry(role, o, i, 3, 3, 16, bn, &p) == 0, "pack_entry_fill: unknown role %d", role);
         p.bf16 = 1;
-        en.total = (long long)p.nchunks * p.rowsPad * 16;    // WEIGHTS (one thread each writes its 32 plane entries)
+        en.total = (long long)p.nchunks * p.rowsPad * 16;    // WEIGHTS (one thread each writes its 32 / 16 plane entries)
         REFID_FILL_CHECK(en.total * 32 < 0x7fffffffLL, "pack_entry_fill: Winograd x three packing exceeds the 32-bit index range");
     } else {
         REFID_FILL_CHECK(false, "pack_entry_fill: unknown kind %d", kind);

@@ -343,7 +343,7 @@ class _Packing:
     """One packed copy of a conv's weights: the ConvOp attribute that holds the buffer (by name: _Egaca re-binds conv5.wp and
     side.wp to halves of one buffer), the packer ("pack": the fp32 / bf16 tile layouts, "split": bf16 / fp16 planes of the
     direct tile, "wino6": planes of U = G g G^T) and that packer's arguments after the weight; `flag` is bf16 for "pack",
-    f16 for the plane forms.  lazy: a fallback layout the batched repack leaves out (ConvOp._packed writes it on demand)."""
+    f16 for "split", the product terms (0 = six bf16, 3 = three fp16, 1 = one fp16) for "wino6".  lazy: a fallback layout the batched repack leaves out (ConvOp._packed writes it on demand)."""
     __slots__ = ("attr", "form", "args", "flag", "lazy", "epoch")
 
     def __init__(self, attr, form, args, flag=False):
@@ -352,12 +352,14 @@ class _Packing:
     def alloc(self, device):
         if self.form == "pack":
             return torch.empty(ops.packed_weight_floats(*self.args), dtype=torch.bfloat16 if self.flag else torch.float32, device=device)
-        return torch.empty(self.nbytes() // 2, dtype=torch.bfloat16, device=device)
+        one_plane = self.form == "wino6" and self.flag == 1    # (ops.conv2d tells the one-plane Winograd packing by its type)
+        return torch.empty(self.nbytes() // 2, dtype=torch.float16 if one_plane else torch.bfloat16, device=device)
 
     def nbytes(self):
         """Size of a plane-form packing (also what its 2 GiB guard looks at)."""
-        size = ops.packed_weight_split_bytes if self.form == "split" else ops.packed_weight_wino6_bytes
-        return size(*self.args, self.flag)
+        if self.form == "split":
+            return ops.packed_weight_split_bytes(*self.args, self.flag)
+        return ops.packed_weight_wino6_bytes(*self.args, terms=self.flag)
 
     def pack(self, op):
         out = getattr(op, self.attr)
@@ -366,7 +368,7 @@ class _Packing:
         elif self.form == "split":
             ops.pack_conv_weights_split(op.w, *self.args[:-1], planes=self.args[-1], out=out, oscale=op.scale, f16=self.flag)
         else:
-            ops.pack_conv_weights_wino6(op.w, *self.args, out=out, oscale=op.scale, f16=self.flag)
+            ops.pack_conv_weights_wino6(op.w, *self.args, out=out, oscale=op.scale, terms=self.flag)
         self.epoch = op.arena.pack_epoch
 
     def plan(self, op, plan):
@@ -376,7 +378,7 @@ class _Packing:
         elif self.form == "split":
             plan.add_split(op.w, *self.args, out, oscale=op.scale, f16=self.flag)
         else:
-            plan.add_wino6(op.w, *self.args, out, oscale=op.scale, f16=self.flag)
+            plan.add_wino6(op.w, *self.args, out, oscale=op.scale, terms=self.flag)
 
 
 class ConvOp:
@@ -384,7 +386,10 @@ class ConvOp:
 
     def __init__(self, arena, name, kind="conv", need_dgrad=True, scale_name=None, compute_dtype="fp32"):
         self.arena, self.name, self.kind = arena, name, kind
-        bf16 = self.bf16 = compute_dtype == "bf16"
+        # "fp16": the bf16 mode's tiles, except that the 3x3 calls the fp32 mode sends to the Winograd fp16 tile run on that
+        # tile's ONE-product form (one fp16 plane per operand: 11 significand bits on 4/9 of the direct conv's multiplies)
+        fp16 = self.fp16 = compute_dtype == "fp16"
+        bf16 = self.bf16 = compute_dtype == "bf16" or fp16
         self.split = 0                        # product terms of the split-bf16 tile (algo 4) this conv may use
         self.w = arena.p(name + ".weight")
         self.gw = arena.g(name + ".weight")
@@ -472,11 +477,15 @@ class ConvOp:
         # ... and thin outputs (pred, 32 -> 3): the direct fp32 tile pads them to 32 GEMM columns and is bound by the fp32
         # matrix pipe (100 us per launch at B=8); on the 32-channel Winograd x six form the padding costs cheap bf16 MFMAs
         thin6 = WINO6_THIN and kind == "conv" and k == 3 and co <= 4 and ci % 16 == 0 and USE_WINOGRAD
-        # the packings' form: two fp16 planes + header (mfma_terms 3) or three bf16 planes (0)
-        if WINO6 and not bf16 and ((self.f_algo == 1 and co >= WINO6_MIN_CO) or thin6) and ci % 4 == 0:
-            wp6 = _Packing("wp6", "wino6", (ops.ROLE_WINO_FWD, co, ci), WINO_F16_FWD)
-        if WINO6 and not bf16 and need_dgrad and self.d_algo == 1 and ci >= WINO6_MIN_CO and co % 4 == 0:
-            wd6 = _Packing("wd6", "wino6", (ops.ROLE_WINO_DGRAD, co, ci), WINO_F16_DGRAD)
+        # the packings' form: two fp16 planes + header (mfma_terms 3) or three bf16 planes (0); "fp16": one fp16 plane (1) for
+        # exactly the convs that have these packings in the fp32 mode (f_wino / d_wino: that mode's f_algo / d_algo == 1)
+        f_wino, d_wino = self.f_algo == 1, self.d_algo == 1
+        if fp16 and bf16 and USE_WINOGRAD and kind == "conv" and k == 3:
+            f_wino, d_wino = co >= 16, True
+        if WINO6 and (fp16 or not bf16) and ((f_wino and co >= WINO6_MIN_CO) or thin6) and ci % 4 == 0:
+            wp6 = _Packing("wp6", "wino6", (ops.ROLE_WINO_FWD, co, ci), 1 if fp16 else (3 if WINO_F16_FWD else 0))
+        if WINO6 and (fp16 or not bf16) and need_dgrad and d_wino and ci >= WINO6_MIN_CO and co % 4 == 0:
+            wd6 = _Packing("wd6", "wino6", (ops.ROLE_WINO_DGRAD, co, ci), 1 if fp16 else (3 if WINO_F16_DGRAD else 0))
         if wp6 is not None and wp6.nbytes() >= 2 ** 31 - 1:
             wp6 = None
         if wd6 is not None and wd6.nbytes() >= 2 ** 31 - 1:
@@ -491,8 +500,11 @@ class ConvOp:
             planes = {1: 1, 3: 2}[terms]
             sf_bn = ops.conv_bn(3, 3, 1, 0, co)
             sf_pad = -(-co // sf_bn) * sf_bn
-            wps = _Packing("wps", "split", (ops.ROLE_FWD, sf_bn, 3, 3, co, ci, planes))
-            if need_dgrad and co % 8 == 0:
+            # "fp16": a conv on the one-plane Winograd packing never reads the split planes -- but for the input-gradient halves
+            # of a ci == 2 co conv below the Winograd tile's 32 rows, which stay on the split tile as in the bf16 mode
+            if not (fp16 and wp6 is not None):
+                wps = _Packing("wps", "split", (ops.ROLE_FWD, sf_bn, 3, 3, co, ci, planes))
+            if need_dgrad and co % 8 == 0 and (not (fp16 and wd6 is not None) or (ci == 2 * co and co < WINO6_MIN_CO)):
                 sd_bn = self.d_bn if self.d_algo != 1 else ops.conv_bn(3, 3, 1, 0, min(ci, 128))
                 if ci == 2 * co:
                     sd_bn = ops.conv_bn(3, 3, 1, 0, co)
@@ -515,8 +527,9 @@ class ConvOp:
         # gradient row ranges below 32 rows) -- 159 MB of the model's 463 MB of packed weights that the batched repack of
         # every optimiser step does not write; whoever needs one packs it on demand (_packed), stamped with the arena's
         # pack epoch.  The one-by-one repack() writes everything.
-        self.wp_lazy = wp.lazy = LAZY_FALLBACK_PACKS and wp6 is not None and self.f_algo == 1
-        self.wd_lazy = LAZY_FALLBACK_PACKS and wd6 is not None and self.d_algo == 1
+        # ("fp16": the bf16 direct-tile packing is the fallback layout in the same way)
+        self.wp_lazy = wp.lazy = LAZY_FALLBACK_PACKS and wp6 is not None and (self.f_algo == 1 or fp16)
+        self.wd_lazy = LAZY_FALLBACK_PACKS and wd6 is not None and (self.d_algo == 1 or fp16)
         if wd is not None:
             wd.lazy = self.wd_lazy
         self.packings = [p for p in (wp, wd, wp6, wd6, wps, wds) if p is not None]
@@ -534,9 +547,9 @@ class ConvOp:
         self._f_split = self._f_wino6 = self._d_split = self._d_wino6 = self._d_plain = None
         if wps is not None:
             self._f_split = ("wps", dict(kh=kh, kw=kw, stride=st, pad=1, mode=0, cout_pad=sf_pad, algo=4, terms=self.split), True, False)
-        if wp6 is not None and self.split == 0:
+        if wp6 is not None and (self.split == 0 or fp16):
             self._f_wino6 = ("wp6", dict(kh=3, kw=3, stride=1, pad=1, mode=0, cout_pad=-(-self.f_rows // 64) * 64, algo=5,
-                                     terms=3 if wp6.flag else 0), True, False)
+                                     terms=wp6.flag), True, False)
         # (the pointwise tile has no second output)
         self._f_plain = ("wp", dict(kh=kh, kw=kw, stride=st, pad=self.pad, mode=md, cout_pad=self.f_pad, algo=self.f_algo),
                          self.f_algo != 3, True)
@@ -544,9 +557,10 @@ class ConvOp:
             kh, kw, st, md = d_geo
             if wds is not None:
                 self._d_split = ("wds", dict(kh=kh, kw=kw, stride=st, pad=1, mode=md, cout_pad=sd_pad, algo=4, terms=self.split), True, False)
-            if wd6 is not None and self.split == 0:
-                self._d_wino6 = ("wd6", dict(kh=3, kw=3, stride=1, pad=1, mode=0, cout_pad=self.d_pad, algo=5,
-                                         terms=3 if wd6.flag else 0), True, False)
+            if wd6 is not None and (self.split == 0 or fp16):
+                # (the planes' rows are padded to 64 = the fp32 Winograd tile's d_bn; "fp16" keeps the bf16 tile's d_bn in d_pad)
+                self._d_wino6 = ("wd6", dict(kh=3, kw=3, stride=1, pad=1, mode=0, cout_pad=-(-self.d_rows // 64) * 64, algo=5,
+                                         terms=wd6.flag), True, False)
             # the pointwise tile: the patch GEMM of ConvTranspose2d writes the second output, the 1x1 layers keep their separate
             # skip-sum launch.  GELU' rides only in the fp32 pointwise tile of a 1x1 conv (refid_conv_desc.mask_mode = 1)
             self._d_plain = ("wd", dict(kh=kh, kw=kw, stride=st, pad=d_padding, mode=md, cout_pad=self.d_pad, algo=self.d_algo),
@@ -660,6 +674,9 @@ class ConvOp:
     # ---- input gradient ----------------------------------------------------------------------
     def _dgrad_route(self, g, cnt):
         """Which tile takes the input gradient of `cnt` rows from g?  (one of the tuples built in __init__)"""
+        r = self._d_wino6
+        if self.fp16 and r is not None and cnt >= WINO6_MIN_CO:
+            return r                          # ("fp16": the one-product Winograd form wherever the fp32 mode runs that tile)
         r = self._d_split
         if r is not None and (self.kind == "conv" or _fills_gpu(g.shape[0], g.shape[1], g.shape[2], cnt, 4)):
             return r
@@ -960,8 +977,8 @@ class Engine:
             # EGACA's LayerNorm / depthwise / squeeze-excite kernels take 2*base in {16, 32, 64, 128} channels; every
             # options/*.yml of the reference uses 32
             raise ValueError("base_num_channels must be 8, 16, 32 or 64 (the reference's configs use 32)")
-        if compute_dtype not in ("fp32", "bf16", "bf16x3"):
-            raise ValueError(f"compute_dtype must be 'fp32', 'bf16x3' or 'bf16', got {compute_dtype!r}")
+        if compute_dtype not in ("fp32", "bf16", "bf16x3", "fp16"):
+            raise ValueError(f"compute_dtype must be 'fp32', 'bf16x3', 'bf16' or 'fp16', got {compute_dtype!r}")
         # "bf16x3": fp32 tensors, fp32 accumulation; the 3x3 forward / input-gradient convs multiply on the bf16 matrix
         # cores with every operand split in two bf16 numbers and three products per fp32 product (2^-16 relative per
         # product, 64x finer than TF32); weight gradients and everything else as in "fp32".  Explicit opt-in.

@@ -136,29 +136,42 @@ def pack_conv_weights_split(w, role, bn, kh, kw, o, i, planes=3, out=None, oscal
     return out
 
 
-def packed_weight_wino6_bytes(role, o, i, f16=False):
-    """Bytes of the Winograd-domain packing for conv2d(algo=5): three bf16 planes (terms 0 / 6), or -- f16 -- a 64-byte header
-    + two fp16 planes (terms 3)."""
-    L = lib()
-    return L.refid_packed_weight_wino3h_bytes(role, o, i, 64) if f16 else L.refid_packed_weight_wino6_bytes(role, o, i, 64)
+def _wino6_form(f16, terms):
+    """The packing a conv2d(algo=5, terms=...) call reads: suffix of the C entry points.  `terms` wins over the older `f16`
+    flag (f16=True = terms 3)."""
+    if terms is None:
+        terms = 3 if f16 else 0
+    if terms not in (0, 6, 3, 1):
+        raise _lib.RefidHipError(f"Winograd packing: terms must be 0 / 6 (three bf16 planes), 3 (two fp16 planes) or 1 (one fp16 "
+                                 f"plane), got {terms}")
+    return {0: "wino6", 6: "wino6", 3: "wino3h", 1: "wino1h"}[terms]
 
 
-def pack_conv_weights_wino6(w, role, o, i, out=None, oscale=None, f16=False):
+def packed_weight_wino6_bytes(role, o, i, f16=False, terms=None):
+    """Bytes of the Winograd-domain packing for conv2d(algo=5): three bf16 planes (terms 0 / 6), a 64-byte header + two fp16
+    planes (terms 3, or f16=True), or the header + one fp16 plane (terms 1)."""
+    return getattr(lib(), "refid_packed_weight_%s_bytes" % _wino6_form(f16, terms))(role, o, i, 64)
+
+
+def pack_conv_weights_wino6(w, role, o, i, out=None, oscale=None, f16=False, terms=None):
     """Winograd-domain weights as three bf16 planes for conv2d(algo=5); role = ROLE_WINO_FWD / ROLE_WINO_DGRAD.
-    f16: the two-fp16-plane packing of conv2d(algo=5, terms=3) (scaled by a per-tensor power of two kept in its header)."""
+    terms=3 (or f16=True): the two-fp16-plane packing of conv2d(algo=5, terms=3) (scaled by a per-tensor power of two kept in
+    its header); terms=1: its high plane alone, for the one-product form conv2d(algo=5, terms=1)."""
     L = lib()
-    nb = packed_weight_wino6_bytes(role, o, i, f16)
+    form = _wino6_form(f16, terms)
+    nb = packed_weight_wino6_bytes(role, o, i, f16, terms)
     if nb == 0:
         raise _lib.RefidHipError("pack_conv_weights_wino6: bad geometry")
     if not w.is_contiguous():
         raise _lib.RefidHipError("pack_conv_weights_wino6: weight must be contiguous")
     if out is None:
-        out = torch.empty(nb // 2, dtype=torch.bfloat16, device=w.device)
+        # (the one-plane form is tagged by its tensor type: conv2d(algo=5, terms=1) takes nothing else)
+        out = torch.empty(nb // 2, dtype=torch.float16 if form == "wino1h" else torch.bfloat16, device=w.device)
     elif out.numel() * out.element_size() != nb:
         raise _lib.RefidHipError("pack_conv_weights_wino6: out has the wrong size")
-    fn = L.refid_pack_conv_weights_wino3h if f16 else L.refid_pack_conv_weights_wino6
+    fn = getattr(L, "refid_pack_conv_weights_" + form)
     check(fn(w.data_ptr(), oscale.data_ptr() if oscale is not None else None, out.data_ptr(), role, o, i, 64, _stream()),
-          "refid_pack_conv_weights_wino3h" if f16 else "refid_pack_conv_weights_wino6")
+          "refid_pack_conv_weights_" + form)
     return out
 
 
@@ -194,7 +207,8 @@ def conv2d(in_a, w_packed, out, *, kh, kw, stride=1, pad=0, mode=0, cout, cout_p
            in_b=None, bias=None, res=None, mask=None, slope_pre=1.0, slope_post=1.0, slope_mask=1.0, algo=0, pw=None,
            terms=0, add2=None, out2=None, mask_mode=0):
     """out = mask(post(pre(conv([in_a|in_b]) + bias) + res)); see refid_conv_desc.  pw: dict of the pointwise tile's
-    EGACA fusions (refid_pw_extras); terms: algo 4's product count (0 / 6, or 3); algo 3: 0 = fp32 MFMA, 6 = six bf16 products
+    EGACA fusions (refid_pw_extras); terms: algo 4's product count (0 / 6, 3 or 1); algo 5: 0 / 6 = six bf16
+    products, 3 = three fp16 products, 1 = one fp16 product (w_packed from pack_conv_weights_wino6 with the same terms); algo 3: 0 = fp32 MFMA, 6 = six bf16 products
     (w_packed from pack_conv_weights_split with kh = kw = 1).  add2 / out2: second output out2 = out + add2 (not algo 3)."""
     if DESC_CACHE and pw is None and PROFILE is None:
         return _conv2d_cached(in_a, w_packed, out, kh, kw, stride, pad, mode, cout, cout_pad, co_base, in_b, bias, res, mask,
@@ -213,6 +227,17 @@ def conv2d(in_a, w_packed, out, *, kh, kw, stride=1, pad=0, mode=0, cout, cout_p
         d.c_b = in_b.shape[3]
         if in_b.shape[:3] != in_a.shape[:3]:
             raise _lib.RefidHipError("conv2d: in_a / in_b pixel grids differ")
+    if algo == 5 and terms == 1:
+        # the one-plane packing is half the two-plane one: a packing of the other form would be read as the wrong planes.  The
+        # one-plane packing is the only one held in a float16 tensor (the others: bfloat16), and it must cover the chunks this
+        # call reads (64-byte header + [chunk16][xi][cout_pad][16] fp16; a call may read the first chunks of a longer packing:
+        # the first source alone of a two-source conv)
+        chunk = 16 * cout_pad * 16 * 2
+        have = w_packed.numel() * w_packed.element_size()
+        if w_packed.dtype != torch.float16 or have < 64 + -(-(d.c_a + d.c_b) // 16) * chunk or (have - 64) % chunk:
+            raise _lib.RefidHipError(f"conv2d: algo 5 with terms=1 reads the one-plane fp16 packing (a float16 tensor from "
+                                     f"pack_conv_weights_wino6 with terms=1: 64 + chunks x {chunk} bytes), got {have} bytes of "
+                                     f"{w_packed.dtype}")
     d.w_packed = w_packed.data_ptr()
     d.bias = bias.data_ptr() if bias is not None else None
     d.out, d.ld_out = _nhwc(out, "out")
@@ -266,6 +291,8 @@ def conv2d(in_a, w_packed, out, *, kh, kw, stride=1, pad=0, mode=0, cout, cout_p
         name = "conv_wino6_kernel<2>" if cout > 32 else "conv_wino6_kernel<1>"     # 64- / 32-channel workgroup tile
         if terms == 3:
             name = name[:-1] + ", true>"                                           # three fp16 products
+        if terms == 1:
+            name = name[:-1] + ", true, fp16x1>"                                   # one fp16 product
     if algo == 4:
         name = "conv_split_kernel<%s>" % ("3, fp16" if terms == TERMS_F16X3 else (terms or 6))
     if algo == 3:
@@ -763,8 +790,10 @@ class PackPlan:
         else:
             self._add(2 if kh == 1 and kw == 1 else 1, w, oscale, out, role, o, i, kh, kw, 8, bn, planes)
 
-    def add_wino6(self, w, role, o, i, out, oscale=None, f16=False):
-        self._add(5 if f16 else 3, w, oscale, out, role, o, i, 3, 3, 16, 64, 2 if f16 else 3)
+    def add_wino6(self, w, role, o, i, out, oscale=None, f16=False, terms=None):
+        form = _wino6_form(f16, terms)
+        kind, planes = {"wino6": (3, 3), "wino3h": (5, 2), "wino1h": (5, 1)}[form]
+        self._add(kind, w, oscale, out, role, o, i, 3, 3, 16, 64, planes)
 
     def add_mul_vec(self, a, b, out):
         self._add(4, a, b, out, o=a.numel())

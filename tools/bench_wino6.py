@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
-"""fp32 Winograd tile (algo 1) vs Winograd x six bf16 products (algo 5) vs Winograd x three fp16 products (algo 5, terms 3) at
-the config-2 shapes (B=8): time and -- on a small crop -- the largest deviation of each from the float64 convolution."""
+"""fp32 Winograd tile (algo 1) vs Winograd x six bf16 products (algo 5) vs Winograd x three fp16 products (algo 5, terms 3) vs
+Winograd x ONE fp16 product (algo 5, terms 1: compute_dtype 'fp16') vs the bf16 one-product direct tile (algo 4, terms 1:
+compute_dtype 'bf16'; single-source layers only, as in the engine) at the config-2 shapes (B=8): time and -- on a small crop --
+the largest deviation of each from the float64 convolution."""
 import os
 import sys
 
@@ -29,9 +31,18 @@ def one(name, H, Ca, Cb, Co, res=False, mask=False):
     o1 = torch.empty(B, H, H, Co, device="cuda")
     o6 = torch.empty(B, H, H, Co, device="cuda")
     o3 = torch.empty(B, H, H, Co, device="cuda")
+    wh = ops.pack_conv_weights_wino6(w, ops.ROLE_WINO_FWD, Co, Ci, terms=1)
+    oh = torch.empty(B, H, H, Co, device="cuda")
+    ob = tb = None
+    if b is None:                                           # (one bf16 product: the engine sends single-source convs only)
+        bn = ops.conv_bn(3, 3, 1, 0, Co)
+        wb = ops.pack_conv_weights_split(w, ops.ROLE_FWD, bn, 3, 3, Co, Ci, planes=1)
+        ob = torch.empty(B, H, H, Co, device="cuda")
+        tb = timeit(lambda: ops.conv2d(a, wb, ob, algo=4, terms=1, **dict(kw, cout_pad=-(-Co // bn) * bn)))
     t1 = timeit(lambda: ops.conv2d(a, w1, o1, algo=1, **kw))
     t6 = timeit(lambda: ops.conv2d(a, w6, o6, algo=5, **kw))
     t3 = timeit(lambda: ops.conv2d(a, w3, o3, algo=5, terms=3, **kw))
+    th = timeit(lambda: ops.conv2d(a, wh, oh, algo=5, terms=1, **kw))
     # float64 reference on a crop of sample 0 (rows 0..15: includes the top border)
     crop = 18
     xa = torch.cat([a[:1, :crop], b[:1, :crop]], 3) if b is not None else a[:1, :crop]
@@ -41,9 +52,12 @@ def one(name, H, Ca, Cb, Co, res=False, mask=False):
         ref = ref + r[:1, :crop - 2].double().cpu()
     if mask:
         ref = ref * torch.where(m[:1, :crop - 2].cpu() > 0, 1.0, 0.2)
-    e1, e6, e3 = ((o[:1, :crop - 2].double().cpu() - ref).abs().max().item() for o in (o1, o6, o3))
+    e1, e6, e3, eh = ((o[:1, :crop - 2].double().cpu() - ref).abs().max().item() for o in (o1, o6, o3, oh))
+    direct = "bf16 direct       -                -" if ob is None else \
+        f"bf16 direct {tb*1e6:7.1f} us  err {(ob[:1, :crop - 2].double().cpu() - ref).abs().max().item():.1e}"
     print(f"{name:28s} wino fp32 {t1*1e6:7.1f} us | x6 bf16 {t6*1e6:7.1f} us | x3 fp16 {t3*1e6:7.1f} us {fl/t3/1e12:6.1f} TF(eff) "
-          f"x{t6/t3:4.2f} vs x6 | err vs fp64: fp32 {e1:.1e}  x6 {e6:.1e}  x3 {e3:.1e}", flush=True)
+          f"x{t6/t3:4.2f} vs x6 | x1 fp16 {th*1e6:7.1f} us x{t3/th:4.2f} vs x3 | {direct} | err vs fp64: fp32 {e1:.1e}  x6 {e6:.1e}  "
+          f"x3 {e3:.1e}  x1 {eh:.1e}", flush=True)
 
 
 if __name__ == "__main__":

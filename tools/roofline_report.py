@@ -32,8 +32,10 @@ def norm(name):
 def algo_key(k):
     """rocprof kernel name -> name used by refid_amd.ops.PROFILE (tools/profile_step.py)."""
     if k.startswith("conv_wino6_kernel"):
-        m = re.match(r"conv_wino6_kernel<(\d+)(?:, (true|false))?>", k)           # <NT, F16>: ops.PROFILE names "<NT>" / "<NT, true>"
+        # <NT, F16, ONE>: ops.PROFILE names "<NT>" / "<NT, true>" / "<NT, true, fp16x1>"
+        m = re.match(r"conv_wino6_kernel<(\d+)(?:, (true|false))?(?:, (true|false))?>", k)
         if not m: return "conv_wino6_kernel<2>"
+        if m.group(3) == "true": return f"conv_wino6_kernel<{m.group(1)}, true, fp16x1>"
         return f"conv_wino6_kernel<{m.group(1)}, true>" if m.group(2) == "true" else f"conv_wino6_kernel<{m.group(1)}>"
     if k.startswith("conv_wino_kernel"): return k
     if k.startswith("wgrad_wino_kernel"): return "wgrad_wino_kernel"
