@@ -378,6 +378,7 @@ __global__ __launch_bounds__(256, (SIX || NT > 2) ? 3 : 4) void conv_pw_kernel(c
 int refid_launch_pointwise(const ConvKArgs& ka, hipStream_t st, const PwExtra* ex, int terms) {
     ConvKArgs a = ka;
     a.nchunks = cdiv(a.Ctot, KC);
+    if (a.Cout % 4) a.vecOK = 0;      // the 16-byte epilogue writes whole channel quads: a ragged last quad takes the scalar one
     const long long npix = (long long)a.N * a.H * a.W;
     const int nb = (int)((npix + 127) / 128);
     const bool six = terms == 6;
