@@ -545,6 +545,52 @@ int refid_tile_add(const float* tile, float* acc, float* cnt, int c, int th, int
                    void* stream);
 int refid_tile_normalize(float* acc, const float* cnt, int c, int h, int w, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Training-batch assembly from raw frames and events (csrc/sample.hip): the device counterpart of the recurrent
+ * datasets' __getitem__ (data/image_npy_dataset.py:188-232, data/image_sharp_npy_dataset.py:180-225) -- event
+ * voxelisation restricted to the crop, paired crop, flip / flip / transpose, BGR->RGB and /255, and the lq / voxel / gt
+ * layouts -- batched over the samples of a batch through a table of refid_sample_desc in device memory.
+ * Bit-reproducible: the event sums are 64-bit fixed point (32 fractional bits) integer atomics, every float is one
+ * correctly rounded operation.  Events outside the frame, outside the crop, or with a negative normalised time are
+ * DROPPED (the reference's flat np.add.at index wraps or spills them into other pixels; that is not reproduced).
+ * ---------------------------------------------------------------------------------- */
+typedef struct refid_sample_desc {
+    const float* events;                        /* (n_events,4) float32 rows [t,x,y,p], 16-byte aligned (device)  */
+    long long n_events;                         /* may be 0                                                       */
+    float first_stamp, last_stamp;              /* normalisation: ts = (bins-1)*(t-first)/(last-first), in fp32   */
+    int height, width;                          /* full frame                                                     */
+    const unsigned char* frames;                /* 2 + n_gt frames (blur0, blur1, gt...), u8 HWC BGR (device)     */
+    long long frame_stride;                     /* bytes from one frame to the next (>= the uploaded window)      */
+    int row_pitch;                              /* bytes from one row to the next                                 */
+    int y0, x0;                                 /* frame coordinates of the uploaded window's first pixel         */
+    int top, left;                              /* crop origin in frame coordinates                               */
+    int hflip, vflip, rot90;                    /* transforms.py:110-129, applied in this order after the crop    */
+} refid_sample_desc;
+
+#define REFID_LAYOUT_BLUR 0    /* bins = 2m+n+1; lq (B, 6+2(m-1), h, w) = blur0 | bins 1..m-1 | blur1 | bins m+2+n..  */
+#define REFID_LAYOUT_SHARP 1   /* bins = n+1;    lq (B, 2, 3, h, w)                                                  */
+#define REFID_ASSEMBLE_ZERO 1
+#define REFID_ASSEMBLE_SCATTER 2
+#define REFID_ASSEMBLE_FINISH 4
+#define REFID_ASSEMBLE_FRAMES 8
+#define REFID_ASSEMBLE_ALL 15
+typedef struct refid_assemble_desc {
+    const refid_sample_desc* samples_host;      /* the table in host memory (validated on every call)             */
+    const refid_sample_desc* samples_dev;       /* the same table in device memory (read by the kernels)          */
+    int batch;
+    int m, n, layout;
+    int crop_h, crop_w;                         /* crop BEFORE the transpose; rot90 needs crop_h == crop_w        */
+    long long* scratch;                         /* int64 [batch][bins][crop_h*crop_w]                             */
+    float* lq;
+    float* voxel;                               /* (batch, bins-1, 2, h, w): sliding bin pairs                    */
+    float* gt;                                  /* (batch, bins-1, 3, h, w)                                       */
+} refid_assemble_desc;
+
+/* Number of voxel bins of a layout, or -1 (with the error text set) when (m, n, layout) is not supported. */
+int refid_assemble_bins(int m, int n, int layout);
+/* Runs the chosen stages (REFID_ASSEMBLE_*) in the order zero, scatter, finish, frames on `stream`: one launch each. */
+int refid_assemble_batch(const refid_assemble_desc* d, int stages, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -72,6 +72,33 @@ class WgradDesc(C.Structure):
     ]
 
 
+class SampleDesc(C.Structure):
+    """refid_sample_desc: one sample of a raw batch (refid_amd.data.DeviceBatchAssembler fills the table)."""
+    _fields_ = [
+        ("events", C.c_void_p), ("n_events", C.c_longlong),
+        ("first_stamp", C.c_float), ("last_stamp", C.c_float),
+        ("height", C.c_int), ("width", C.c_int),
+        ("frames", C.c_void_p), ("frame_stride", C.c_longlong), ("row_pitch", C.c_int),
+        ("y0", C.c_int), ("x0", C.c_int),
+        ("top", C.c_int), ("left", C.c_int),
+        ("hflip", C.c_int), ("vflip", C.c_int), ("rot90", C.c_int),
+    ]
+
+
+class AssembleDesc(C.Structure):
+    _fields_ = [
+        ("samples_host", C.c_void_p), ("samples_dev", C.c_void_p),
+        ("batch", C.c_int),
+        ("m", C.c_int), ("n", C.c_int), ("layout", C.c_int),
+        ("crop_h", C.c_int), ("crop_w", C.c_int),
+        ("scratch", C.c_void_p),
+        ("lq", C.c_void_p), ("voxel", C.c_void_p), ("gt", C.c_void_p),
+    ]
+
+
+LAYOUT_BLUR, LAYOUT_SHARP = 0, 1                 # == REFID_LAYOUT_* in include/refid_hip.h
+ASSEMBLE_ZERO, ASSEMBLE_SCATTER, ASSEMBLE_FINISH, ASSEMBLE_FRAMES, ASSEMBLE_ALL = 1, 2, 4, 8, 15
+
 ABI_VERSION = 9          # == REFID_ABI_VERSION in include/refid_hip.h
 _lib = None
 
@@ -186,6 +213,8 @@ def _bind_extra(L):
     L.refid_hin_lrelu_bwd.argtypes = [vp, i, vp, i, vp, i, vp, vp, vp, i, vp, vp, vp, vp, i, i, i, i, f, vp]
     L.refid_fac_fwd.argtypes = [vp, i, vp, i, vp, i, ll, i, vp]
     L.refid_fac_bwd.argtypes = [vp, i, vp, i, vp, i, vp, i, vp, i, ll, i, vp]
+    L.refid_assemble_bins.argtypes = [i, i, i]
+    L.refid_assemble_batch.argtypes = [C.POINTER(AssembleDesc), i, vp]
 
 
 def check(rc, what):

@@ -4,7 +4,9 @@
 //                            basicsr/metrics/psnr_ssim.py:48-63 (calculate_psnr, float64 MSE)
 //   * tile overlap-averaging basicsr/models/twoImage_event_recurrent_model.py:252-268 (grids_inverse)
 // HBM-bound streaming kernels; the scalar sums (PSNR / SSIM) are two-stage and deterministic, only the event scatter-add
-// uses (fp32) atomics, as np.add.at's order is unspecified too.
+// uses (fp32) atomics, as np.add.at's order is unspecified too.  That whole-frame, float64-event voxeliser stays for
+// callers that want a full grid; the training path does not need it any more: sample.hip voxelises the float32 event
+// rows of the datasets inside the crop with integer (bit-reproducible) sums while it assembles the batch.
 #include "common.h"
 
 namespace {

@@ -9,11 +9,18 @@ Event voxelisation:
 Mirrors ``events_to_voxel_grid(events, num_bins, width, height)`` of the reference
 (basicsr/data/event_util.py:6-66; events = [N x 4] rows of [timestamp, x, y, polarity], sorted by
 time) and the recurrent datasets' slicing of a (2m+n+1)- or (n+1)-bin grid into sliding two-bin
-pairs (image_npy_dataset.py:226-232)."""
+pairs (image_npy_dataset.py:226-232).
+
+Batch assembly: ``DeviceBatchAssembler`` is the device counterpart of the rest of those datasets' ``__getitem__``
+(image_npy_dataset.py:188-232, image_sharp_npy_dataset.py:180-225): from u8 frames and float32 event rows it builds
+``lq`` / ``voxel`` / ``gt`` with the kernels of csrc/sample.hip, voxelising only the crop; ``draw_augmentation`` draws
+the crop origin and the flips in the reference's order, and ``CUDAPrefetcher(..., assemble=...)`` runs the assembler
+on its side stream."""
 import ctypes as C
 
 import torch
 
+from . import _lib
 from ._lib import RefidHipError, check, lib
 
 
@@ -48,16 +55,182 @@ def sliding_bin_pairs(voxel):
     return torch.stack([voxel[:-1], voxel[1:]], dim=1)
 
 
+def draw_augmentation(rng, frame_h, frame_w, gt_size, use_hflip, use_rot):
+    """(top, left, hflip, vflip, rot90) drawn from ``rng`` (a ``random.Random``, or the ``random`` module) in the
+    reference's order with its short-circuits: triple_random_crop's two ``randint`` (transforms.py:212-213; skipped when
+    ``gt_size`` is None, image_npy_dataset.py:188), then augment's ``random() < 0.5`` for hflip only if ``use_hflip``,
+    for vflip and for rot90 only if ``use_rot`` (transforms.py:110-112)."""
+    top = left = 0
+    if gt_size is not None:
+        if frame_h < gt_size or frame_w < gt_size:
+            raise ValueError(f"frame ({frame_h}, {frame_w}) is smaller than the patch size {gt_size}")
+        top = rng.randint(0, frame_h - gt_size)
+        left = rng.randint(0, frame_w - gt_size)
+    hflip = bool(use_hflip and rng.random() < 0.5)
+    vflip = bool(use_rot and rng.random() < 0.5)
+    rot90 = bool(use_rot and rng.random() < 0.5)
+    return top, left, hflip, vflip, rot90
+
+
+_RAW_KEYS = ("frames", "events", "first_stamp", "last_stamp", "frame_hw", "origin", "top", "left", "hflip", "vflip", "rot90")
+
+
+class DeviceBatchAssembler:
+    """Builds ``{'lq', 'voxel', 'gt'}`` on the device from raw samples, one launch set per batch (csrc/sample.hip).
+
+    ``layout='blur'``: 2m+n+1 voxel bins, lq (B, 6+2(m-1), h, w) = blur0 | bins 1..m-1 | blur1 | bins m+2+n.. (the blur
+    datasets with ``return_deblur_voxel``); ``layout='sharp'``: n+1 bins, lq (B, 2, 3, h, w).  voxel is (B, bins-1, 2, h, w),
+    gt (B, bins-1, 3, h, w).  ``gt_size=None`` keeps the whole frame (all samples of a batch then share one frame size, and
+    rot90 needs a square frame).
+
+    ``__call__(raw_batch)``: a list of per-sample dicts, or a dict of per-sample lists.  Per sample:
+      frames       u8 tensor (2 + bins-1, Hwin, Wwin, 3), BGR: blur0, blur1, then the ground-truth frames; host or device
+      events       float32 tensor (N, 4) rows [t, x, y, p] as the datasets build them (N may be 0); host or device
+      first_stamp, last_stamp   optional; default events[0,0] / events[-1,0] (event_util.py:25-31).  Give them when the
+                   events were pre-filtered (e.g. to the crop window) so that the normalisation does not change
+      frame_hw     optional (H, W) of the full frame; default: the frames' own size
+      origin       optional (y0, x0) of the uploaded window inside the frame; default (0, 0)
+      top, left, hflip, vflip, rot90   from ``draw_augmentation``; default 0
+    Every other key is passed through as a per-sample list.  Everything runs on the current stream; host tensors are
+    uploaded there (pin them for an asynchronous copy).  The cached scratch is ordered by that stream only: use one
+    assembler per stream (``CUDAPrefetcher`` runs its own on its side stream)."""
+
+    def __init__(self, m, n, layout="blur", gt_size=None, use_hflip=False, use_rot=False, device=None):
+        if layout not in ("blur", "sharp"):
+            raise RefidHipError(f"DeviceBatchAssembler: unknown layout {layout!r} ('blur' or 'sharp')")
+        from . import ops
+        self.m, self.n = int(m), int(n)
+        self.layout = layout
+        self._layout = _lib.LAYOUT_BLUR if layout == "blur" else _lib.LAYOUT_SHARP
+        self.bins = ops.assemble_bins(self.m, self.n, self._layout)
+        self.gt_size = None if gt_size is None else int(gt_size)
+        self.use_hflip, self.use_rot = bool(use_hflip), bool(use_rot)
+        self.device = torch.device("cuda" if device is None else device)
+        if self.device.type != "cuda":
+            raise RefidHipError("DeviceBatchAssembler: a GPU device is required (the HIP path has no CPU fallback)")
+        self._last = None
+        self._cache = {}                      # (B, h, w) -> scratch, device table, pinned table, event of the last upload
+
+    def draw(self, rng, frame_h, frame_w):
+        """``draw_augmentation`` with this assembler's gt_size / use_hflip / use_rot, as a dict for a raw sample."""
+        keys = ("top", "left", "hflip", "vflip", "rot90")
+        return dict(zip(keys, draw_augmentation(rng, frame_h, frame_w, self.gt_size, self.use_hflip, self.use_rot)))
+
+    def rerun(self, stages):
+        """Launches ``stages`` (``_lib.ASSEMBLE_*``) again for the batch of the last call, into its outputs: lets a
+        benchmark put device events around a single kernel (tools/bench_assemble.py)."""
+        from . import ops
+        ops.assemble_batch(self._last[0], stages)
+
+    def _geometry(self, batch, h, w):
+        key = (batch, h, w)
+        c = self._cache.get(key)
+        if c is None:
+            nbytes = batch * C.sizeof(_lib.SampleDesc)
+            c = {"scratch": torch.empty((batch, self.bins, h, w), dtype=torch.int64, device=self.device),
+                 "table_dev": torch.empty(nbytes, dtype=torch.uint8, device=self.device),
+                 "table_pin": torch.empty(nbytes, dtype=torch.uint8).pin_memory(),
+                 "uploaded": None}
+            self._cache[key] = c
+        return c
+
+    @staticmethod
+    def _samples(raw_batch):
+        if isinstance(raw_batch, dict):
+            keys = list(raw_batch)
+            count = len(raw_batch["frames"])
+            return [{k: raw_batch[k][i] for k in keys} for i in range(count)]
+        return list(raw_batch)
+
+    def __call__(self, raw_batch, stages=_lib.ASSEMBLE_ALL):
+        from . import ops
+        samples = self._samples(raw_batch)
+        if not samples:
+            raise RefidHipError("DeviceBatchAssembler: empty batch")
+        B = len(samples)
+        table = (_lib.SampleDesc * B)()
+        keep = []                             # device tensors the kernels read
+        crop = None
+        for b, s in enumerate(samples):
+            fr, ev = s["frames"], s["events"]
+            if fr.dtype != torch.uint8 or fr.dim() != 4 or fr.shape[3] != 3 or fr.shape[0] != self.bins + 1:
+                raise RefidHipError(f"DeviceBatchAssembler: sample {b}: frames must be uint8 ({self.bins + 1}, H, W, 3) "
+                                    f"(blur0, blur1, {self.bins - 1} ground-truth frames), got {fr.dtype} {tuple(fr.shape)}")
+            if ev.dtype != torch.float32 or ev.dim() != 2 or ev.shape[1] != 4:
+                raise RefidHipError(f"DeviceBatchAssembler: sample {b}: events must be float32 (N, 4) rows [t, x, y, p], "
+                                    f"got {ev.dtype} {tuple(ev.shape)}")
+            n_ev = ev.shape[0]
+            first, last = s.get("first_stamp"), s.get("last_stamp")
+            if first is None or last is None:
+                first, last = (float(ev[0, 0]), float(ev[-1, 0])) if n_ev else (0.0, 0.0)
+            fr = fr.contiguous().to(self.device, non_blocking=True)
+            ev = ev.contiguous().to(self.device, non_blocking=True)
+            keep += [fr, ev]
+            win_h, win_w = fr.shape[1], fr.shape[2]
+            y0, x0 = s.get("origin", (0, 0))
+            H, W = s.get("frame_hw", (y0 + win_h, x0 + win_w))
+            h, w = (H, W) if self.gt_size is None else (self.gt_size, self.gt_size)
+            if crop is None:
+                crop = (int(h), int(w))
+            elif crop != (int(h), int(w)):
+                raise RefidHipError(f"DeviceBatchAssembler: sample {b}: output {h}x{w} differs from sample 0's "
+                                    f"{crop[0]}x{crop[1]} (gt_size=None needs equal frame sizes)")
+            top, left = int(s.get("top", 0)), int(s.get("left", 0))
+            if top < y0 or left < x0 or top + h > y0 + win_h or left + w > x0 + win_w:
+                raise RefidHipError(f"DeviceBatchAssembler: sample {b}: crop {h}x{w} at ({top},{left}) does not fit inside "
+                                    f"the uploaded {win_h}x{win_w} window at ({y0},{x0})")
+            d = table[b]
+            d.events, d.n_events = (ev.data_ptr() if n_ev else None), n_ev
+            d.first_stamp, d.last_stamp = float(first), float(last)
+            d.height, d.width = int(H), int(W)
+            d.frames, d.frame_stride, d.row_pitch = fr.data_ptr(), win_h * win_w * 3, win_w * 3
+            d.y0, d.x0, d.top, d.left = int(y0), int(x0), top, left
+            d.hflip, d.vflip, d.rot90 = int(bool(s.get("hflip", 0))), int(bool(s.get("vflip", 0))), int(bool(s.get("rot90", 0)))
+        h, w = crop
+        c = self._geometry(B, h, w)
+        if c["uploaded"] is not None:
+            c["uploaded"].synchronize()       # the previous batch's table copy has left the pinned buffer
+        C.memmove(c["table_pin"].data_ptr(), C.addressof(table), C.sizeof(table))
+        c["table_dev"].copy_(c["table_pin"], non_blocking=True)
+        c["uploaded"] = torch.cuda.Event()
+        c["uploaded"].record()
+        nb = self.bins
+        if self.layout == "blur":
+            lq = torch.empty((B, 6 + 2 * (self.m - 1), h, w), dtype=torch.float32, device=self.device)
+        else:
+            lq = torch.empty((B, 2, 3, h, w), dtype=torch.float32, device=self.device)
+        voxel = torch.empty((B, nb - 1, 2, h, w), dtype=torch.float32, device=self.device)
+        gt = torch.empty((B, nb - 1, 3, h, w), dtype=torch.float32, device=self.device)
+        desc = _lib.AssembleDesc()
+        desc.samples_host, desc.samples_dev = C.addressof(table), c["table_dev"].data_ptr()
+        desc.batch, desc.m, desc.n, desc.layout = B, self.m, self.n, self._layout
+        desc.crop_h, desc.crop_w = h, w
+        desc.scratch, desc.lq, desc.voxel, desc.gt = c["scratch"].data_ptr(), lq.data_ptr(), voxel.data_ptr(), gt.data_ptr()
+        ops.assemble_batch(desc, stages)
+        self._last = (desc, table, keep)      # rerun() launches again from these
+        cur = torch.cuda.current_stream(self.device)
+        for t in keep:                        # (tensors the caller allocated on another stream stay valid until the kernels ran)
+            t.record_stream(cur)
+        out = {"lq": lq, "voxel": voxel, "gt": gt}
+        for k in samples[0]:
+            if k not in _RAW_KEYS:
+                out[k] = [s[k] for s in samples]
+        return out
+
+
 class CUDAPrefetcher:
     """prefetch_dataloader.py:84-125.  ``loader`` is any re-iterable of dict batches whose tensors live in (preferably
     pinned) host memory; ``next()`` returns the batch on the device, or None at the end of an epoch; ``reset()`` starts
     the next epoch.  Additions over the reference: the returned tensors are tied to the consumer stream
     (``record_stream``: the caching allocator must not hand their memory to the NEXT copy while the step still reads
     them), and -- only with ``time_waits=True`` (bench.py) -- the time the compute stream actually had to wait for a copy
-    is measured with events (``exposed_ms()``); a training loop keeps no per-iteration state, like the reference class."""
+    is measured with events (``exposed_ms()``); a training loop keeps no per-iteration state, like the reference class.
+    ``assemble`` (a ``DeviceBatchAssembler``): the loader yields RAW batches, and ``preload()`` uploads them and runs the
+    assembler on the side stream, so that assembling batch k+1 overlaps step k."""
 
-    def __init__(self, loader, opt=None, device=None, time_waits=False):
+    def __init__(self, loader, opt=None, device=None, time_waits=False, assemble=None):
         self.ori_loader = loader
+        self.assemble = assemble
         self.loader = iter(loader)
         self.opt = opt
         if device is None:
@@ -78,6 +251,9 @@ class CUDAPrefetcher:
             self.batch = None
             return None
         with torch.cuda.stream(self.stream):
+            if self.assemble is not None:
+                self.batch = self.assemble(self.batch)
+                return None
             self.batch = {k: (v.to(device=self.device, non_blocking=True) if torch.is_tensor(v) else v)
                           for k, v in self.batch.items()}
 

@@ -954,3 +954,16 @@ def fac_bwd(g, feat, filt):
     check(lib().refid_fac_bwd(pg, ldg, pf, ldf, pi, ldi, gfeat.data_ptr(), c, gfilt.data_ptr(), 2 * c, n * h * w, c,
                               _stream()), "refid_fac_bwd")
     return gfeat, gfilt
+
+
+def assemble_bins(m, n, layout):
+    """Voxel bins of a batch-assembly layout (_lib.LAYOUT_BLUR: 2m+n+1, LAYOUT_SHARP: n+1); raises on an unsupported one."""
+    bins = lib().refid_assemble_bins(int(m), int(n), int(layout))
+    if bins < 0:
+        raise _lib.RefidHipError("refid_assemble_bins: " + lib().refid_last_error().decode("utf-8", "replace"))
+    return bins
+
+
+def assemble_batch(desc, stages=_lib.ASSEMBLE_ALL):
+    """Runs the batch-assembly kernels of csrc/sample.hip for an _lib.AssembleDesc on the current stream."""
+    check(lib().refid_assemble_batch(C.byref(desc), int(stages), _stream()), "refid_assemble_batch")

@@ -67,3 +67,28 @@ def shapes_from_dataset_opt(ds):
     if ds.get("return_deblur_voxel", False):
         return 2 * m + n, 2 * 3 + 2 * (m - 1)
     return n, 6
+
+
+def assembler_from_dataset_opt(ds, device=None):
+    """``device_assemble: true`` in a dataset block selects batch assembly on the GPU: returns the
+    ``refid_amd.data.DeviceBatchAssembler`` for the block's num_end_interpolation / num_inter_interpolation / gt_size
+    / use_hflip / use_rot (hand it to ``CUDAPrefetcher(..., assemble=...)``; its ``draw(rng, H, W)`` draws a sample's crop and
+    flips the way the reference does).  None when the key is absent or false.
+    The layout follows the dataset class: the sharp-interpolation datasets (``*Sharp*``, image_sharp_npy_dataset.py) give
+    lq (2,3,h,w), the blur datasets with ``return_deblur_voxel`` the 6+2(m-1)-channel lq."""
+    if not ds.get("device_assemble", False):
+        return None
+    from ._lib import RefidHipError
+    from .data import DeviceBatchAssembler
+    if not ds.get("one_voxel_flag", True):
+        raise RefidHipError("device_assemble: the per-pair voxel mode (one_voxel_flag: false) is not supported")
+    sharp = "sharp" in str(ds.get("type", "")).lower()
+    if sharp and ds.get("return_deblur_voxel", False):
+        raise RefidHipError("device_assemble: the sharp layout's zero-padded return_deblur_voxel "
+                            "(image_sharp_npy_dataset.py:203-214) is not supported")
+    if not sharp and not ds.get("return_deblur_voxel", False):
+        raise RefidHipError("device_assemble: the blur datasets are supported with return_deblur_voxel: true only")
+    # norm_voxel: accepted and ignored -- the reference discards voxel_norm's result (image_npy_dataset.py:206-208)
+    return DeviceBatchAssembler(int(ds.get("num_end_interpolation", 1)), int(ds.get("num_inter_interpolation", 1)),
+                                layout="sharp" if sharp else "blur", gt_size=ds.get("gt_size"),
+                                use_hflip=ds.get("use_hflip", False), use_rot=ds.get("use_rot", False), device=device)
