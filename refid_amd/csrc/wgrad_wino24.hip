@@ -441,6 +441,297 @@ __global__ __launch_bounds__(256, NS == 2 ? 2 : 3) void wgrad_wino24_kernel(cons
     }
 }
 
+// PAIR form (NS = 2, an even number of input-channel tiles): ONE workgroup of eight waves computes the two 64(o) x 32(i) tiles
+// (blockIdx.y: input tiles 2y and 2y + 1) that the four-wave form gives to two workgroups.  Wave w is F(3,2) row w & 3 of
+// input tile 2y + (w >> 2) and runs W24Row's K loop on its 12 accumulators exactly as above -- same tiles, same order, same
+// MFMA sequence: the slabs are bit-identical.  What changes is the staging: the gradient tile (16 KB of a stage's 29.5 KB)
+// is fetched ONCE for both input tiles, and with one workgroup per CU the LDS holds a ring of THREE stages of
+//     [X tile of half 0: 13,824 B] [X tile of half 1: 13,824 B] [dY tile, both 32-channel halves: 16,384 B] = 44,032 B,
+// laid out region by region ([X0 x 3][X1 x 3][dY x 3]) so that every stage of a wave's X half (41,472 B) and of dY (49,152 B)
+// lies inside the 8-bit x 256-byte offset range of ds_read2st64 from ONE set of bases: the K loop is written for a TRIPLE of
+// tiles and still carries no address arithmetic.  Tile t + 2 is requested at the top of tile t (two K tiles of lead), ONE
+// barrier per K tile: after it every wave has left tile t - 1, whose stage the request overwrites.  Every wave issues a
+// FIXED number of DMA instructions per request (rows 0 / 1: halo rows 2 row, 2 row + 1 of their half = 6; rows 2 / 3: halo row
+// row + 2 of their half and the gradient pieces (half w >> 2, rows 2 (row - 2), + 1) = 7; dead rows are requested out of
+// range), so "my pieces of tile t have landed" is vmcnt(requests of tile t + 1) and the lead survives the wait.
+constexpr int PAIR_STAGES = 3;
+constexpr int PAIR_G0 = 2 * PAIR_STAGES * X_BYTES;                             // 82,944: the gradient ring
+constexpr int PAIR_LDS_BYTES = PAIR_G0 + PAIR_STAGES * 2 * GS_BYTES;           // 132,096: one workgroup per CU
+
+// the lane index, opaque to the compiler (not merged with an earlier copy)
+__device__ __forceinline__ int w24_lane_again() {
+    int l = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    asm volatile("" : "+v"(l));
+    return l;
+}
+
+template <bool DOWN>
+__global__ __launch_bounds__(512, 1) void wgrad_wino24_pair_kernel(const W24Args a) {
+    constexpr int NS = 2, OT = 32 * NS, XPS = DOWN ? 2 : 1;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int row = wave & 3, hf = wave >> 2;              // F(3,2) row; which of the two input-channel tiles
+    const int li = lane & 31, kh = lane >> 5;
+    const int phase = DOWN ? blockIdx.z / a.ncoT : 0, php = phase >> 1, phq = phase & 1;
+    const int co0 = (DOWN ? blockIdx.z % a.ncoT : blockIdx.z) * OT, ci0 = (2 * blockIdx.y + hf) * IT;
+    const int split = blockIdx.x;
+    const int Hin = DOWN ? a.Hin : a.H, Win = DOWN ? a.Win : a.W;
+
+    // one X descriptor per half (wave-uniform): the halves may lie in different sources, or beyond them
+    const bool xFromA = ci0 < a.Ca || ci0 >= a.Ctot;
+    const int xld = xFromA ? a.ldA : a.ldB;
+    const long long gpixAll = (long long)a.N * a.Ho * a.Wo, xpixAll = (long long)a.N * Hin * Win;
+    const int limG = (int)min(gpixAll * a.ldG * 4, 0x7fffffffLL), limX = (int)min(xpixAll * xld * 4, 0x7fffffffLL);
+    const int ntAll = a.ntiles * a.groups;
+    const int chunk = (ntAll + a.nsplit - 1) / a.nsplit;
+    const int p0 = min(split * chunk, ntAll), p1 = min(p0 + chunk, ntAll);
+
+    int qg, qn, qy, qx;
+    {
+        int t = p0 < ntAll ? p0 : 0;
+        qg = t / a.ntiles; t -= qg * a.ntiles;
+        qx = t % a.tilesX; t /= a.tilesX;
+        qy = t % a.tilesY; qn = t / a.tilesY;
+    }
+    // ---- DMA roles: pieces, lane constants and the FAST / masked paths as in the four-wave kernel
+    const int xq = ci0 + (lane & 7) * 4, xt = ci0 + (lane & 31), gq = co0 + (lane & 7) * 4;
+    const int xlc = ((lane >> 3) * XPS * xld + (xFromA ? xq : xq - a.Ca)) * 4;
+    const int xlt = ((lane >> 5) * XPS * xld + (xFromA ? xt : xt - a.Ca)) * 4;
+    const int glc = ((lane >> 3) * a.ldG + gq) * 4;
+    const bool fullch = ci0 + IT <= a.Ctot && co0 + OT <= a.Co;                     // wave-uniform
+    constexpr int OOB = 0x7ff00000;
+    const int xRowB = XPS * Win * xld * 4, gRowB = a.Wo * a.ldG * 4;
+    auto x_origin = [&](int n, int ty, int tx) {
+        return ((n * Hin + XPS * (ty * GH - a.pad) + php) * Win + XPS * (tx * GW - a.pad) + phq) * xld * 4;
+    };
+    const float* gPtr = a.g[qg];
+    const float* xPtr = xFromA ? a.inA[qg] : a.inB[qg];
+    int xTile = x_origin(qn, qy, qx);
+    int gTile = ((qn * a.Ho + qy * GH) * a.Wo + qx * GW) * a.ldG * 4;
+    // this wave's share of a request: halo rows xr0 .. xr0 + nxr - 1 of its half; rows 2 / 3 also two gradient rows of half hf
+    const int xr0 = row < 2 ? 2 * row : row + 2, nxr = row < 2 ? 2 : 1;
+    const int gr0 = 2 * (row - 2);
+    auto request = [&](int st) {
+        const int oy0 = qy * GH, ox0 = qx * GW;
+        const int iy0 = oy0 - a.pad, ix0 = ox0 - a.pad;
+        const __amdgpu_buffer_rsrc_t rsG = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(gPtr), 0, limG, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xPtr), 0, limX, 0x00020000);
+        char* xdst = smem + (hf * PAIR_STAGES + st) * X_BYTES;
+        char* gdst = smem + PAIR_G0 + st * (2 * GS_BYTES) + hf * GS_BYTES;
+        const bool fast = fullch && ix0 >= 0 && ix0 + XW <= a.W && ox0 + GW <= a.Wo && xld * 8 * XPS * 4 < 0x100000 && a.ldG * 8 * 4 < 0x100000;
+        if (fast) {
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                if (k < nxr && !W24_NO_DMA) {
+                    const int r = xr0 + k;
+                    const int base = (unsigned)(iy0 + r) < (unsigned)a.H ? xTile + r * xRowB : OOB;
+                    char* dst = xdst + r * (XW * IT * 4);
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_ptr24)dst, 16, base + xlc, 0, 0, 0);
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_ptr24)(dst + 1024), 16, base + 8 * XPS * xld * 4 + xlc, 0, 0, 0);
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_ptr24)(dst + 2048), 4, base + 16 * XPS * xld * 4 + xlt, 0, 0, 0);
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                if (row >= 2 && !W24_NO_DMA) {
+                    const int r = gr0 + k;
+                    const int base = oy0 + r < a.Ho ? gTile + r * gRowB + hf * 128 : OOB;
+                    char* dst = gdst + r * (GW * 32 * 4);
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsG, (lds_ptr24)dst, 16, base + glc, 0, 0, 0);
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsG, (lds_ptr24)(dst + 1024), 16, base + 8 * a.ldG * 4 + glc, 0, 0, 0);
+                }
+            }
+        } else {
+            const int l8 = lane >> 3, l32 = lane >> 5;
+            const int xbadq = xq < a.Ctot ? 0 : -1, xbadt = xt < a.Ctot ? 0 : -1;
+            const int gbad = gq + hf * 32 < a.Co ? 0 : -1;
+            const int cx0 = (unsigned)(ix0 + l8) < (unsigned)a.W ? 0 : -1;
+            const int cx1 = (unsigned)(ix0 + 8 + l8) < (unsigned)a.W ? 0 : -1;
+            const int cxt = (unsigned)(ix0 + 16 + l32) < (unsigned)a.W ? 0 : -1;
+            const int cg0 = ox0 + l8 < a.Wo ? 0 : -1, cg1 = ox0 + 8 + l8 < a.Wo ? 0 : -1;
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                if (k < nxr && !W24_NO_DMA) {
+                    const int r = xr0 + k;
+                    const int rbad = (unsigned)(iy0 + r) < (unsigned)a.H ? 0 : -1;
+                    const int base = xTile + r * xRowB;
+                    char* dst = xdst + r * (XW * IT * 4);
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_ptr24)dst, 16, (base + xlc) | xbadq | rbad | cx0, 0, 0, 0);
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_ptr24)(dst + 1024), 16,
+                                                             (base + 8 * XPS * xld * 4 + xlc) | xbadq | rbad | cx1, 0, 0, 0);
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_ptr24)(dst + 2048), 4,
+                                                             (base + 16 * XPS * xld * 4 + xlt) | xbadt | rbad | cxt, 0, 0, 0);
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                if (row >= 2 && !W24_NO_DMA) {
+                    const int r = gr0 + k;
+                    const int rbad = oy0 + r < a.Ho ? 0 : -1;
+                    const int base = gTile + r * gRowB + hf * 128;
+                    char* dst = gdst + r * (GW * 32 * 4);
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsG, (lds_ptr24)dst, 16, (base + glc) | gbad | rbad | cg0, 0, 0, 0);
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsG, (lds_ptr24)(dst + 1024), 16,
+                                                             (base + 8 * a.ldG * 4 + glc) | gbad | rbad | cg1, 0, 0, 0);
+                }
+            }
+        }
+        // advance
+        if (REFID_W24_ABLATE == 7) return;
+        qx += 1;
+        if (qx != a.tilesX) {
+            xTile += GW * XPS * xld * 4;
+            gTile += GW * a.ldG * 4;
+        } else {
+            qx = 0;
+            qy += 1;
+            if (qy == a.tilesY) {
+                qy = 0;
+                qn += 1;
+                if (qn == a.N) {
+                    qn = 0;
+                    qg = min(qg + 1, a.groups - 1);
+                    gPtr = a.g[qg];
+                    xPtr = xFromA ? a.inA[qg] : a.inB[qg];
+                }
+            }
+            xTile = x_origin(qn, qy, 0);
+            gTile = (qn * a.Ho + qy * GH) * a.Wo * a.ldG * 4;
+        }
+    };
+
+    f32x16 acc[6][NS];                                     // [j][o half]
+#pragma unroll
+    for (int j = 0; j < 6; ++j)
+#pragma unroll
+        for (int sm = 0; sm < NS; ++sm)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[j][sm][r] = 0.f;
+
+    // The bases point into stage 0 of the wave's X half and of the gradient ring and never change: stage s is s x 54 (X) /
+    // s x 64 (dY) units of 256 bytes further, an immediate of the same ds_read2st64.
+    static_assert(X_BYTES % 256 == 0 && (PAIR_STAGES * X_BYTES) / 256 < 256 && (PAIR_STAGES * 2 * GS_BYTES) / 256 < 256,
+                  "ds_read2st64 offset range");
+    lds_cf24* xe = (lds_cf24*)(smem + hf * PAIR_STAGES * X_BYTES) + (2 * kh) * (XW * IT) + li;
+    lds_cf24* ge = (lds_cf24*)(smem + PAIR_G0) + (2 * kh) * (GW * 32) + li;
+    lds_cf24* xb[4] = {xe, xe + IT, xe + 2 * IT, xe + 3 * IT};
+    lds_cf24* gb[4] = {ge, ge + 32, ge + 2 * 32, ge + 3 * 32};
+    asm volatile("" : "+v"(xb[0]), "+v"(xb[1]), "+v"(xb[2]), "+v"(xb[3]), "+v"(xe));
+    asm volatile("" : "+v"(gb[0]), "+v"(gb[1]), "+v"(gb[2]), "+v"(gb[3]));
+
+    auto kloop = [&](auto TI) {
+        constexpr int I = decltype(TI)::value;
+        using R = W24Row<I>;
+        float bs[NS];                                      // (row 1 only: the tile sums live and die in its K loop)
+#pragma unroll
+        for (int sm = 0; sm < NS; ++sm) bs[sm] = 0.f;
+        auto tile = [&](auto ST) {
+            constexpr int XO = decltype(ST)::value * (X_BYTES / 4), GO = decltype(ST)::value * (2 * GS_BYTES / 4);      // floats
+            lds_cf24* xbb[4] = {xb[0] + XO, xb[1] + XO, xb[2] + XO, xb[3] + XO};
+            lds_cf24* gbb[4] = {gb[0] + GO, gb[1] + GO, gb[2] + GO, gb[3] + GO};
+            f32x2 t[6], p4, p5;
+#pragma unroll
+            for (int s = 0; s < TC; s += 2) {
+                R::x_rows(xbb, s, t);
+                if (s == 0) {
+                    const f32x2 a01 = R::x_rows01(xe + XO);
+                    t[0] = w24_pair<0, 0>(a01, t[4]);
+                    t[1] = w24_pair<1, 0>(a01, t[5]);
+                } else {
+                    t[0] = w24_pair<1, 0>(p4, t[4]);
+                    t[1] = w24_pair<1, 0>(p5, t[5]);
+                }
+                p4 = t[4]; p5 = t[5];
+                f32x2 v[6];
+                R::v_cols(t, v);
+#pragma unroll
+                for (int sm = 0; sm < NS; ++sm) {
+                    f32x2 x[4], z[6];
+                    R::g_rows(gbb, s, sm, x);
+                    R::z_cols(x, z);
+                    if constexpr (I == 1) bs[sm] += z[1][0] + z[1][1];
+#pragma unroll
+                    for (int h = 0; h < 2; ++h)
+#pragma unroll
+                        for (int j = 0; j < 6; ++j) {
+                            if (W24_NO_MFMA) { asm volatile("" :: "v"(v[j][h]), "v"(z[j][h])); continue; }
+                            acc[j][sm] = __builtin_amdgcn_mfma_f32_32x32x2f32(v[j][h], z[j][h], acc[j][sm], 0, 0, 0);
+                        }
+                }
+            }
+        };
+        // tile j of the range: my pieces of it have landed once at most the requests of tile j + 1 (if any) are in flight;
+        // behind the barrier everybody's have, and everybody has left tile j - 1, whose stage tile j + 2 goes to
+        const int n = p1 - p0;
+        auto step = [&](auto ST, int j) {
+            constexpr int S = decltype(ST)::value;
+            if (j + 1 < n) __builtin_amdgcn_s_waitcnt(I < 2 ? 0x0F76 : 0x0F77);        // vmcnt(6) / vmcnt(7)
+            else __builtin_amdgcn_s_waitcnt(0x0F70);
+            if (!W24_NO_BAR) __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_sched_barrier(0);
+            if (j + 2 < n) request((S + 2) % PAIR_STAGES);
+            tile(ST);
+        };
+        if (n > 0) request(0);
+        if (n > 1) request(1);
+        // (triples in the loop, the last one or two tiles after it: no exit from the middle of the loop body)
+        int j = 0;
+        for (; j + 3 <= n; j += 3) {
+            step(std::integral_constant<int, 0>{}, j);
+            step(std::integral_constant<int, 1>{}, j + 1);
+            step(std::integral_constant<int, 2>{}, j + 2);
+        }
+        if (j < n) {
+            step(std::integral_constant<int, 0>{}, j);
+            if (j + 1 < n) step(std::integral_constant<int, 1>{}, j + 1);
+        }
+        if constexpr (I == 1) {
+            // row 1 of the half that holds input tile 0 has the tile sums of the output channels: the two tile rows (kh) by
+            // one shuffle -- fixed order
+            if (a.bslabs != nullptr && blockIdx.y == 0 && hf == 0 && phase == 0) {
+                const int le = w24_lane_again();
+#pragma unroll
+                for (int sm = 0; sm < NS; ++sm) {
+                    const float tot = bs[sm] + __shfl_xor(bs[sm], 32, 64);
+                    if ((le >> 5) == 0) {
+                        float* dst = a.bslabs + (long long)split * a.CoP + co0 + sm * 32 + (le & 31);
+                        *dst = a.accum ? *dst + tot : tot;
+                    }
+                }
+            }
+        }
+    };
+    switch (row) {
+        case 0: kloop(std::integral_constant<int, 0>{}); break;
+        case 1: kloop(std::integral_constant<int, 1>{}); break;
+        case 2: kloop(std::integral_constant<int, 2>{}); break;
+        default: kloop(std::integral_constant<int, 3>{}); break;
+    }
+
+    // ---- slab: as the four-wave kernel's, for input tile 2 blockIdx.y + hf.  (The lane's coordinates are derived again: kept
+    // from the top of the kernel they would be the two registers too many next to 192 accumulators -- a spill.)
+    const int le = w24_lane_again(), lie = le & 31, khe = le >> 5;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        float* sl = a.slabs + ((long long)((split * (DOWN ? 4 : 1) + phase) * NXI + row * 6 + j) * a.CoP) * a.CiP;
+#pragma unroll
+        for (int sm = 0; sm < NS; ++sm) {
+            const int co = co0 + sm * 32 + lie;
+#pragma unroll
+            for (int qd = 0; qd < 4; ++qd) {
+                const int ci = ci0 + 8 * qd + 4 * khe;
+                f32x4 vv;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) vv[k] = acc[j][sm][4 * qd + k];
+                f32x4* dst = reinterpret_cast<f32x4*>(sl + (long long)co * a.CiP + ci);
+                if (a.accum) vv += *dst;
+                *dst = vv;
+            }
+        }
+    }
+}
+
 struct W24rArgs {
     const float* slabs; const float* bslabs; float* dw; float* db;
     int nsplit, Co, Ci, CoP, CiP, iBase, iTotal, perGroup;
@@ -642,7 +933,9 @@ Geo24 geo24_of(const refid_wgrad_desc* d) {
     g.ntiles = g.tilesX * g.tilesY * d->n;
     // two (NS = 1: three) workgroups per CU; a multiple of 8 splits keeps the workgroups of one K range on one XCD (grid x
     // is fastest)
-    static const int wgs = []() { const char* e = getenv("REFID_W24_WGS"); return e ? atoi(e) : 512; }();
+    // (read per call, like REFID_W24_PAIR: a test walks the split plan through the ring's short ranges in one process)
+    const char* wgsEnv = getenv("REFID_W24_WGS");
+    const int wgs = wgsEnv ? atoi(wgsEnv) : 512;
     int want = cdiv(ns_of(d) == 1 ? wgs * 3 / 2 : wgs, g.ncoT * g.nciT * (is_down(d) ? 4 : 1));
     if (want >= 8) want = want / 8 * 8;
     if (want < 1) want = 1;
@@ -652,6 +945,12 @@ Geo24 geo24_of(const refid_wgrad_desc* d) {
     g.CiP = g.nciT * IT;
     return g;
 }
+
+// The pair form (eight waves, two input-channel tiles per workgroup) takes every 64-channel-tile launch with an even number
+// of input tiles; REFID_W24_PAIR=0 keeps the four-wave form everywhere, =2 makes a launch the pair form cannot take an
+// error instead of a fallback (tests observe the routing through it).  Read per call: one process can alternate the forms.
+int pair_mode() { const char* e = getenv("REFID_W24_PAIR"); return e ? atoi(e) : 1; }
+bool pair_fits(const refid_wgrad_desc* d, const Geo24& g) { return ns_of(d) == 2 && g.nciT % 2 == 0; }
 
 }  // namespace
 
@@ -736,9 +1035,16 @@ int refid_wgrad_wino24_launch(const refid_wgrad_desc* d, hipStream_t st) {
     if (int rc = refid_lds_attr_once(attr_done1, &wgrad_wino24_kernel<1, false>, lds24_bytes(1), "wgrad_wino24<1>")) return rc;
     if (int rc = refid_lds_attr_once(attr_done2, &wgrad_wino24_kernel<2, true>, lds24_bytes(2), "wgrad_wino24<down>")) return rc;
     if (int rc = refid_lds_attr_once(attr_done3, &wgrad_wino24_kernel<1, true>, lds24_bytes(1), "wgrad_wino24<1, down>")) return rc;
+    static std::atomic<unsigned long long> attr_done4{0}, attr_done5{0};
+    if (int rc = refid_lds_attr_once(attr_done4, &wgrad_wino24_pair_kernel<false>, PAIR_LDS_BYTES, "wgrad_wino24<pair>")) return rc;
+    if (int rc = refid_lds_attr_once(attr_done5, &wgrad_wino24_pair_kernel<true>, PAIR_LDS_BYTES, "wgrad_wino24<pair, down>")) return rc;
     const Geo24 g = geo24_of(d);
     const bool down = is_down(d);
     const long long slab = slab_floats(d, g);
+    const int pmode = pair_mode();
+    const bool pair = pmode != 0 && pair_fits(d, g);
+    REFID_CHECK(pair || pmode != 2, "wgrad (Winograd 2x4 tiles): REFID_W24_PAIR=2, but this launch takes the four-wave form "
+                                    "(c_o <= 32 or an odd number of input-channel tiles)");
     if (down)
         REFID_CHECK(d->kw == 4 && d->stride == 2 && d->pad == 1 && d->h % 2 == 0 && d->w % 2 == 0 && d->ho == d->h / 2 && d->wo == d->w / 2,
                     "wgrad (algo 7): a 4x4 stride-2 pad-1 conv over an even-sized input");
@@ -777,7 +1083,12 @@ int refid_wgrad_wino24_launch(const refid_wgrad_desc* d, hipStream_t st) {
     a.CoP = g.CoP; a.CiP = g.CiP;
     a.accum = (d->phase == 2);
     if (d->phase != 3) {
-        if (down) {
+        if (pair) {
+            if (down)
+                hipLaunchKernelGGL((wgrad_wino24_pair_kernel<true>), dim3(g.nsplit, g.nciT / 2, 4 * g.ncoT), dim3(512), PAIR_LDS_BYTES, st, a);
+            else
+                hipLaunchKernelGGL((wgrad_wino24_pair_kernel<false>), dim3(g.nsplit, g.nciT / 2, g.ncoT), dim3(512), PAIR_LDS_BYTES, st, a);
+        } else if (down) {
             if (ns_of(d) == 1)
                 hipLaunchKernelGGL((wgrad_wino24_kernel<1, true>), dim3(g.nsplit, g.nciT, 4 * g.ncoT), dim3(256), lds24_bytes(1), st, a);
             else

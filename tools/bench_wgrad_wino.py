@@ -1,6 +1,11 @@
 #!/usr/bin/env python3
 """fp32 Winograd weight gradient at the config-2 shapes, 8 grouped time steps per launch as in the train step: the F(2x2,3x3)
-tile (algo 1, "regs") against the 2x4-tile form (algo 5, "f24").  Not bit-equal: the largest relative difference is printed."""
+tile (algo 1, "regs") against the 2x4-tile form (algo 5, "f24").  Not bit-equal: the largest relative difference is printed.
+
+  python tools/bench_wgrad_wino.py pair     the 2x4-tile form's four-wave and pair workgroups (REFID_W24_PAIR=0 / 1) side by
+                                            side, ALTERNATING in one process (ROUNDS rounds per layer; median and min..max
+                                            of each form, so a difference can be held against the spread of the same form);
+                                            the conv_down shapes (algo 7) included; results compared bit for bit."""
 import os
 import subprocess
 import sys
@@ -51,8 +56,53 @@ def run(tag, algo):
     torch.save(out, f"/tmp/wgrad_wino_{tag}.pt")
 
 
+DOWN_SHAPES = [("down 64->64 @256", 256, 64, 64), ("down 128->128 @128", 128, 128, 128), ("down 256->256 @64", 64, 256, 256)]
+
+
+def run_pair():
+    import statistics
+    import torch
+    from refid_amd import ops
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from bench_kernels import timeit, B
+    G, rounds = int(os.environ.get("GROUPS", 8)), int(os.environ.get("ROUNDS", 5))
+    cases = [(n, H, Ca, Cb, Co, False) for n, H, Ca, Cb, Co in SHAPES] + [(n, H, Ca, 0, Co, True) for n, H, Ca, Co in DOWN_SHAPES]
+    only = os.environ.get("ONLY_SHAPE")
+    print(f"# B={B} grouped steps={G} rounds={rounds}: us per launch, median (min..max); 4w = four-wave form, pair = pair form")
+    for name, H, Ca, Cb, Co, down in (cases if only is None else [cases[int(only)]]):
+        torch.manual_seed(1)
+        Ci, k, Ho = Ca + Cb, (4 if down else 3), (H // 2 if down else H)
+        steps = []
+        for t in range(G):
+            a = torch.randn(B, H, H, Ca, device="cuda")
+            b = torch.randn(B, H, H, Cb, device="cuda") if Cb else None
+            g = torch.randn(B, Ho, Ho, Co, device="cuda") * 0.01
+            steps.append((g, a, b))
+        g0, a0, b0 = steps[0]
+        geo = dict(kh=4, kw=4, stride=2, pad=1, algo=7) if down else dict(kh=3, kw=3, pad=1, algo=5)
+        times, grads = {"0": [], "1": []}, {}
+        for r in range(rounds):
+            for mode in ("0", "1"):
+                os.environ["REFID_W24_PAIR"] = mode
+                dw = torch.zeros(Co, Ci, k, k, device="cuda"); db = torch.zeros(Co, device="cuda")
+
+                def go():
+                    return ops.conv2d_wgrad(g0, a0, dw, in_b=b0, db=db, phase=1, more=steps[1:], **geo)
+                times[mode].append(timeit(go) * 1e6)
+                if r == 0:
+                    ops.conv2d_wgrad(g0, a0, dw, in_b=b0, db=db, phase=3, slabs=go(), **geo)
+                    grads[mode] = (dw.clone(), db.clone())
+        same = torch.equal(grads["0"][0], grads["1"][0]) and torch.equal(grads["0"][1], grads["1"][1])
+        m0, m1 = statistics.median(times["0"]), statistics.median(times["1"])
+        print(f"{name:26s} 4w {m0:8.1f} ({min(times['0']):8.1f}..{max(times['0']):8.1f})  pair {m1:8.1f} "
+              f"({min(times['1']):8.1f}..{max(times['1']):8.1f})  pair/4w {m1 / m0:5.3f}  bits {'equal' if same else 'DIFFER'}",
+              flush=True)
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 1:
+    if len(sys.argv) > 1 and sys.argv[1] == "pair":
+        run_pair()
+    elif len(sys.argv) > 1:
         run(sys.argv[1], {"regs": 1, "f24": 5}[sys.argv[1]])
     else:
         other = "f24"
