@@ -539,6 +539,18 @@ int refid_sqerr_u8(const float* a, const float* b, int n_frames, long long frame
 int refid_ssim3d_u8_parts(int n_frames, int h, int w);
 int refid_ssim3d_u8(const float* a, const float* b, int n_frames, int h, int w, double* sum_out, double* parts,
                     void* stream);
+/* The validation tail of one item in one pass (twoImage_event_recurrent_model.py:412-432 get_current_visuals +
+ * tensor2img per frame, utils/img_util.py:59-121; :460-491 calculate_psnr / calculate_ssim per frame,
+ * metrics/psnr_ssim.py:9-63,135-182,225-303).  pred, gt: (n_frames, 3, h, w) fp32 NCHW.  pred_u8 / gt_u8:
+ * (n_frames, h, w, 3) uint8, tensor2img's quantisation (clamp [0,1], x255, round half to even); flags &
+ * REFID_VAL_TAIL_BGR writes the channels as tensor2img(rgb2bgr=True) returns them, otherwise RGB (what a PNG holds).
+ * sq_out[f] = sum (q(pred)-q(gt))^2 of frame f as an exact integer (calculate_psnr's MSE numerator);
+ * ssim_out[f] = the sum refid_ssim3d_u8 gives for frame f, bit for bit.  gt, gt_u8, sq_out and ssim_out may each be
+ * NULL (gt NULL: conversion only); parts: refid_val_tail_parts(...) 8-byte words, needed with sq_out or ssim_out. */
+#define REFID_VAL_TAIL_BGR 1
+long long refid_val_tail_parts(int n_frames, int h, int w);
+int refid_val_tail(const float* pred, const float* gt, int n_frames, int h, int w, int flags, unsigned char* pred_u8,
+                   unsigned char* gt_u8, unsigned long long* sq_out, double* ssim_out, void* parts, void* stream);
 /* grids_inverse (twoImage_event_recurrent_model.py:252-268): acc[:, i0:i0+th, j0:j0+tw] += tile,
  * cnt += 1; then acc /= cnt. */
 int refid_tile_add(const float* tile, float* acc, float* cnt, int c, int th, int tw, int h, int w, int i0, int j0,

@@ -99,6 +99,7 @@ class AssembleDesc(C.Structure):
 LAYOUT_BLUR, LAYOUT_SHARP = 0, 1                 # == REFID_LAYOUT_* in include/refid_hip.h
 ASSEMBLE_ZERO, ASSEMBLE_SCATTER, ASSEMBLE_FINISH, ASSEMBLE_FRAMES, ASSEMBLE_ALL = 1, 2, 4, 8, 15
 
+VAL_TAIL_BGR = 1         # == REFID_VAL_TAIL_BGR in include/refid_hip.h
 ABI_VERSION = 9          # == REFID_ABI_VERSION in include/refid_hip.h
 _lib = None
 
@@ -206,6 +207,9 @@ def _bind_extra(L):
     L.refid_sqerr_u8.argtypes = [vp, vp, i, ll, vp, vp, vp]
     L.refid_ssim3d_u8_parts.argtypes = [i, i, i]
     L.refid_ssim3d_u8.argtypes = [vp, vp, i, i, i, vp, vp, vp]
+    L.refid_val_tail_parts.argtypes = [i, i, i]
+    L.refid_val_tail_parts.restype = ll
+    L.refid_val_tail.argtypes = [vp, vp, i, i, i, i, vp, vp, vp, vp, vp, vp]
     L.refid_tile_add.argtypes = [vp, vp, vp, i, i, i, i, i, i, i, vp]
     L.refid_tile_normalize.argtypes = [vp, vp, i, i, i, vp]
     L.refid_hin_parts.argtypes = [i]

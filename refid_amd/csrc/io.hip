@@ -139,6 +139,153 @@ __global__ __launch_bounds__(256) void ssim3d_kernel(const float* __restrict__ a
         out[((long long)f * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = sred[0] + sred[1] + sred[2] + sred[3];
 }
 
+// ---- fused validation tail (twoImage_event_recurrent_model.py:412-491): tensor2img of pred / gt into HWC uint8 images,
+// the integer squared error of calculate_psnr and the _ssim_3d sum, in one pass over the fp32 frames.  Same 16x16 tile,
+// same staging and same SSIM arithmetic as ssim3d_kernel, so its partials (and their fixed-order finish) are the same
+// bits; the frame index is folded into blockIdx.x: partial index = blockIdx.x = [frame][tile row][tile column].
+
+// One 16-lane group writes one row segment of a tile (nv = 3 * pixels bytes, HWC) from its image in LDS, which the
+// staging loop laid out so that LDS and global addresses agree modulo 16 (see val_tail_kernel).  Aligned full segments
+// (48 bytes) go out as three 16-byte stores; otherwise 4-byte stores from the first aligned address, and lanes 12 / 13
+// write the at most three head / tail bytes that a neighbouring tile's segment shares a word with.
+__device__ __forceinline__ void val_store_row(unsigned char* __restrict__ dst, const unsigned* srow, int j, int nv) {
+    const unsigned long long a = (unsigned long long)dst;
+    const unsigned char* src = reinterpret_cast<const unsigned char*>(srow) + (a & 3);      // src[k] = byte k of the segment
+    if (nv == 48 && (a & 15) == 0) {
+        if (j < 3) *reinterpret_cast<uint4*>(dst + 16 * j) = *reinterpret_cast<const uint4*>(src + 16 * j);
+        return;
+    }
+    const int head = min((int)((4 - (a & 3)) & 3), nv);
+    const int nd = (nv - head) >> 2;                               // <= 12
+    if (j < nd) *reinterpret_cast<unsigned*>(dst + head + 4 * j) = *reinterpret_cast<const unsigned*>(src + head + 4 * j);
+    else if (j == 12) { for (int k = 0; k < head; ++k) dst[k] = src[k]; }
+    else if (j == 13) { for (int k = head + 4 * nd; k < nv; ++k) dst[k] = src[k]; }
+}
+
+// Sum over the workgroup of per-thread integer squared errors (each <= 3 * 255^2); thread 0 returns the total.
+__device__ __forceinline__ unsigned long long val_block_sum(unsigned v, unsigned* sh) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (unsigned long long)sh[0] + sh[1] + sh[2] + sh[3];
+}
+
+template <bool SSIM>
+__global__ __launch_bounds__(256) void val_tail_kernel(const float* __restrict__ a, const float* __restrict__ b, int H, int W,
+                                                      int tiles_x, int tiles_y, int bgr, const SsimConst k,
+                                                      unsigned char* __restrict__ a_u8, unsigned char* __restrict__ b_u8,
+                                                      unsigned long long* __restrict__ sq_parts,
+                                                      double* __restrict__ ssim_parts) {
+    constexpr int T = 16, R = SSIM ? 5 : 0, HS = T + 2 * R;         // 26 with the SSIM halo, 16 without
+    __shared__ float sA[3][HS][HS + 1], sB[3][HS][HS + 1];
+    __shared__ float sH[SSIM ? 5 : 1][3][SSIM ? HS : 1][T + 1];
+    // the tile's uint8 HWC rows, 64 bytes each; byte k of a row lies at (address of its global row segment & 3) + k, so
+    // the word a lane stores to an aligned global address is an aligned word here
+    __shared__ __attribute__((aligned(16))) unsigned uA[T][16], uB[T][16];
+    __shared__ double sred[4];
+    __shared__ unsigned sqred[4];
+    const int tile = blockIdx.x % (tiles_x * tiles_y);
+    const long long f = blockIdx.x / (tiles_x * tiles_y);
+    const int y0 = (tile / tiles_x) * T, x0 = (tile % tiles_x) * T;
+    const float* pa = a + f * 3 * H * W;
+    const float* pb = b ? b + f * 3 * H * W : nullptr;
+    const long long off0 = ((f * H + y0) * W + x0) * 3;            // the tile's first byte in the uint8 images
+    const unsigned a_lo = (unsigned)(unsigned long long)(a_u8 + off0);
+    const unsigned b_lo = b_u8 ? (unsigned)(unsigned long long)(b_u8 + off0) : 0u;
+    for (int e = threadIdx.x; e < 3 * HS * HS; e += 256) {
+        const int c = e / (HS * HS), r = (e / HS) % HS, q = e % HS;
+        const int y = min(max(y0 + r - R, 0), H - 1), x = min(max(x0 + q - R, 0), W - 1);   // replicate
+        const float va = quant255(pa[((long long)c * H + y) * W + x]);
+        const float vb = pb ? quant255(pb[((long long)c * H + y) * W + x]) : 0.f;
+        sA[c][r][q] = va;
+        sB[c][r][q] = vb;
+        const int row = r - R, px = q - R;
+        if (row >= 0 && row < T && px >= 0 && px < T) {            // interior: also as a byte of the HWC row
+            const int k = 3 * px + (bgr ? 2 - c : c);
+            const unsigned step = 3u * (unsigned)W * (unsigned)row; // the row segment's address, modulo 4
+            reinterpret_cast<unsigned char*>(uA[row])[((a_lo + step) & 3) + k] = (unsigned char)va;
+            if (b_u8) reinterpret_cast<unsigned char*>(uB[row])[((b_lo + step) & 3) + k] = (unsigned char)vb;
+        }
+    }
+    __syncthreads();
+    const int ty = threadIdx.x / T, tx = threadIdx.x % T;
+    const bool inside = y0 + ty < H && x0 + tx < W;
+    if (y0 + ty < H) {                                              // 16 lanes per row segment
+        const int nv = min(T, W - x0) * 3;
+        const long long off = off0 + (long long)ty * W * 3;
+        val_store_row(a_u8 + off, uA[ty], tx, nv);
+        if (b_u8) val_store_row(b_u8 + off, uB[ty], tx, nv);
+    }
+    if (sq_parts) {                                                 // (block-uniform)
+        unsigned d2 = 0;
+        if (inside) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const int d = (int)sA[c][ty + R][tx + R] - (int)sB[c][ty + R][tx + R];
+                d2 += (unsigned)(d * d);
+            }
+        }
+        const unsigned long long s = val_block_sum(d2, sqred);
+        if (threadIdx.x == 0) sq_parts[blockIdx.x] = s;
+    }
+    if constexpr (SSIM) {
+        for (int e = threadIdx.x; e < 3 * HS * T; e += 256) {       // horizontal pass, 5 fields
+            const int c = e / (HS * T), r = (e / T) % HS, q = e % T;
+            float m1 = 0.f, m2 = 0.f, s11 = 0.f, s22 = 0.f, s12 = 0.f;
+#pragma unroll
+            for (int j = 0; j < 11; ++j) {
+                const float va = sA[c][r][q + j], vb = sB[c][r][q + j], g = k.g[j];
+                m1 += g * va; m2 += g * vb; s11 += g * va * va; s22 += g * vb * vb; s12 += g * va * vb;
+            }
+            sH[0][c][r][q] = m1; sH[1][c][r][q] = m2; sH[2][c][r][q] = s11; sH[3][c][r][q] = s22; sH[4][c][r][q] = s12;
+        }
+        __syncthreads();
+        float v[5][3];
+#pragma unroll
+        for (int fi = 0; fi < 5; ++fi)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                float s = 0.f;
+#pragma unroll
+                for (int j = 0; j < 11; ++j) s += k.g[j] * sH[fi][c][ty + j][tx];
+                v[fi][c] = s;
+            }
+        double acc = 0.0;
+        if (inside) {
+            const float C1 = (0.01f * 255.f) * (0.01f * 255.f), C2 = (0.03f * 255.f) * (0.03f * 255.f);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {                           // channel-axis pass (replicate-padded)
+                float w[5];
+#pragma unroll
+                for (int fi = 0; fi < 5; ++fi) w[fi] = k.mc[c][0] * v[fi][0] + k.mc[c][1] * v[fi][1] + k.mc[c][2] * v[fi][2];
+                const float mu1 = w[0], mu2 = w[1];
+                const float s1 = w[2] - mu1 * mu1, s2 = w[3] - mu2 * mu2, s12 = w[4] - mu1 * mu2;
+                acc += (double)(((2.f * mu1 * mu2 + C1) * (2.f * s12 + C2)) / ((mu1 * mu1 + mu2 * mu2 + C1) * (s1 + s2 + C2)));
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+        if ((threadIdx.x & 63) == 0) sred[threadIdx.x >> 6] = acc;
+        __syncthreads();
+        if (threadIdx.x == 0) ssim_parts[blockIdx.x] = sred[0] + sred[1] + sred[2] + sred[3];
+    }
+}
+
+// out[f] = sum of the frame's n integer partials (any order gives the same integer)
+__global__ __launch_bounds__(256) void sum_rows_u64_kernel(const unsigned long long* __restrict__ part, int n,
+                                                          unsigned long long* __restrict__ out) {
+    __shared__ unsigned long long sh[4];
+    const unsigned long long* p = part + (long long)blockIdx.x * n;
+    unsigned long long acc = 0;
+    for (int i = threadIdx.x; i < n; i += 256) acc += p[i];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) out[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
+}
+
 int nb(long long n) { long long b = (n + 255) / 256; return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b)); }
 
 }  // namespace
@@ -196,14 +343,7 @@ extern "C" int refid_tile_normalize(float* acc, const float* cnt, int c, int h, 
     return 0;
 }
 
-extern "C" int refid_ssim3d_u8_parts(int n_frames, int h, int w) {
-    return (n_frames > 0 && h > 0 && w > 0) ? n_frames * cdiv(w, 16) * cdiv(h, 16) : 0;
-}
-
-extern "C" int refid_ssim3d_u8(const float* a, const float* b, int n_frames, int h, int w, double* sum_out,
-                               double* parts, void* stream) {
-    REFID_CHECK(a && b && sum_out && parts && n_frames > 0 && h > 0 && w > 0, "ssim3d_u8: bad arguments");
-    hipStream_t st = (hipStream_t)stream;
+static SsimConst ssim_const() {
     SsimConst k;
     double g[11], s = 0.0;                                  // cv2.getGaussianKernel(11, 1.5)
     for (int i = 0; i < 11; ++i) { g[i] = exp(-((i - 5) * (i - 5)) / (2.0 * 1.5 * 1.5)); s += g[i]; }
@@ -213,8 +353,54 @@ extern "C" int refid_ssim3d_u8(const float* a, const float* b, int n_frames, int
         for (int j = 0; j < 11; ++j) { int cc = c + j - 5; cc = cc < 0 ? 0 : (cc > 2 ? 2 : cc); m[cc] += g[j]; }
         for (int q = 0; q < 3; ++q) k.mc[c][q] = (float)m[q];
     }
+    return k;
+}
+
+extern "C" int refid_ssim3d_u8_parts(int n_frames, int h, int w) {
+    return (n_frames > 0 && h > 0 && w > 0) ? n_frames * cdiv(w, 16) * cdiv(h, 16) : 0;
+}
+
+extern "C" int refid_ssim3d_u8(const float* a, const float* b, int n_frames, int h, int w, double* sum_out,
+                               double* parts, void* stream) {
+    REFID_CHECK(a && b && sum_out && parts && n_frames > 0 && h > 0 && w > 0, "ssim3d_u8: bad arguments");
+    hipStream_t st = (hipStream_t)stream;
+    const SsimConst k = ssim_const();
     dim3 grid(cdiv(w, 16), cdiv(h, 16), n_frames);
     hipLaunchKernelGGL(ssim3d_kernel, grid, dim3(256), 0, st, a, b, h, w, k, parts);
     REFID_LAUNCH_CHECK("ssim3d_u8");
     return refid_launch_sum_rows_f64(parts, n_frames, (int)(grid.x * grid.y), sum_out, st);
+}
+
+static long long val_tail_blocks(int n_frames, int h, int w) { return (long long)n_frames * cdiv(w, 16) * cdiv(h, 16); }
+
+extern "C" long long refid_val_tail_parts(int n_frames, int h, int w) {
+    return (n_frames > 0 && h > 0 && w > 0) ? 2 * val_tail_blocks(n_frames, h, w) : 0;
+}
+
+extern "C" int refid_val_tail(const float* pred, const float* gt, int n_frames, int h, int w, int flags,
+                              unsigned char* pred_u8, unsigned char* gt_u8, unsigned long long* sq_out, double* ssim_out,
+                              void* parts, void* stream) {
+    REFID_CHECK(pred && pred_u8 && n_frames > 0 && h > 0 && w > 0, "val_tail: bad arguments");
+    REFID_CHECK(gt || !(gt_u8 || sq_out || ssim_out), "val_tail: gt_u8 / sq_out / ssim_out need gt");
+    REFID_CHECK(parts || !(sq_out || ssim_out), "val_tail: sq_out / ssim_out need parts");
+    REFID_CHECK((flags & ~REFID_VAL_TAIL_BGR) == 0, "val_tail: unknown flags 0x%x", flags);
+    const long long blocks = val_tail_blocks(n_frames, h, w);
+    REFID_CHECK(blocks <= 0x7fffffffll, "val_tail: %lld tiles exceed the grid (n_frames=%d, %dx%d)", blocks, n_frames, h, w);
+    hipStream_t st = (hipStream_t)stream;
+    const int tx = cdiv(w, 16), ty = cdiv(h, 16), bgr = flags & REFID_VAL_TAIL_BGR;
+    double* ssim_parts = (double*)parts;                    // [blocks] doubles, then [blocks] integer squared errors
+    unsigned long long* sq_parts = sq_out ? (unsigned long long*)parts + blocks : nullptr;
+    if (ssim_out)
+        hipLaunchKernelGGL(val_tail_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, pred, gt, h, w, tx, ty, bgr,
+                           ssim_const(), pred_u8, gt_u8, sq_parts, ssim_parts);
+    else
+        hipLaunchKernelGGL(val_tail_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, pred, gt, h, w, tx, ty, bgr,
+                           SsimConst{}, pred_u8, gt_u8, sq_parts, ssim_parts);
+    REFID_LAUNCH_CHECK("val_tail");
+    if (sq_out) {
+        hipLaunchKernelGGL(sum_rows_u64_kernel, dim3(n_frames), dim3(256), 0, st, sq_parts, tx * ty, sq_out);
+        REFID_LAUNCH_CHECK("val_tail/sq");
+    }
+    if (ssim_out) return refid_launch_sum_rows_f64(ssim_parts, n_frames, tx * ty, ssim_out, st);
+    return 0;
 }

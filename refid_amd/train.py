@@ -5,11 +5,13 @@ init_training_settings :37-65, setup_optimizers :67-95, feed_data :97-113,
 optimize_parameters :273-310, test :312-330; base_model.py :77-108 (schedulers),
 :158-180 (update_learning_rate), :188-219/:256-281 (save/load network), :325-350 (loss reduce).
 
-Only what a train step / eval step needs is mirrored; datasets,
-logging, validation image dumps are out of scope.  The step itself is MI355X-native:
+What a train step, an eval step and the validation loop need is mirrored (validation,
+dist_validation, nondist_validation :348-536, single_image_inference :332-346, get_current_visuals :544-550); the
+datasets' file handling, tqdm and wandb are out of scope.  The step itself is MI355X-native:
 forward + BPTT in the HIP engine, Charbonnier forward+backward in one kernel, global grad
 norm + clip + AdamW fused over the flat arenas, gradient all-reduce (RCCL) overlapped with BPTT.
 """
+import logging
 import math
 import os
 from collections import OrderedDict
@@ -17,7 +19,8 @@ from copy import deepcopy
 
 import torch
 
-from . import ops
+from . import metrics, ops, tiling
+from ._lib import RefidHipError
 from .archs import define_network
 from .dist import GradSync, get_dist_info
 
@@ -176,6 +179,10 @@ class TwoImageEventRecurrentRestorationModel:
         self.voxel = data["voxel"].to(self.device, non_blocking=True)
         if "gt" in data:
             self.gt = data["gt"].to(self.device, non_blocking=True)
+        if "seq" in data:                                        # :107-113: lists (one entry per sample) -> first entry
+            self.seq_name = data["seq"][0]
+        if "origin_index" in data:
+            self.origin_index = data["origin_index"][0]
 
     # ---- S2: one optimisation step ----------------------------------------------------------------
     # ---- hipGraph replay of the step (MI355X: ~5000 kernel launches per step; at 1-2 samples per GPU the Python /
@@ -400,6 +407,112 @@ class TwoImageEventRecurrentRestorationModel:
                 i = j
             self.output = torch.cat(outs, dim=0)
         self.net_g.train()
+
+    # ---- validation (twoImage_event_recurrent_model.py:332-550) ------------------------------------------------------
+    def get_current_visuals(self):
+        """:544-550, for callers that want the fp32 tensors on the host; the validation loop does not go through it."""
+        out = OrderedDict()
+        out["lq"] = self.lq.detach().cpu()
+        out["result"] = self.output.detach().cpu()
+        if hasattr(self, "gt"):
+            out["gt"] = self.gt.detach().cpu()
+        return out
+
+    def _val_forward(self):
+        """test(), or with val.grids the tiled whole-frame pass (grids / grids_voxel / test / grids_inverse, :405-411)."""
+        val = self.opt.get("val", {})
+        if val.get("grids") is None:
+            return self.test()
+        if "crop_size" not in val:
+            raise RefidHipError("val.grids needs val.crop_size")
+        self.net_g.eval()
+        outs = [tiling.tiled_forward(self.net_g, self.lq[i:i + 1], self.voxel[i:i + 1], val["crop_size"],
+                                     val.get("max_minibatch") or 1) for i in range(self.lq.size(0))]
+        self.output = outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
+        self.net_g.train()
+
+    def single_image_inference(self, img, voxel, save_path):
+        """:332-346.  One PNG: the item's T output frames, quantised as tensor2img does, stacked top to bottom (the
+        reference hands the 4-D result to torchvision's make_grid, which is not restated)."""
+        from .png import write_png
+        was_training = self.net_g.training
+        self.feed_data(data={"lq": img.unsqueeze(dim=0), "voxel": voxel.unsqueeze(dim=0)})
+        self._val_forward()
+        self.net_g.train(was_training)
+        u8 = metrics.val_tail(self.output, bgr=False).pred_u8
+        write_png(save_path, u8.reshape(-1, u8.shape[-2], 3).cpu().numpy())
+
+    def validation(self, dataloader, current_iter, tb_logger, save_img=False, rgb2bgr=True, use_image=True):
+        """base_model.py: dispatch on opt['dist']."""
+        if self.opt.get("dist"):
+            return self.dist_validation(dataloader, current_iter, tb_logger, save_img, rgb2bgr, use_image)
+        return self.nondist_validation(dataloader, current_iter, tb_logger, save_img, rgb2bgr, use_image)
+
+    def dist_validation(self, dataloader, current_iter, tb_logger, save_img, rgb2bgr, use_image):
+        """:348-355: rank 0 validates, every other rank returns 0. (the rank this model was built with, not LOCAL_RANK)."""
+        if self.rank == 0:
+            return self.nondist_validation(dataloader, current_iter, tb_logger, save_img, rgb2bgr, use_image)
+        return 0.
+
+    def nondist_validation(self, dataloader, current_iter, tb_logger, save_img, rgb2bgr, use_image):
+        """:357-512 with the reference's option keys, file names, bookkeeping and log lines.  Per item: the forward pass,
+        then ONE fused kernel for all T frames (uint8 frames + PSNR / SSIM sums, metrics.val_tail); the uint8 frames are
+        copied out and written as PNGs behind the next item's forward pass (validation.FrameWriter).  Every sample of an
+        item is evaluated (`seq` / `origin_index` entry i names sample i; the reference looks at sample 0 only, the same
+        thing at its batch_size 1).  `rgb2bgr` is accepted and unused, as in the reference's loop."""
+        from .validation import FrameWriter
+        val = self.opt.get("val", {})
+        metrics.check_metric_options(val, use_image)
+        dataset_name = self.opt.get("name")
+        save_gt = val.get("save_gt", False)
+        self.m = self.opt["datasets"]["val"].get("num_end_interpolation")
+        self.n = self.opt["datasets"]["val"].get("num_inter_interpolation")
+        book = metrics.ValidationMetrics(val.get("metrics_deblur"), val.get("metrics_interpo"), self.m, self.n)
+        types = {o["type"] for o in list(book.opt_deblur.values()) + list(book.opt_interpo.values())} \
+            if book.with_metrics else set()
+        was_training = self.net_g.training
+        writer = FrameWriter(self.device) if save_img else None
+        try:
+            for val_data in dataloader:
+                self.feed_data(val_data)
+                self._val_forward()
+                out = self.output
+                gt = self.gt if "gt" in val_data else None
+                if gt is None and (types or (save_img and save_gt)):
+                    raise RefidHipError("nondist_validation: val.metrics_* / val.save_gt need data['gt']")
+                b, h, w = out.shape[0], out.shape[-2], out.shape[-1]
+                tail = metrics.val_tail(out, gt, bgr=False, want_gt_u8=bool(save_img and save_gt),
+                                        psnr="calculate_psnr" in types, ssim="calculate_ssim" in types)
+                t = tail.pred_u8.numel() // (b * h * w * 3)
+                for i in range(b):
+                    book.add_item({k: v[i * t:(i + 1) * t] for k, v in
+                                   (("calculate_psnr", tail.psnr), ("calculate_ssim", tail.ssim)) if v is not None})
+                if writer is not None:
+                    for key in ("seq", "origin_index"):
+                        if key not in val_data or len(val_data[key]) < b:
+                            raise RefidHipError(f"nondist_validation: save_img needs data['{key}'] with one entry per sample")
+                    stem = [os.path.join(self.opt["path"]["visualization"], dataset_name, val_data["seq"][i],
+                                         f"{val_data['origin_index'][i]}_{f:02d}") for i in range(b) for f in range(t)]
+                    batches = [(tail.pred_u8.view(b * t, h, w, 3), [s + ".png" for s in stem])]
+                    if save_gt:
+                        batches.append((tail.gt_u8.view(b * t, h, w, 3), [s + "_gt.png" for s in stem]))
+                    writer.dump(batches)
+        finally:
+            self.net_g.train(was_training)
+            if writer is not None:
+                writer.close()
+        current_metric = book.finish()
+        if book.with_metrics:
+            self.metric_results_deblur, self.metric_results_interpo = book.deblur, book.interpo
+            self.metric_results_total = book.total
+            logger = logging.getLogger("basicsr")               # get_root_logger's name
+            for line in book.log_lines(dataset_name):
+                logger.info(line)
+            if tb_logger:
+                for res in (book.deblur, book.interpo):
+                    for name, value in res.items():
+                        tb_logger.add_scalar(f"metrics/{name}", value, current_iter)
+        return current_metric
 
     # ---- checkpoints (state-dict key names are a compatibility contract, SURVEY.md section 5) ------
     def save_network(self, net, net_label, current_iter, param_key="params"):

@@ -1,0 +1,76 @@
+"""Image dumps of the validation loop (twoImage_event_recurrent_model.py:435-458) without stalling the GPU.
+
+The uint8 frames that ``metrics.val_tail`` leaves on the device go to one of two pinned host buffers on a side stream;
+a small thread pool encodes and writes the PNGs.  The buffers alternate, so the copy and the encoding of item k overlap
+the forward pass of item k+1.  A worker reads a pinned buffer only after the copy's event has completed, and a buffer
+is reused only after every job that reads it has finished.  No fp32 frame leaves the device."""
+import threading
+from concurrent.futures import ThreadPoolExecutor
+
+import torch
+
+from .png import write_png
+
+
+class FrameWriter:
+    WORKERS = 4              # encoding is zlib (releases the GIL); never sized from the machine's core count
+    QUEUE = 32               # jobs submitted and not finished; `dump` blocks beyond that
+
+    def __init__(self, device, level=1):
+        self.level = level
+        self.stream = torch.cuda.Stream(device)
+        self.slots = [dict(buf=None, jobs=[]), dict(buf=None, jobs=[])]
+        self.turn = 0
+        self.pool = ThreadPoolExecutor(max_workers=self.WORKERS, thread_name_prefix="refid-png")
+        self.room = threading.BoundedSemaphore(self.QUEUE)
+
+    def dump(self, batches):
+        """batches: [(uint8 device tensor (N, H, W, 3), [N paths])] of ONE item; returns at once."""
+        slot = self.slots[self.turn]
+        self.turn ^= 1
+        self._drain(slot)                                   # its previous item is written: the buffer may be overwritten
+        total = sum(t.numel() for t, _ in batches)
+        if slot["buf"] is None or slot["buf"].numel() < total:
+            slot["buf"] = torch.empty(total, dtype=torch.uint8).pin_memory()
+        self.stream.wait_stream(torch.cuda.current_stream())
+        views, off = [], 0
+        with torch.cuda.stream(self.stream):
+            for t, paths in batches:
+                dst = slot["buf"][off:off + t.numel()].view(t.shape)
+                dst.copy_(t, non_blocking=True)
+                t.record_stream(self.stream)                # the allocator must not hand t's block out before the copy ran
+                views.append((dst.numpy(), paths))
+                off += t.numel()
+            done = torch.cuda.Event()
+            done.record(self.stream)
+        for frames, paths in views:
+            for i, path in enumerate(paths):
+                self.room.acquire()
+                slot["jobs"].append(self.pool.submit(self._job, done, frames[i], path))
+
+    def _job(self, done, frame, path):
+        try:
+            done.synchronize()                              # nothing reads the pinned buffer before its copy has completed
+            write_png(path, frame, self.level)
+        finally:
+            self.room.release()
+
+    @staticmethod
+    def _drain(slot):
+        jobs, slot["jobs"] = slot["jobs"], []
+        err = None
+        for j in jobs:                                      # wait for ALL of them, then re-raise the first failure
+            try:
+                j.result()
+            except BaseException as ex:                     # noqa: BLE001
+                err = err or ex
+        if err is not None:
+            raise err
+
+    def close(self):
+        """Joins the pool: every file exists when this returns; a worker's exception is raised here."""
+        try:
+            for slot in self.slots:
+                self._drain(slot)
+        finally:
+            self.pool.shutdown(wait=True, cancel_futures=True)
