@@ -170,6 +170,7 @@ struct W24Row {
 // lies in 0..3 --: 4 phases x 3 = 12 fp32 MFMA-units per output pixel instead of the direct form's 16.  The only differences:
 // the phase (grid z) selects the slab block, and the DMA gathers every other pixel of every other row (per-lane offsets, so it
 // costs nothing); the reduction scatters the 2x2 sub-blocks into the 4x4 gradient.
+// (Since wgrad_wino24_down_kernel -- F(2,3) x F(2,4), below -- this is the form behind REFID_W24_DOWN=0.)
 template <int NS, bool DOWN>
 __global__ __launch_bounds__(256, NS == 2 ? 2 : 3) void wgrad_wino24_kernel(const W24Args a) {
     constexpr int OT = 32 * NS, BUF_BYTES = buf_bytes(NS), XPS = DOWN ? 2 : 1;     // XPS: input pixels per phase pixel
@@ -732,11 +733,334 @@ __global__ __launch_bounds__(512, 1) void wgrad_wino24_pair_kernel(const W24Args
     }
 }
 
+// conv_down, F(2,3) x F(2,4) form (REFID_W24_DOWN, the default).  A parity phase needs only 2 taps per direction, so the
+// SAME four transform rows (By^T of F(2,3) is By^T of F(3,2): points 0, +-1, inf on a 4-row window) cover THREE gradient rows
+// instead of two, and five column points (0, +-1, 2, inf) cover 2 taps x FOUR gradient columns: per 3 x 4 gradient tile and
+// its 4 x 5 window 20 products per 12 pixels, 4 phases x 20 / 12 = 6.67 fp32 MFMA-units per output pixel instead of the
+// sub-block form's 12 -- and nothing computed is thrown away.
+//     Gy rows {g0, g0+g1+g2, g0-g1+g2, g2}                        Ay^T = [1 1/2 1/2 0; 0 1/2 -1/2 1]  (By^T row 3 is d3 - d1)
+//     Gx rows {1,0,0,0} {1,1,1,1} {1,-1,1,-1} {1,2,4,8} {0,0,0,1}  Ax^T = [1 1 1 1 0; 0 1 -1 2 1] diag(1/2, -1/2, -1/6, 1/6, 1)
+//     Bx^T rows [2,-1,-2,1,0] [0,-2,-1,1,0] [0,2,-3,1,0] [0,-1,0,1,0] [0,2,-1,-2,1]
+// The window of a phase of parity 0 (taps at offsets {0, +1}: ky = 1, 3) starts at the tile's own row, that of parity 1
+// (offsets {-1, 0}: ky = 0, 2) one phase pixel earlier: the pad is php down and phq across.  Wave w is still transform row w
+// (xi = 5w .. 5w+4: 10 accumulators = 160 registers) of a 64(o) x 32(i) channel tile; K tile = 2 x 4 tiles of 3 x 4 pixels
+// (6 x 16 gradient pixels, a 7 x 17 halo at the 18-pixel pitch; MFMA K half = tile row: the lane's row base is 3 kh).
+// Two stages laid out region by region, [X s0][X s1][dY s0][dY s1], so that both stages lie inside the offset range of
+// ds_read2st64 from ONE set of bases; 81,408 B for NS = 2: two workgroups per CU (162,816 of 163,840 B).
+constexpr int DGH = 6, DXH = DGH + 1;                  // gradient rows / halo rows of a K tile (columns: GW, pitch XW)
+constexpr int DX_BYTES = DXH * XW * IT * 4;            // 16,128
+constexpr int DGS_BYTES = DGH * GW * 32 * 4;           // 12,288 per 32-channel half
+constexpr int down_lds_bytes(int ns) { return 2 * (DX_BYTES + ns * DGS_BYTES); }     // 81,408 (NS = 2) / 56,832
+constexpr int NXD = 20;
+
+// The transforms of one wave (row I), packed over two consecutive tile columns like W24Row's.  Neighbouring tile columns
+// share ONE window column: column 4s+4 of the low half is column 0 of the high half.
+template <int I>
+struct W24DownRow {
+    using B = W24Row<I>;
+    static constexpr int XR = XW * IT, GR = GW * 32, GSUB = DGH * GW * 32;
+    // window columns 4s+1 .. 4s+4 (and their partners four columns on), row-transformed
+    static __device__ __forceinline__ void x_rows(lds_cf24* const (&xb)[4], int s, f32x2 (&t)[5]) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const int col = 4 * s + 1 + c;
+            lds_cf24* p = xb[col & 3] + (col & ~3) * IT;
+            const f32x2 a = f32x2{p[B::XA * XR], p[B::XA * XR + 4 * IT]};
+            const f32x2 b = f32x2{p[B::XB * XR], p[B::XB * XR + 4 * IT]};
+            t[1 + c] = B::x_comb(a, b);
+        }
+    }
+    // the K tile's first window column
+    static __device__ __forceinline__ float x_row0(lds_cf24* xe) { return B::x_comb(xe[B::XA * XR], xe[B::XB * XR]); }
+    // gradient tile columns 4s .. 4s+3 (and partners) of one 32-channel half, row-transformed: {g0, g0+g1+g2, g0-g1+g2, g2}
+    static __device__ __forceinline__ void g_rows(lds_cf24* const (&gb)[4], int s, int sub, f32x2 (&x)[4]) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const int col = 4 * s + c;
+            lds_cf24* p = gb[col & 3] + sub * GSUB + (col & ~3) * 32;
+            if constexpr (I == 0) x[c] = f32x2{p[0], p[4 * 32]};
+            else if constexpr (I == 3) x[c] = f32x2{p[2 * GR], p[2 * GR + 4 * 32]};
+            else {
+                const f32x2 g0 = f32x2{p[0], p[4 * 32]}, g1 = f32x2{p[GR], p[GR + 4 * 32]}, g2 = f32x2{p[2 * GR], p[2 * GR + 4 * 32]};
+                x[c] = I == 1 ? (g0 + g2) + g1 : (g0 + g2) - g1;
+            }
+        }
+    }
+    // V = (row) Bx over the five window columns t[0..4]
+    static __device__ __forceinline__ void v_cols(const f32x2 (&t)[5], f32x2 (&v)[5]) {
+        const f32x2 d31 = t[3] - t[1];
+        v[0] = 2.f * (t[0] - t[2]) + d31;
+        v[1] = (t[3] - t[2]) - 2.f * t[1];
+        v[2] = 2.f * t[1] + (-3.f * t[2] + t[3]);
+        v[3] = d31;
+        v[4] = (t[4] - t[2]) - 2.f * d31;
+    }
+    // Z = (row) Gx^T over the four tile columns
+    static __device__ __forceinline__ void z_cols(const f32x2 (&x)[4], f32x2 (&z)[5]) {
+        const f32x2 e = x[0] + x[2], o = x[1] + x[3], e4 = 4.f * x[2] + x[0], o4 = 4.f * x[3] + x[1];
+        z[0] = x[0]; z[1] = e + o; z[2] = e - o; z[3] = 2.f * o4 + e4; z[4] = x[3];
+    }
+};
+
+template <int NS>
+__global__ __launch_bounds__(256, 2) void wgrad_wino24_down_kernel(const W24Args a) {
+    constexpr int OT = 32 * NS, XPS = 2;                   // XPS: input pixels per phase pixel
+    constexpr int G0 = 2 * DX_BYTES, GST_BYTES = NS * DGS_BYTES;      // the gradient region; one stage of it
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int li = lane & 31, kh = lane >> 5;
+    const int phase = blockIdx.z / a.ncoT, php = phase >> 1, phq = phase & 1;
+    const int co0 = (blockIdx.z % a.ncoT) * OT, ci0 = blockIdx.y * IT;
+    const int split = blockIdx.x;
+    const int Hin = a.Hin, Win = a.Win;
+
+    const bool xFromA = ci0 < a.Ca || ci0 >= a.Ctot;
+    const int xld = xFromA ? a.ldA : a.ldB;
+    const long long gpixAll = (long long)a.N * a.Ho * a.Wo, xpixAll = (long long)a.N * Hin * Win;
+    const int limG = (int)min(gpixAll * a.ldG * 4, 0x7fffffffLL), limX = (int)min(xpixAll * xld * 4, 0x7fffffffLL);
+    const int ntAll = a.ntiles * a.groups;
+    const int chunk = (ntAll + a.nsplit - 1) / a.nsplit;
+    const int p0 = min(split * chunk, ntAll), p1 = min(p0 + chunk, ntAll);
+
+    int qg, qn, qy, qx;
+    {
+        int t = p0 < ntAll ? p0 : 0;
+        qg = t / a.ntiles; t -= qg * a.ntiles;
+        qx = t % a.tilesX; t /= a.tilesX;
+        qy = t % a.tilesY; qn = t / a.tilesY;
+    }
+    // ---- DMA roles: pieces, lane constants and the FAST / masked paths as in wgrad_wino24_kernel.  The halo needs 17 of the
+    // 18 columns a row's three pieces fetch: the FAST test lets the unused last one fall wherever it falls inside the buffer.
+    const int xq = ci0 + (lane & 7) * 4, xt = ci0 + (lane & 31), gq = co0 + (lane & 7) * 4;
+    const int xlc = ((lane >> 3) * XPS * xld + (xFromA ? xq : xq - a.Ca)) * 4;
+    const int xlt = ((lane >> 5) * XPS * xld + (xFromA ? xt : xt - a.Ca)) * 4;
+    const int glc = ((lane >> 3) * a.ldG + gq) * 4;
+    const bool fullch = ci0 + IT <= a.Ctot && co0 + OT <= a.Co;
+    constexpr int OOB = 0x7ff00000;
+    const int xRowB = XPS * Win * xld * 4, gRowB = a.Wo * a.ldG * 4;
+    auto x_origin = [&](int n, int ty, int tx) {           // byte offset of phase pixel (ty DGH - php, tx GW - phq) of sample n
+        return ((n * Hin + XPS * (ty * DGH - php) + php) * Win + XPS * (tx * GW - phq) + phq) * xld * 4;
+    };
+    const float* gPtr = a.g[qg];
+    const float* xPtr = xFromA ? a.inA[qg] : a.inB[qg];
+    int xTile = x_origin(qn, qy, qx);
+    int gTile = ((qn * a.Ho + qy * DGH) * a.Wo + qx * GW) * a.ldG * 4;
+    // this wave's share of a request: halo rows wave and wave + 4 (wave 3: one row), and gradient (half, row) pieces
+    // q = 6 half + row: NS = 2: three each (12 / 12 / 12 / 9 DMA instructions), NS = 1: one each, wave 3 three (8 / 8 / 8 / 9)
+    const int q0 = NS == 2 ? 3 * wave : wave, nq = NS == 2 ? 3 : (wave < 3 ? 1 : 3);
+    auto request = [&](int buf) {
+        const int oy0 = qy * DGH, ox0 = qx * GW;
+        const int iy0 = oy0 - php, ix0 = ox0 - phq;
+        const __amdgpu_buffer_rsrc_t rsG = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(gPtr), 0, limG, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xPtr), 0, limX, 0x00020000);
+        char* xdst = smem + buf * DX_BYTES;
+        char* gdst = smem + G0 + buf * GST_BYTES;
+        const bool fast = fullch && ix0 >= 0 && ix0 + XW - 1 <= a.W && ox0 + GW <= a.Wo && xld * 8 * XPS * 4 < 0x100000 && a.ldG * 8 * 4 < 0x100000;
+        if (fast) {
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const int r = wave + 4 * k;
+                if (r < DXH) {
+                    const int base = (unsigned)(iy0 + r) < (unsigned)a.H ? xTile + r * xRowB : OOB;
+                    char* dst = xdst + r * (XW * IT * 4);
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_ptr24)dst, 16, base + xlc, 0, 0, 0);
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_ptr24)(dst + 1024), 16, base + 8 * XPS * xld * 4 + xlc, 0, 0, 0);
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_ptr24)(dst + 2048), 4, base + 16 * XPS * xld * 4 + xlt, 0, 0, 0);
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                if (k < nq) {
+                    const int q = q0 + k, r = q % DGH, sub = q / DGH;
+                    const int base = oy0 + r < a.Ho ? gTile + r * gRowB + sub * 128 : OOB;
+                    char* dst = gdst + sub * DGS_BYTES + r * (GW * 32 * 4);
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsG, (lds_ptr24)dst, 16, base + glc, 0, 0, 0);
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsG, (lds_ptr24)(dst + 1024), 16, base + 8 * a.ldG * 4 + glc, 0, 0, 0);
+                }
+            }
+        } else {
+            const int l8 = lane >> 3, l32 = lane >> 5;
+            const int xbadq = xq < a.Ctot ? 0 : -1, xbadt = xt < a.Ctot ? 0 : -1;
+            const int gbad0 = gq < a.Co ? 0 : -1, gbad1 = gq + 32 < a.Co ? 0 : -1;         // (NS = 1: no second half)
+            const int cx0 = (unsigned)(ix0 + l8) < (unsigned)a.W ? 0 : -1;               // column tests (per lane)
+            const int cx1 = (unsigned)(ix0 + 8 + l8) < (unsigned)a.W ? 0 : -1;
+            const int cxt = (unsigned)(ix0 + 16 + l32) < (unsigned)a.W ? 0 : -1;
+            const int cg0 = ox0 + l8 < a.Wo ? 0 : -1, cg1 = ox0 + 8 + l8 < a.Wo ? 0 : -1;
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const int r = wave + 4 * k;
+                if (r < DXH) {
+                    const int rbad = (unsigned)(iy0 + r) < (unsigned)a.H ? 0 : -1;
+                    const int base = xTile + r * xRowB;                                   // bytes, < 2^31 for live lanes (host check)
+                    char* dst = xdst + r * (XW * IT * 4);
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_ptr24)dst, 16, (base + xlc) | xbadq | rbad | cx0, 0, 0, 0);
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_ptr24)(dst + 1024), 16,
+                                                             (base + 8 * XPS * xld * 4 + xlc) | xbadq | rbad | cx1, 0, 0, 0);
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_ptr24)(dst + 2048), 4,
+                                                             (base + 16 * XPS * xld * 4 + xlt) | xbadt | rbad | cxt, 0, 0, 0);
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                if (k < nq) {
+                    const int q = q0 + k, r = q % DGH, sub = q / DGH;
+                    const int rbad = oy0 + r < a.Ho ? 0 : -1;
+                    const int base = gTile + r * gRowB + sub * 128;
+                    const int gbad = sub ? gbad1 : gbad0;
+                    char* dst = gdst + sub * DGS_BYTES + r * (GW * 32 * 4);
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsG, (lds_ptr24)dst, 16, (base + glc) | gbad | rbad | cg0, 0, 0, 0);
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsG, (lds_ptr24)(dst + 1024), 16,
+                                                             (base + 8 * a.ldG * 4 + glc) | gbad | rbad | cg1, 0, 0, 0);
+                }
+            }
+        }
+        // advance
+        qx += 1;
+        if (qx != a.tilesX) {
+            xTile += GW * XPS * xld * 4;
+            gTile += GW * a.ldG * 4;
+        } else {
+            qx = 0;
+            qy += 1;
+            if (qy == a.tilesY) {
+                qy = 0;
+                qn += 1;
+                if (qn == a.N) {
+                    qn = 0;
+                    qg = min(qg + 1, a.groups - 1);
+                    gPtr = a.g[qg];
+                    xPtr = xFromA ? a.inA[qg] : a.inB[qg];
+                }
+            }
+            xTile = x_origin(qn, qy, 0);
+            gTile = (qn * a.Ho + qy * DGH) * a.Wo * a.ldG * 4;
+        }
+    };
+
+    f32x16 acc[5][NS];                                     // [j][o half]
+#pragma unroll
+    for (int j = 0; j < 5; ++j)
+#pragma unroll
+        for (int sm = 0; sm < NS; ++sm)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[j][sm][r] = 0.f;
+    float bs[NS];
+#pragma unroll
+    for (int sm = 0; sm < NS; ++sm) bs[sm] = 0.f;
+
+    // The bases point into stage 0 of each region and never change: stage 1 is 63 (X) / 48 NS (dY) units of 256 bytes
+    // further, an immediate of the same ds_read2st64 (largest unit offsets: 63 + 27 + 8 (X), 96 + 48 + 16 + 8 (dY)).
+    static_assert(DX_BYTES % 256 == 0 && DGS_BYTES % 256 == 0 && (DX_BYTES + 3 * XW * IT * 4 + 16 * IT * 4) / 256 < 256 &&
+                      (GST_BYTES + NS * DGS_BYTES) / 256 < 256, "ds_read2st64 offset range");
+    lds_cf24* xe = (lds_cf24*)smem + (3 * kh) * (XW * IT) + li;
+    lds_cf24* ge = (lds_cf24*)(smem + G0) + (3 * kh) * (GW * 32) + li;
+    lds_cf24* xb[4] = {xe, xe + IT, xe + 2 * IT, xe + 3 * IT};
+    lds_cf24* gb[4] = {ge, ge + 32, ge + 2 * 32, ge + 3 * 32};
+    asm volatile("" : "+v"(xb[0]), "+v"(xb[1]), "+v"(xb[2]), "+v"(xb[3]), "+v"(xe));
+    asm volatile("" : "+v"(gb[0]), "+v"(gb[1]), "+v"(gb[2]), "+v"(gb[3]));
+
+    auto kloop = [&](auto TI) {
+        constexpr int I = decltype(TI)::value;
+        using R = W24DownRow<I>;
+        auto tile = [&](auto BUF) {
+            constexpr int XO = decltype(BUF)::value * (DX_BYTES / 4), GO = decltype(BUF)::value * (GST_BYTES / 4);      // floats
+            lds_cf24* xbb[4] = {xb[0] + XO, xb[1] + XO, xb[2] + XO, xb[3] + XO};
+            lds_cf24* gbb[4] = {gb[0] + GO, gb[1] + GO, gb[2] + GO, gb[3] + GO};
+            f32x2 t[5], p4;
+#pragma unroll
+            for (int s = 0; s < TC; s += 2) {
+                // window columns 4s+k (low half) and 4s+4+k (high half); column 0 of the high half is column 4 of the low
+                // half, column 0 of the low half the previous pair's column 4 of the high half (p4), or the tile's first
+                R::x_rows(xbb, s, t);
+                if (s == 0) {
+                    const float c0 = R::x_row0(xe + XO);
+                    t[0] = w24_pair<0, 0>(f32x2{c0, c0}, t[4]);
+                } else {
+                    t[0] = w24_pair<1, 0>(p4, t[4]);
+                }
+                p4 = t[4];
+                f32x2 v[5];
+                R::v_cols(t, v);
+#pragma unroll
+                for (int sm = 0; sm < NS; ++sm) {
+                    f32x2 x[4], z[5];
+                    R::g_rows(gbb, s, sm, x);
+                    R::z_cols(x, z);
+                    if constexpr (I == 1) bs[sm] += z[1][0] + z[1][1];     // point (1, 1) = sum of the 3x4 gradient tile
+#pragma unroll
+                    for (int h = 0; h < 2; ++h)
+#pragma unroll
+                        for (int j = 0; j < 5; ++j)
+                            acc[j][sm] = __builtin_amdgcn_mfma_f32_32x32x2f32(v[j][h], z[j][h], acc[j][sm], 0, 0, 0);
+                }
+            }
+        };
+        auto sync = [&] {
+            __builtin_amdgcn_s_waitcnt(0x0F70);            // vmcnt(0): this wave's pieces of the tile have landed
+            __builtin_amdgcn_s_barrier();                  // ... everybody's; and everybody is done with the other stage
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        // (pairs in the loop, an odd last tile after it: no exit from the middle of the loop body)
+        const int npairs = (p1 - p0) >> 1;
+        if (p0 < p1) request(0);
+        for (int i = 0; i < npairs; ++i) {
+            sync();
+            request(1);
+            tile(std::integral_constant<int, 0>{});
+            sync();
+            if (p0 + 2 * i + 2 < p1) request(0);
+            tile(std::integral_constant<int, 1>{});
+        }
+        if ((p1 - p0) & 1) {
+            sync();
+            tile(std::integral_constant<int, 0>{});
+        }
+    };
+    switch (wave) {
+        case 0: kloop(std::integral_constant<int, 0>{}); break;
+        case 1: kloop(std::integral_constant<int, 1>{}); break;
+        case 2: kloop(std::integral_constant<int, 2>{}); break;
+        default: kloop(std::integral_constant<int, 3>{}); break;
+    }
+
+    // ---- slab: [split][phase][xi][co][ci]; D[ci][co]: lane li = output channel, register quad = 4 ci ------
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+        float* sl = a.slabs + ((long long)((split * 4 + phase) * NXD + wave * 5 + j) * a.CoP) * a.CiP;
+#pragma unroll
+        for (int sm = 0; sm < NS; ++sm) {
+            const int co = co0 + sm * 32 + li;
+#pragma unroll
+            for (int qd = 0; qd < 4; ++qd) {
+                const int ci = ci0 + 8 * qd + 4 * kh;
+                f32x4 vv;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) vv[k] = acc[j][sm][4 * qd + k];
+                f32x4* dst = reinterpret_cast<f32x4*>(sl + (long long)co * a.CiP + ci);
+                if (a.accum) vv += *dst;
+                *dst = vv;
+            }
+        }
+    }
+    if (a.bslabs != nullptr && blockIdx.y == 0 && phase == 0 && wave == 1) {
+        // wave 1 holds the tile sums of the output channels: the two tile rows (kh) by one shuffle -- fixed order
+#pragma unroll
+        for (int sm = 0; sm < NS; ++sm) {
+            const float tot = bs[sm] + __shfl_xor(bs[sm], 32, 64);
+            if (kh == 0) {
+                float* dst = a.bslabs + (long long)split * a.CoP + co0 + sm * 32 + li;
+                *dst = a.accum ? *dst + tot : tot;
+            }
+        }
+    }
+}
+
 struct W24rArgs {
     const float* slabs; const float* bslabs; float* dw; float* db;
     int nsplit, Co, Ci, CoP, CiP, iBase, iTotal, perGroup;
     int nsplitW;                           // slabs behind `slabs` (= nsplit, or the folded count); bslabs always has nsplit rows
-    int down;                              // (batched launch) the conv_down form of the stage
+    int down;                              // the conv_down form of the stage: 1 = 3x3 sub-blocks of 24 planes, 2 = F(2,3) x F(2,4)
 };
 
 // First stage of the slab reduction.  Reading the slabs per (co, ci) element touches 64-256 contiguous bytes of each of 24 planes
@@ -900,7 +1224,56 @@ __device__ __forceinline__ void w24_reduce_down_body(const W24rArgs& a, const in
     }
 }
 
-__global__ __launch_bounds__(256) void wgrad_wino24_reduce_down_kernel(const W24rArgs a) { w24_reduce_down_body(a, blockIdx.x); }
+// F(2,3) x F(2,4) form of conv_down: per (co, ci, phase) the 20 planes -> the phase's 2x2 taps dg = Ay^T dU Ax, scattered to
+// ky = 2u + 1 - p, kx = 2v + 1 - q (parity 0: taps 1, 3; parity 1: taps 0, 2).  Same thread mapping and slab order as above.
+__device__ __forceinline__ void w24_reduce_down23_body(const W24rArgs& a, const int blk) {
+    const long long plane = (long long)a.CoP * a.CiP;
+    const long long slabStride = 4 * NXD * plane;
+    const long long gid = (long long)blk * 256 + threadIdx.x;
+    const long long e = gid >> 2;
+    const int ph = (int)(gid & 3);
+    const bool live = e < (long long)a.Co * a.Ci;
+    const int ci = live ? (int)(e % a.Ci) : 0, co = live ? (int)(e / a.Ci) : 0;
+    if (live) {
+        const float* p = a.slabs + (long long)co * a.CiP + ci + ph * NXD * plane;
+        float u[NXD];
+#pragma unroll
+        for (int x = 0; x < NXD; ++x) u[x] = 0.f;
+        for (int k = 0; k < a.nsplitW; ++k) {
+#pragma unroll
+            for (int x = 0; x < NXD; ++x) u[x] += p[k * slabStride + x * plane];
+        }
+        constexpr float c6 = 1.f / 6.f;
+        float* dst = a.dw + ((long long)co * a.iTotal + a.iBase + ci) * 16;
+#pragma unroll
+        for (int pp = 0; pp < 2; ++pp) {
+            const int ky = 2 * pp + 1 - (ph >> 1);
+            float t[5];
+#pragma unroll
+            for (int j = 0; j < 5; ++j) {
+                const float m = 0.5f * (u[5 + j] + u[10 + j]), d = 0.5f * (u[5 + j] - u[10 + j]);
+                t[j] = pp == 0 ? u[j] + m : d + u[15 + j];
+            }
+            // Ax^T = [ 1/2 -1/2 -1/6 1/6 0 ; 0 -1/2 1/6 1/3 1 ]
+            const float r2[2] = {0.5f * (t[0] - t[1]) + c6 * (t[3] - t[2]), (c6 * t[2] - 0.5f * t[1]) + (2.f * c6 * t[3] + t[4])};
+            const int kx = 1 - (ph & 1);
+            dst[ky * 4 + kx] += r2[0];
+            dst[ky * 4 + kx + 2] += r2[1];
+        }
+    }
+    if (a.db != nullptr && blk == 0) {
+        for (int c2 = threadIdx.x; c2 < a.Co; c2 += 256) {
+            float sacc = 0.f;
+            for (int k = 0; k < a.nsplit; ++k) sacc += a.bslabs[(long long)k * a.CoP + c2];
+            a.db[c2] += sacc;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void wgrad_wino24_reduce_down_kernel(const W24rArgs a) {
+    if (a.down == 2) w24_reduce_down23_body(a, blockIdx.x);
+    else w24_reduce_down_body(a, blockIdx.x);
+}
 
 // every queued reduction of the family in ONE launch (refid_wgrad_desc.phase = 4 + refid_wgrad_finish_flush)
 struct W24rBatch { W24rArgs job[REFID_FINISH_BATCH]; int blk0[REFID_FINISH_BATCH + 1]; int n; };
@@ -910,7 +1283,8 @@ __global__ __launch_bounds__(256) void wgrad_wino24_reduce_batch_kernel(const W2
     int j = 0;
     for (int k = 1; k < b.n; ++k) j = (int)blockIdx.x >= b.blk0[k] ? k : j;       // (workgroup-uniform)
     const int blk = (int)blockIdx.x - b.blk0[j];
-    if (b.job[j].down) w24_reduce_down_body(b.job[j], blk);
+    if (b.job[j].down == 2) w24_reduce_down23_body(b.job[j], blk);
+    else if (b.job[j].down) w24_reduce_down_body(b.job[j], blk);
     else w24_reduce_body(b.job[j], blk, part);
 }
 
@@ -922,14 +1296,23 @@ struct Geo24 { int ncoT, nciT, tilesX, tilesY, ntiles, nsplit, CoP, CiP; };
 int ns_of(const refid_wgrad_desc* d) { return d->c_o <= 32 ? 1 : 2; }      // 32-channel output tile for the thin layers
 bool is_down(const refid_wgrad_desc* d) { return d->kh == 4; }              // algo 7: conv_down through its parity phases
 
-Geo24 geo24_of(const refid_wgrad_desc* d) {
+// conv_down takes the F(2,3) x F(2,4) form (wgrad_wino24_down_kernel); REFID_W24_DOWN=0 keeps the 3x3 sub-block form of the
+// stride-1 kernels.  Read per call, like REFID_W24_PAIR: one process can alternate the forms (not between the launches and the
+// reduction of one set of slabs: the slab images differ).
+bool down_f23(const refid_wgrad_desc* d) {
+    if (!is_down(d)) return false;
+    const char* e = getenv("REFID_W24_DOWN");
+    return !e || atoi(e) != 0;
+}
+
+Geo24 geo24_of(const refid_wgrad_desc* d, bool f23) {
     Geo24 g;
     const int OT = 32 * ns_of(d);
     g.ncoT = cdiv(d->c_o, OT);
     const int ci_geo = (d->phase != 0) ? d->i_total - d->i_base : d->c_a + d->c_b;     // stable across steps
     g.nciT = cdiv(ci_geo > d->c_a + d->c_b ? ci_geo : d->c_a + d->c_b, IT);
     g.tilesX = cdiv(d->wo, GW);
-    g.tilesY = cdiv(d->ho, GH);
+    g.tilesY = cdiv(d->ho, f23 ? DGH : GH);
     g.ntiles = g.tilesX * g.tilesY * d->n;
     // two (NS = 1: three) workgroups per CU; a multiple of 8 splits keeps the workgroups of one K range on one XCD (grid x
     // is fastest)
@@ -1020,13 +1403,22 @@ int refid_wino24_finish_flush(hipStream_t st) {
 }
 
 namespace {
-long long slab_floats(const refid_wgrad_desc* d, const Geo24& g) { return (long long)(is_down(d) ? 4 : 1) * NXI * g.CoP * g.CiP; }
+long long slab_floats(const refid_wgrad_desc* d, const Geo24& g, bool f23) {
+    return (long long)(is_down(d) ? 4 : 1) * (f23 ? NXD : NXI) * g.CoP * g.CiP;
+}
+size_t workspace_bytes_of(const refid_wgrad_desc* d, bool f23) {
+    const Geo24 g = geo24_of(d, f23);
+    const long long slab = slab_floats(d, g, f23);
+    return ((size_t)g.nsplit * slab + (size_t)g.nsplit * g.CoP + (size_t)refid_slab_fold_count(slab, g.nsplit) * slab) * sizeof(float);
+}
 }  // namespace
 
+// (conv_down: an upper bound for both of its forms -- a buffer sized once serves whichever form a later call takes)
 size_t refid_wgrad_wino24_workspace_bytes(const refid_wgrad_desc* d) {
-    const Geo24 g = geo24_of(d);
-    const long long slab = slab_floats(d, g);
-    return ((size_t)g.nsplit * slab + (size_t)g.nsplit * g.CoP + (size_t)refid_slab_fold_count(slab, g.nsplit) * slab) * sizeof(float);
+    const size_t w = workspace_bytes_of(d, false);
+    if (!is_down(d)) return w;
+    const size_t w23 = workspace_bytes_of(d, true);
+    return w23 > w ? w23 : w;
 }
 
 int refid_wgrad_wino24_launch(const refid_wgrad_desc* d, hipStream_t st) {
@@ -1038,12 +1430,15 @@ int refid_wgrad_wino24_launch(const refid_wgrad_desc* d, hipStream_t st) {
     static std::atomic<unsigned long long> attr_done4{0}, attr_done5{0};
     if (int rc = refid_lds_attr_once(attr_done4, &wgrad_wino24_pair_kernel<false>, PAIR_LDS_BYTES, "wgrad_wino24<pair>")) return rc;
     if (int rc = refid_lds_attr_once(attr_done5, &wgrad_wino24_pair_kernel<true>, PAIR_LDS_BYTES, "wgrad_wino24<pair, down>")) return rc;
-    const Geo24 g = geo24_of(d);
-    const bool down = is_down(d);
-    const long long slab = slab_floats(d, g);
+    static std::atomic<unsigned long long> attr_done6{0}, attr_done7{0};
+    if (int rc = refid_lds_attr_once(attr_done6, &wgrad_wino24_down_kernel<2>, down_lds_bytes(2), "wgrad_wino24_down")) return rc;
+    if (int rc = refid_lds_attr_once(attr_done7, &wgrad_wino24_down_kernel<1>, down_lds_bytes(1), "wgrad_wino24_down<1>")) return rc;
+    const bool down = is_down(d), f23 = down_f23(d);
+    const Geo24 g = geo24_of(d, f23);
+    const long long slab = slab_floats(d, g, f23);
     const int pmode = pair_mode();
-    const bool pair = pmode != 0 && pair_fits(d, g);
-    REFID_CHECK(pair || pmode != 2, "wgrad (Winograd 2x4 tiles): REFID_W24_PAIR=2, but this launch takes the four-wave form "
+    const bool pair = !f23 && pmode != 0 && pair_fits(d, g);     // (the F(2,3) x F(2,4) form has no pair layout)
+    REFID_CHECK(pair || pmode != 2 || f23, "wgrad (Winograd 2x4 tiles): REFID_W24_PAIR=2, but this launch takes the four-wave form "
                                     "(c_o <= 32 or an odd number of input-channel tiles)");
     if (down)
         REFID_CHECK(d->kw == 4 && d->stride == 2 && d->pad == 1 && d->h % 2 == 0 && d->w % 2 == 0 && d->ho == d->h / 2 && d->wo == d->w / 2,
@@ -1083,7 +1478,12 @@ int refid_wgrad_wino24_launch(const refid_wgrad_desc* d, hipStream_t st) {
     a.CoP = g.CoP; a.CiP = g.CiP;
     a.accum = (d->phase == 2);
     if (d->phase != 3) {
-        if (pair) {
+        if (f23) {
+            if (ns_of(d) == 1)
+                hipLaunchKernelGGL((wgrad_wino24_down_kernel<1>), dim3(g.nsplit, g.nciT, 4 * g.ncoT), dim3(256), down_lds_bytes(1), st, a);
+            else
+                hipLaunchKernelGGL((wgrad_wino24_down_kernel<2>), dim3(g.nsplit, g.nciT, 4 * g.ncoT), dim3(256), down_lds_bytes(2), st, a);
+        } else if (pair) {
             if (down)
                 hipLaunchKernelGGL((wgrad_wino24_pair_kernel<true>), dim3(g.nsplit, g.nciT / 2, 4 * g.ncoT), dim3(512), PAIR_LDS_BYTES, st, a);
             else
@@ -1118,7 +1518,7 @@ int refid_wgrad_wino24_launch(const refid_wgrad_desc* d, hipStream_t st) {
     while (lpe < 16 && (long long)lpe * 2 * total <= 65536 && lpe * 2 <= nred) lpe *= 2;
     r.perGroup = lpe;
     r.nsplitW = nred;
-    r.down = down ? 1 : 0;
+    r.down = down ? (f23 ? 2 : 1) : 0;
     if (refid_finish_defer_now()) {
         for (const W24rQueued& q : w24_queue)              // (two jobs on one gradient block would race: flush first)
             if (q.r.dw == r.dw && q.r.iBase == r.iBase) {

@@ -39,6 +39,7 @@ def algo_key(k):
         return f"conv_wino6_kernel<{m.group(1)}, true>" if m.group(2) == "true" else f"conv_wino6_kernel<{m.group(1)}>"
     if k.startswith("conv_wino_kernel"): return k
     if k.startswith("wgrad_wino_kernel"): return "wgrad_wino_kernel"
+    if k.startswith("wgrad_wino24_down_kernel"): return "wgrad_wino24_down_kernel"      # conv_down, F(2,3) x F(2,4) form
     if k.startswith("wgrad_wino24_kernel") and "true" in k: return "wgrad_wino24_down_kernel"
     if k.startswith("wgrad_wino24_kernel"): return "wgrad_wino24_kernel"
     if k.startswith("conv_pw_kernel"):
@@ -91,6 +92,7 @@ def main():
             mult, peak, bound = 1.0, FP32, "mfma-fp32"
             if "wino6" in k and "true" in k: mult, peak, bound = 16.0 / 36.0 * 3.0, BF16, "mfma-fp16"
             elif "wino6" in k: mult, peak, bound = 16.0 / 36.0 * 6.0, BF16, "mfma-bf16"
+            elif "wino24_down" in k: mult = (20.0 / 3.0) / 16.0                 # 4 phases x 20 products per 12 pixels
             elif "wino24" in k and "true" in k: mult = 12.0 / 16.0
             elif "wino24" in k: mult = 12.0 / 36.0
             elif "wino" in k: mult = 16.0 / 36.0
