@@ -603,6 +603,44 @@ int refid_assemble_bins(int m, int n, int layout);
 /* Runs the chosen stages (REFID_ASSEMBLE_*) in the order zero, scatter, finish, frames on `stream`: one launch each. */
 int refid_assemble_batch(const refid_assemble_desc* d, int stages, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Test-time assembly of network inputs for frame pairs of ONE resident sequence (csrc/sequence.hip): the key frames and
+ * the whole event stream are uploaded once, and every pair (two key-frame indices + a row window of the stream) becomes
+ * one sample of `lq` / `voxel` in the layouts of refid_assemble_batch.  No crop, no flips, no ground truth.  The event
+ * arithmetic is that of refid_assemble_batch, bit for bit (fp32 normalisation in three roundings, 64-bit fixed-point
+ * integer atomics, one rounding to fp32; events outside the frame or with a negative normalised time are dropped;
+ * polarity <= 0 counts as -1).  Frames of any size: the outputs are (out_h, out_w) >= (height, width) planes, filled in
+ * the same launches -- image channels replicate the last row / column (np.pad mode="edge"), voxel channels are zero
+ * there.  Pair windows may overlap, be adjacent, be empty, or all cover the same rows.  The host table and every
+ * argument are validated on each call: -1 with refid_last_error() naming the offending field, nothing launched.
+ * The library allocates nothing.
+ * ---------------------------------------------------------------------------------- */
+typedef struct refid_seq_pair {
+    int left, right;                            /* key-frame indices into `frames`                                */
+    long long row0, row1;                       /* event rows [row0, row1) of the stream; may be empty            */
+    float first_stamp, last_stamp;              /* ts = (bins-1)*(t-first)/(last-first) in fp32, as refid_sample_desc */
+} refid_seq_pair;
+typedef struct refid_seq_desc {
+    const float* events;                        /* device, (n_events,4) float32 rows [t,x,y,p], 16-byte aligned    */
+    long long n_events;                         /* may be 0                                                       */
+    const unsigned char* frames;                /* device, n_frames u8 HWC key frames                             */
+    int n_frames;
+    long long frame_stride;                     /* bytes from one frame to the next                               */
+    int row_pitch;                              /* bytes from one row to the next                                 */
+    int height, width;
+    int bgr;                                    /* != 0: BGR as decoded by cv2 (swapped to RGB); 0: RGB           */
+    const refid_seq_pair* pairs_host;           /* the pair table in host memory (validated on every call)        */
+    const refid_seq_pair* pairs_dev;            /* the same table in device memory (read by the kernels)          */
+    int n_pairs;
+    int m, n, layout;                           /* REFID_LAYOUT_BLUR / REFID_LAYOUT_SHARP                         */
+    int out_h, out_w;                           /* >= height, width: the padded size the network takes            */
+    long long* scratch;                         /* int64 [n_pairs][bins][height*width]                            */
+    float* lq;                                  /* sharp: (P, 2, 3, out_h, out_w); blur: (P, 6+2(m-1), out_h, out_w) */
+    float* voxel;                               /* (P, bins-1, 2, out_h, out_w): sliding bin pairs                */
+} refid_seq_desc;
+/* Runs the chosen stages (REFID_ASSEMBLE_*) in the order zero, scatter, finish, frames on `stream`: one launch each. */
+int refid_seq_assemble(const refid_seq_desc* d, int stages, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -96,6 +96,28 @@ class AssembleDesc(C.Structure):
     ]
 
 
+class SeqPair(C.Structure):
+    """refid_seq_pair: one frame pair of a resident sequence (refid_amd.sequence.SequenceAssembler fills the table)."""
+    _fields_ = [
+        ("left", C.c_int), ("right", C.c_int),
+        ("row0", C.c_longlong), ("row1", C.c_longlong),
+        ("first_stamp", C.c_float), ("last_stamp", C.c_float),
+    ]
+
+
+class SeqDesc(C.Structure):
+    _fields_ = [
+        ("events", C.c_void_p), ("n_events", C.c_longlong),
+        ("frames", C.c_void_p), ("n_frames", C.c_int),
+        ("frame_stride", C.c_longlong), ("row_pitch", C.c_int), ("height", C.c_int), ("width", C.c_int), ("bgr", C.c_int),
+        ("pairs_host", C.c_void_p), ("pairs_dev", C.c_void_p), ("n_pairs", C.c_int),
+        ("m", C.c_int), ("n", C.c_int), ("layout", C.c_int),
+        ("out_h", C.c_int), ("out_w", C.c_int),
+        ("scratch", C.c_void_p),
+        ("lq", C.c_void_p), ("voxel", C.c_void_p),
+    ]
+
+
 LAYOUT_BLUR, LAYOUT_SHARP = 0, 1                 # == REFID_LAYOUT_* in include/refid_hip.h
 ASSEMBLE_ZERO, ASSEMBLE_SCATTER, ASSEMBLE_FINISH, ASSEMBLE_FRAMES, ASSEMBLE_ALL = 1, 2, 4, 8, 15
 
@@ -219,6 +241,7 @@ def _bind_extra(L):
     L.refid_fac_bwd.argtypes = [vp, i, vp, i, vp, i, vp, i, vp, i, ll, i, vp]
     L.refid_assemble_bins.argtypes = [i, i, i]
     L.refid_assemble_batch.argtypes = [C.POINTER(AssembleDesc), i, vp]
+    L.refid_seq_assemble.argtypes = [C.POINTER(SeqDesc), i, vp]
 
 
 def check(rc, what):

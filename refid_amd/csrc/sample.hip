@@ -20,10 +20,9 @@
 #include <cstdint>
 
 #include "common.h"
+#include "event_fixed.h"
 
 namespace {
-
-constexpr float TWO32 = 4294967296.f;
 
 struct BatchGeom {
     int bins, m, n, layout;
@@ -50,30 +49,12 @@ __global__ __launch_bounds__(256) void sample_scatter_kernel(const refid_sample_
     const float scale = (float)(g.bins - 1);
     const float4* ev = reinterpret_cast<const float4*>(s.events);
     for (long long i = blockIdx.x * 256ll + threadIdx.x; i < s.n_events; i += (long long)gridDim.x * 256) {
-        const float4 e = ev[i];                                                // [t, x, y, p]
-        const float ts = (scale * (e.x - s.first_stamp)) / dT;                 // event_util.py:37, fp32
-        if (!(ts >= 0.f && ts < (float)g.bins)) continue;                      // negative (or NaN) time; ti >= bins
-        if (!(e.y > -1.f && e.y < (float)s.width && e.z > -1.f && e.z < (float)s.height)) continue;
-        const int x = (int)e.y, y = (int)e.z;                                  // astype(int): truncation
-        const int cy = y - s.top, cx = x - s.left;
+        EventTerm t;
+        if (!event_term(ev[i], s.first_stamp, dT, scale, g.bins, s.width, s.height, t)) continue;
+        const int cy = t.y - s.top, cx = t.x - s.left;
         if (cy < 0 || cy >= g.ch || cx < 0 || cx >= g.cw) continue;
-        const int ti = (int)ts;
-        const float dts = ts - (float)ti;                                      // exact
-        const long long q = (long long)(dts * TWO32);                          // exact product, < 2^32
-        const long long one = 1ll << 32;
-        const bool pos = e.w > 0.f;
-        unsigned long long* p = acc + (long long)ti * plane + out_index(s, g, cy, cx);
-        atomicAdd(p, (unsigned long long)(pos ? one - q : q - one));           // left bin: ti < bins holds
-        if (ti + 1 < g.bins) atomicAdd(p + plane, (unsigned long long)(pos ? q : -q));
+        event_add(acc + (long long)t.ti * plane + out_index(s, g, cy, cx), plane, g.bins, t);
     }
-}
-
-__device__ __forceinline__ float fixed_to_float(long long a) { return (float)a * (1.f / TWO32); }   // RNE, then exact
-
-template <int V>
-__device__ __forceinline__ void store_v(float* p, const float* v) {
-    if constexpr (V == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    else p[0] = v[0];
 }
 
 // grid = (chunks of the plane, bins, batch); one thread = V consecutive elements of one bin plane

@@ -1,0 +1,107 @@
+"""``python -m refid_amd.interpolate``: key frames + one event stream + a checkpoint -> interpolated PNG frames.
+
+    python -m refid_amd.interpolate --opt options/test/GoPro/7skip.yml --frames seq/frames --events seq/events/*.npz \\
+        --stamps seq/timestamps.txt --out out/seq
+
+``--opt`` supplies ``network_g``, ``path.pretrain_network_g`` and ``datasets.test.num_*`` (the layout follows the model
+type: the ``*Sharp*`` classes take sharp key frames); or give ``--checkpoint`` with ``--n`` / ``--m`` / ``--layout`` and the
+released network size.  ``--frames`` is a directory of 8-bit PNGs (sorted by name) or a ``.npy`` stack (N, H, W, 3) uint8
+RGB; ``--stamps`` a text file with one key-frame timestamp per line (sharp layout) or an exposure ``start end`` per line
+(blur layout), in the events' clock.  Frame f of pair k is written to ``{out}/{k:06d}_{f:02d}.png``."""
+import argparse
+import glob
+import os
+import sys
+
+import numpy as np
+
+RELEASED_NETWORK = dict(type="FinalBidirectionAttenfusion", ev_chn=2, num_encoders=3, base_num_channels=32, num_block=1,
+                        num_residual_blocks=2)
+
+
+def load_frames(path):
+    """A directory of PNGs (sorted by name) or a ``.npy`` stack -> uint8 (N, H, W, 3) RGB."""
+    from .png import read_png
+    if os.path.isdir(path):
+        files = sorted(glob.glob(os.path.join(path, "*.png")))
+        if not files:
+            raise SystemExit(f"--frames: no *.png under {path}")
+        imgs = [read_png(f) for f in files]
+        imgs = [np.repeat(i[:, :, None], 3, axis=2) if i.ndim == 2 else i for i in imgs]
+        if len({i.shape for i in imgs}) != 1:
+            raise SystemExit(f"--frames: the PNGs under {path} differ in size")
+        return np.stack(imgs)
+    stack = np.load(path)
+    if stack.dtype != np.uint8 or stack.ndim != 4 or stack.shape[3] != 3:
+        raise SystemExit(f"--frames: {path} must hold uint8 (N, H, W, 3), got {stack.dtype} {stack.shape}")
+    return stack
+
+
+def settings(args):
+    """(network options, checkpoint path or None, m, n, layout) from --opt, overridden by the explicit arguments."""
+    net, ckpt, m, n, layout = None, None, 1, None, None
+    if args.opt:
+        from .options import parse
+        opt = parse(args.opt, is_train=False)
+        net = dict(opt["network_g"])
+        ckpt = opt.get("path", {}).get("pretrain_network_g")
+        ds = opt.get("datasets", {}).get("test", {})
+        m, n = int(ds.get("num_end_interpolation", 1)), ds.get("num_inter_interpolation")
+        layout = "sharp" if "Sharp" in str(opt.get("model_type", "")) else "blur"
+    ckpt = args.checkpoint or ckpt
+    m = args.m if args.m is not None else m
+    n = args.n if args.n is not None else n
+    layout = args.layout or layout or "sharp"
+    if n is None:
+        raise SystemExit("give --opt (datasets.test.num_inter_interpolation) or --n")
+    if net is None:
+        net = dict(RELEASED_NETWORK, img_chn=6 if layout == "sharp" else 6 + 2 * (m - 1))
+    return net, ckpt, int(m), int(n), layout
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m refid_amd.interpolate", description=__doc__.split("\n\n")[0])
+    ap.add_argument("--opt", help="a test YAML: network_g, path.pretrain_network_g, datasets.test.num_*")
+    ap.add_argument("--checkpoint", help="a .pth with the network's state dict (under 'params' or bare)")
+    ap.add_argument("--n", type=int, help="frames to interpolate between two key frames")
+    ap.add_argument("--m", type=int, help="frames to recover from each blurry key frame (blur layout)")
+    ap.add_argument("--layout", choices=("sharp", "blur"))
+    ap.add_argument("--frames", required=True, help="directory of PNG key frames, or a .npy stack (N, H, W, 3) uint8 RGB")
+    ap.add_argument("--events", required=True, nargs="+", help="event .npz files (x, y, timestamp, polarity), in time order")
+    ap.add_argument("--stamps", required=True, help="key-frame timestamps, one per line ('start end' per line for blur)")
+    ap.add_argument("--out", required=True, help="output directory")
+    ap.add_argument("--max-minibatch", type=int, default=2)
+    ap.add_argument("--swap-xy", action="store_true", help="the HighREV files' swapped x / y columns")
+    args = ap.parse_args(argv)
+
+    import torch
+    from . import sequence
+    from .archs import define_network
+    net_opt, ckpt, m, n, layout = settings(args)
+    frames = load_frames(args.frames)
+    events = sequence.load_event_npz(args.events, swap_xy=args.swap_xy)
+    stamps = np.loadtxt(args.stamps, dtype=np.float64, ndmin=2)
+    if stamps.shape[0] != frames.shape[0]:
+        raise SystemExit(f"--stamps: {stamps.shape[0]} lines for {frames.shape[0]} key frames")
+    if layout == "sharp":
+        windows = sequence.sharp_windows(stamps[:, 0])
+    elif stamps.shape[1] >= 2:
+        windows = sequence.exposure_windows(stamps[:, 0], stamps[:, 1])
+    else:
+        raise SystemExit("--stamps: the blur layout needs an exposure 'start end' per line")
+    pairs = sequence.make_pairs(events[:, 0], *windows)
+    net = define_network(net_opt).to("cuda")
+    if ckpt:
+        state = torch.load(ckpt, map_location="cpu")
+        state = state.get("params", state)
+        net.load_state_dict({(k[7:] if k.startswith("module.") else k): v for k, v in state.items()}, strict=True)
+    else:
+        print("warning: no checkpoint given: the network runs with its initial weights", file=sys.stderr)
+    names = [f"{k:06d}" for k in range(len(pairs))]
+    sequence.SequenceInterpolator(net, m, n, layout, args.max_minibatch).run(frames, events, pairs, out_dir=args.out, names=names)
+    print(f"{len(pairs)} pairs -> {args.out}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -107,12 +107,12 @@ def psnr_from_sqerr(sq, count):
 METRIC_TYPES = ("calculate_psnr", "calculate_ssim")
 
 
-def check_metric_options(val_opt, use_image=True):
+def check_metric_options(val_opt, use_image=True, groups=("metrics_deblur", "metrics_interpo")):
     """What nondist_validation here supports of opt['val'] (no shipped YAML asks for more); names the offending key."""
     if not use_image:
         raise RefidHipError("use_image=False is not supported (the reference's branch feeds 5-D tensors to reorder_image "
                             "and cannot run)")
-    for group in ("metrics_deblur", "metrics_interpo"):
+    for group in groups:
         for name, o in (val_opt.get(group) or {}).items():
             where = f"val.{group}.{name}"
             if o.get("type") not in METRIC_TYPES:
@@ -140,6 +140,12 @@ class ValidationMetrics:
         self.deblur = {k: 0 for k in (metrics_deblur or {})}
         self.interpo = {k: 0 for k in self.opt_interpo}
         self.total = {k: 0 for k in self.deblur}
+
+    def metric_types(self):
+        """The metric functions in use: what the loop asks metrics.val_tail for."""
+        if not self.with_metrics:
+            return set()
+        return {o["type"] for o in list(self.opt_deblur.values()) + list(self.opt_interpo.values())}
 
     def add_item(self, per_frame):
         """per_frame: {'calculate_psnr': [T values], 'calculate_ssim': [T values]} of ONE sample (only the types in use)."""
@@ -179,3 +185,43 @@ class ValidationMetrics:
                 s += f"\t # {k}: {v:.4f}"
             out.append(s)
         return out
+
+
+class InterpolationMetrics:
+    """The sharp models' bookkeeping (Test_twoSharpImage_event_recurrent_model.py:364-370, :453-502), without any GPU
+    dependency: every frame of an item is an interpolation frame; ``finish`` divides the sums by cnt * T (T: the frame
+    count of the last item, the reference's `imgs_per_iter`) and returns the last metric in dict order (0. without
+    metrics); one log line.  Same interface as ``ValidationMetrics``."""
+
+    def __init__(self, metrics_interpo):
+        self.opt_interpo = metrics_interpo
+        self.with_metrics = metrics_interpo is not None
+        self.cnt = 0
+        self.frames = 0
+        self.interpo = {k: 0 for k in (metrics_interpo or {})}
+
+    def metric_types(self):
+        return {o["type"] for o in self.opt_interpo.values()} if self.with_metrics else set()
+
+    def add_item(self, per_frame):
+        self.cnt += 1
+        if not self.with_metrics:
+            return
+        self.frames = len(next(iter(per_frame.values()))) if per_frame else 0
+        for idx in range(self.frames):
+            for name, o in self.opt_interpo.items():
+                self.interpo[name] += per_frame[o["type"]][idx]
+
+    def finish(self):
+        current = 0.
+        if self.with_metrics:
+            for k in self.interpo:
+                self.interpo[k] /= (self.cnt * self.frames)
+                current = self.interpo[k]
+        return current
+
+    def log_lines(self, dataset_name):
+        s = f"Validation {dataset_name} [interpolation],\t"
+        for k, v in self.interpo.items():
+            s += f"\t # {k}: {v:.4f}"
+        return [s]

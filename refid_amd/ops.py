@@ -967,3 +967,8 @@ def assemble_bins(m, n, layout):
 def assemble_batch(desc, stages=_lib.ASSEMBLE_ALL):
     """Runs the batch-assembly kernels of csrc/sample.hip for an _lib.AssembleDesc on the current stream."""
     check(lib().refid_assemble_batch(C.byref(desc), int(stages), _stream()), "refid_assemble_batch")
+
+
+def seq_assemble(desc, stages=_lib.ASSEMBLE_ALL):
+    """Runs the pair-assembly kernels of csrc/sequence.hip for an _lib.SeqDesc on the current stream."""
+    check(lib().refid_seq_assemble(C.byref(desc), int(stages), _stream()), "refid_seq_assemble")

@@ -1,4 +1,4 @@
-"""A PNG writer (and a reader for its own files) on the standard library alone: the validation image dumps of the
+"""A PNG writer and a reader for 8-bit RGB / grey files on the standard library alone: the validation image dumps of the
 reference go through cv2.imwrite (utils/img_util.py:152-170), and cv2 is not a dependency here.
 
 8-bit RGB (H, W, 3) or 8-bit grey (H, W); signature, IHDR, one IDAT, IEND; filter type 0 on every row; one
@@ -57,8 +57,44 @@ def read_chunks(data):
     return out
 
 
+def _unfilter(rows, bpp):
+    """Undoes the per-row PNG filters (0 None, 1 Sub, 2 Up, 3 Average, 4 Paeth) of ``rows`` (h, 1 + stride) uint8; returns
+    (h, stride).  Sub is a running sum along the row and Up adds the finished row above: both vectorised.  Average and
+    Paeth depend on the byte just reconstructed, so they walk the row byte by byte -- correctness first; frames written
+    by this package use filter 0 and never get here."""
+    h, stride = rows.shape[0], rows.shape[1] - 1
+    out = np.zeros((h, stride), dtype=np.uint8)
+    zero = np.zeros(stride, dtype=np.uint8)
+    for y in range(h):
+        ft, cur = int(rows[y, 0]), rows[y, 1:]
+        up = out[y - 1] if y else zero
+        if ft == 0:
+            out[y] = cur
+        elif ft == 1:                                       # x + left: a cumulative sum per byte lane, modulo 256
+            lanes = cur.reshape(-1, bpp).astype(np.uint32)
+            out[y] = (np.cumsum(lanes, axis=0) & 0xff).astype(np.uint8).reshape(-1)
+        elif ft == 2:
+            out[y] = cur + up                               # uint8 arithmetic wraps modulo 256
+        elif ft in (3, 4):
+            line, above, rec = cur.tolist(), up.tolist(), [0] * stride
+            for i in range(stride):
+                a = rec[i - bpp] if i >= bpp else 0
+                b = above[i]
+                if ft == 3:
+                    pred = (a + b) >> 1
+                else:
+                    c = above[i - bpp] if i >= bpp else 0
+                    pa, pb, pc = abs(b - c), abs(a - c), abs(a + b - 2 * c)
+                    pred = a if (pa <= pb and pa <= pc) else (b if pb <= pc else c)
+                rec[i] = (line[i] + pred) & 0xff
+            out[y] = rec
+        else:
+            raise ValueError(f"read_png: unknown filter type {ft} in row {y}")
+    return out
+
+
 def read_png(path):
-    """Decodes what write_png writes (8-bit RGB / grey, no interlace, filter 0 only) into a uint8 array."""
+    """Decodes an 8-bit RGB / grey, non-interlaced PNG (all five filter types) into a uint8 array (H, W, 3) / (H, W)."""
     with open(path, "rb") as f:
         chunks = read_chunks(f.read())
     if not chunks or chunks[0][0] != b"IHDR" or chunks[-1][0] != b"IEND":
@@ -71,7 +107,6 @@ def read_png(path):
     if len(raw) != h * (1 + w * ch):
         raise ValueError("read_png: image data has the wrong length")
     rows = np.frombuffer(raw, dtype=np.uint8).reshape(h, 1 + w * ch)
-    if rows[:, 0].any():
-        raise ValueError("read_png: only filter type 0 is supported")
-    img = rows[:, 1:].reshape(h, w, ch) if ch == 3 else rows[:, 1:]
+    data = _unfilter(rows, ch) if rows[:, 0].any() else rows[:, 1:]
+    img = data.reshape(h, w, ch) if ch == 3 else data
     return np.ascontiguousarray(img)

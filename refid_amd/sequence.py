@@ -1,0 +1,279 @@
+"""Test-time entry: interpolate the frame pairs of a whole sequence, without ground truth and at any frame size.
+
+The key frames and ONE event stream of a sequence are uploaded once (``SequenceAssembler.load``); every pair -- two
+key-frame indices and a row window of the stream -- becomes one sample of ``lq`` / ``voxel`` through the kernels of
+csrc/sequence.hip, padded up to the multiple the network takes.  ``SequenceInterpolator`` runs the network over the
+pairs in minibatches, assembling minibatch k+1 on a side stream while minibatch k computes (the way ``CUDAPrefetcher``
+does it), crops the result back, quantises it with ``metrics.val_tail`` and hands the uint8 frames to
+``validation.FrameWriter``.
+
+Window search stays on the host: the host loaded the events, so ``np.searchsorted`` over the same float32 timestamp
+column the kernel reads costs nothing and needs no synchronisation."""
+import collections
+import ctypes as C
+import os
+
+import numpy as np
+import torch
+
+from . import _lib, metrics
+from ._lib import RefidHipError
+
+Pair = collections.namedtuple("Pair", "left right row0 row1 first_stamp last_stamp")
+
+
+def pair_windows(t, begins, ends):
+    """Event rows of the half-open time windows [begins[k], ends[k]) of a stream: an int64 (K, 2) array of
+    ``[searchsorted(t, begins[k], 'left'), searchsorted(t, ends[k], 'left'))``.  ``t`` is the float32 timestamp column
+    (non-decreasing, else RefidHipError); the bounds are cast to float32, the type the events carry.  An event exactly at
+    ``ends[k]`` belongs to the next window."""
+    t = np.ascontiguousarray(np.asarray(t, dtype=np.float32).reshape(-1))
+    if t.size > 1 and bool(np.any(t[1:] < t[:-1])):
+        raise RefidHipError("pair_windows: the event timestamps are not non-decreasing (sort the stream by time first)")
+    b = np.asarray(begins, dtype=np.float32).reshape(-1)
+    e = np.asarray(ends, dtype=np.float32).reshape(-1)
+    if b.shape != e.shape:
+        raise RefidHipError(f"pair_windows: {b.size} window begins, {e.size} window ends")
+    r0 = np.searchsorted(t, b, "left").astype(np.int64)
+    r1 = np.maximum(np.searchsorted(t, e, "left").astype(np.int64), r0)        # ends[k] < begins[k]: an empty window
+    return np.stack([r0, r1], axis=1)
+
+
+def sharp_windows(frame_stamps):
+    """Sharp key frames: pairs (k, k+1) with the window [stamp_k, stamp_{k+1}).  Returns (lefts, rights, begins, ends)."""
+    s = np.asarray(frame_stamps).reshape(-1)
+    k = np.arange(max(len(s) - 1, 0))
+    return k, k + 1, s[:-1], s[1:]
+
+
+def exposure_windows(starts, ends):
+    """Blurry key frames with exposures [starts[k], ends[k]]: pairs (k, k+1) with the window [start_k, end_{k+1}), which
+    covers both exposures (consecutive windows overlap).  Returns (lefts, rights, begins, ends)."""
+    s, e = np.asarray(starts).reshape(-1), np.asarray(ends).reshape(-1)
+    if s.shape != e.shape:
+        raise RefidHipError(f"exposure_windows: {s.size} exposure starts, {e.size} exposure ends")
+    k = np.arange(max(len(s) - 1, 0))
+    return k, k + 1, s[:-1], e[1:]
+
+
+def make_pairs(t, lefts, rights, begins, ends, stamps="events"):
+    """[Pair] for ``SequenceAssembler.assemble``.  ``stamps='events'`` (what the reference datasets do, event_util.py:25-31):
+    the normalisation runs from the stamp of the first row of the window to that of its last row; an empty window gives
+    (0, 0) and an all-zero voxel.  ``stamps='bounds'``: from ``begins[k]`` to ``ends[k]`` (as float32)."""
+    if stamps not in ("events", "bounds"):
+        raise RefidHipError(f"make_pairs: unknown stamps {stamps!r} ('events' or 'bounds')")
+    t = np.asarray(t, dtype=np.float32).reshape(-1)
+    rows = pair_windows(t, begins, ends)
+    lefts, rights = np.asarray(lefts).reshape(-1), np.asarray(rights).reshape(-1)
+    if not len(lefts) == len(rights) == len(rows):
+        raise RefidHipError(f"make_pairs: {len(lefts)} lefts, {len(rights)} rights, {len(rows)} windows")
+    b32, e32 = np.asarray(begins, dtype=np.float32).reshape(-1), np.asarray(ends, dtype=np.float32).reshape(-1)
+    out = []
+    for k, (r0, r1) in enumerate(rows.tolist()):
+        if stamps == "bounds":
+            first, last = float(b32[k]), float(e32[k])
+        else:
+            first, last = (float(t[r0]), float(t[r1 - 1])) if r1 > r0 else (0.0, 0.0)
+        out.append(Pair(int(lefts[k]), int(rights[k]), r0, r1, first, last))
+    return out
+
+
+def load_event_npz(paths, swap_xy=False):
+    """The reference's per-frame event files (``.npz`` with keys ``x``, ``y``, ``timestamp``, ``polarity``) concatenated to
+    float32 rows [t, x, y, p], exactly as image_sharp_npy_dataset.py:145-163 builds them.  ``swap_xy``: the HighREV
+    files carry x and y in each other's column (image_sharp_Ruisi_dataset.py:145-157).
+
+    float32 timestamps are the reference's choice, and they are kept because the voxel grid is defined on them.  What it
+    costs: float32 has 24 significant bits, so the spacing of representable stamps is t * 2^-23 -- 1 us near t = 8 s of a
+    microsecond clock, 8 us near a minute, and at epoch-sized stamps (1.6e15 us) 1.3e8 us, where every event of a window
+    collapses onto a few values.  Subtract a per-sequence origin before saving such streams."""
+    if isinstance(paths, (str, os.PathLike)):
+        paths = [paths]
+    out = np.zeros((0, 4), dtype=np.float32)
+    for path in paths:
+        z = np.load(path)
+        x = z["x"].astype(np.float32).reshape(-1, 1)
+        y = z["y"].astype(np.float32).reshape(-1, 1)
+        t = z["timestamp"].astype(np.float32).reshape(-1, 1)
+        p = z["polarity"].astype(np.float32).reshape(-1, 1)
+        if swap_xy:
+            x, y = y, x
+        out = np.concatenate((out, np.concatenate((t, x, y, p), axis=1)), axis=0)
+    return out
+
+
+def _round_up(v, multiple):
+    return (v + multiple - 1) // multiple * multiple
+
+
+class SequenceAssembler:
+    """``{'lq', 'voxel'}`` for frame pairs of one resident sequence (csrc/sequence.hip), in the layouts of
+    ``DeviceBatchAssembler``: ``layout='sharp'``: n+1 bins, lq (P, 2, 3, h, w); ``layout='blur'``: 2m+n+1 bins, lq
+    (P, 6+2(m-1), h, w) = frame[left] | bins 1..m-1 | frame[right] | bins m+2+n..; voxel (P, bins-1, 2, h, w).  (h, w) is
+    the frame size rounded up to ``multiple``: image channels replicate the last row / column there, voxel channels are
+    zero.  Everything runs on the current stream; the cached scratch and pair table are ordered by that stream only: use
+    one assembler per stream."""
+
+    def __init__(self, m, n, layout="sharp", multiple=8, device=None):
+        if layout not in ("blur", "sharp"):
+            raise RefidHipError(f"SequenceAssembler: unknown layout {layout!r} ('blur' or 'sharp')")
+        from . import ops
+        self.m, self.n = int(m), int(n)
+        self.layout = layout
+        self._layout = _lib.LAYOUT_BLUR if layout == "blur" else _lib.LAYOUT_SHARP
+        self.bins = ops.assemble_bins(self.m, self.n, self._layout)
+        self.multiple = int(multiple)
+        if self.multiple < 1:
+            raise RefidHipError(f"SequenceAssembler: multiple {multiple} must be >= 1")
+        self.device = torch.device("cuda" if device is None else device)
+        if self.device.type != "cuda":
+            raise RefidHipError("SequenceAssembler: a GPU device is required (the HIP path has no CPU fallback)")
+        self.frames = self.events = None
+        self._cache = {}                      # (P, H, W) -> scratch, device table, pinned table, event of the last upload
+        self._last = None                     # descriptor and host table of the last call: lets a test or benchmark relaunch it
+
+    def load(self, frames, events, bgr=False):
+        """Uploads the sequence once: ``frames`` uint8 (N, H, W, 3), ``events`` float32 (E, 4) rows [t, x, y, p] (E may be
+        0); numpy arrays or tensors, host or device.  ``bgr``: the frames are BGR as cv2 decodes them."""
+        frames = torch.as_tensor(frames) if not torch.is_tensor(frames) else frames
+        events = torch.as_tensor(events) if not torch.is_tensor(events) else events
+        if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or frames.shape[0] < 1:
+            raise RefidHipError(f"SequenceAssembler.load: frames must be uint8 (N, H, W, 3), got {frames.dtype} "
+                                f"{tuple(frames.shape)}")
+        if events.dtype != torch.float32 or events.dim() != 2 or events.shape[1] != 4:
+            raise RefidHipError(f"SequenceAssembler.load: events must be float32 (E, 4) rows [t, x, y, p], got "
+                                f"{events.dtype} {tuple(events.shape)}")
+        self.frames = frames.contiguous().to(self.device, non_blocking=True)
+        self.events = events.contiguous().to(self.device, non_blocking=True)
+        self.bgr = bool(bgr)
+        self.height, self.width = int(frames.shape[1]), int(frames.shape[2])
+        self.out_h, self.out_w = _round_up(self.height, self.multiple), _round_up(self.width, self.multiple)
+        return self
+
+    def _geometry(self, count):
+        key = (count, self.height, self.width)
+        c = self._cache.get(key)
+        if c is None:
+            nbytes = count * C.sizeof(_lib.SeqPair)
+            c = {"scratch": torch.empty((count, self.bins, self.height, self.width), dtype=torch.int64, device=self.device),
+                 "table_dev": torch.empty(nbytes, dtype=torch.uint8, device=self.device),
+                 "table_pin": torch.empty(nbytes, dtype=torch.uint8).pin_memory(),
+                 "uploaded": None}
+            self._cache[key] = c
+        return c
+
+    def assemble(self, pairs, stages=_lib.ASSEMBLE_ALL):
+        from . import ops
+        if self.frames is None:
+            raise RefidHipError("SequenceAssembler.assemble: load() a sequence first")
+        pairs = list(pairs)
+        if not pairs:
+            raise RefidHipError("SequenceAssembler.assemble: no pairs")
+        count = len(pairs)
+        table = (_lib.SeqPair * count)()
+        for k, p in enumerate(pairs):
+            d = table[k]
+            d.left, d.right, d.row0, d.row1 = int(p[0]), int(p[1]), int(p[2]), int(p[3])
+            d.first_stamp, d.last_stamp = float(p[4]), float(p[5])
+        c = self._geometry(count)
+        if c["uploaded"] is not None:
+            c["uploaded"].synchronize()       # the previous table copy has left the pinned buffer
+        C.memmove(c["table_pin"].data_ptr(), C.addressof(table), C.sizeof(table))
+        c["table_dev"].copy_(c["table_pin"], non_blocking=True)
+        c["uploaded"] = torch.cuda.Event()
+        c["uploaded"].record()
+        h, w = self.out_h, self.out_w
+        if self.layout == "blur":
+            lq = torch.empty((count, 6 + 2 * (self.m - 1), h, w), dtype=torch.float32, device=self.device)
+        else:
+            lq = torch.empty((count, 2, 3, h, w), dtype=torch.float32, device=self.device)
+        voxel = torch.empty((count, self.bins - 1, 2, h, w), dtype=torch.float32, device=self.device)
+        desc = _lib.SeqDesc()
+        n_ev = int(self.events.shape[0])
+        desc.events, desc.n_events = (self.events.data_ptr() if n_ev else None), n_ev
+        desc.frames, desc.n_frames = self.frames.data_ptr(), int(self.frames.shape[0])
+        desc.frame_stride, desc.row_pitch = self.height * self.width * 3, self.width * 3
+        desc.height, desc.width, desc.bgr = self.height, self.width, int(self.bgr)
+        desc.pairs_host, desc.pairs_dev, desc.n_pairs = C.addressof(table), c["table_dev"].data_ptr(), count
+        desc.m, desc.n, desc.layout = self.m, self.n, self._layout
+        desc.out_h, desc.out_w = h, w
+        desc.scratch, desc.lq, desc.voxel = c["scratch"].data_ptr(), lq.data_ptr(), voxel.data_ptr()
+        ops.seq_assemble(desc, stages)
+        self._last = (desc, table)
+        cur = torch.cuda.current_stream(self.device)
+        for t in (self.frames, self.events):  # (uploaded on another stream: they stay valid until the kernels ran)
+            t.record_stream(cur)
+        return {"lq": lq, "voxel": voxel}
+
+
+class SequenceInterpolator:
+    """Runs ``net`` over the frame pairs of a sequence.  ``run`` uploads the sequence once, assembles minibatch k+1 on a
+    side stream while minibatch k runs, and turns every output into uint8 RGB frames of the original (H, W).  The
+    minibatch composition is part of the contract: pairs [0, max_minibatch), [max_minibatch, 2 max_minibatch), ... go
+    through ``net(x=lq, event=voxel)`` together, under ``eval()`` / ``no_grad()``."""
+
+    def __init__(self, net, m, n, layout="sharp", max_minibatch=2):
+        self.net = net
+        self.max_minibatch = int(max_minibatch)
+        if self.max_minibatch < 1:
+            raise RefidHipError(f"SequenceInterpolator: max_minibatch {max_minibatch} must be >= 1")
+        if not hasattr(net, "num_encoders"):
+            raise RefidHipError("SequenceInterpolator: the network has no num_encoders (the padding multiple is taken from it)")
+        self.device = next(net.parameters()).device
+        self.assembler = SequenceAssembler(m, n, layout, multiple=1 << int(net.num_encoders), device=self.device)
+        self.stream = torch.cuda.Stream(device=self.device)
+
+    def run(self, frames, events, pairs, out_dir=None, names=None, keep=False, bgr=False):
+        """``frames`` uint8 (N, H, W, 3), ``events`` float32 (E, 4), ``pairs`` from ``make_pairs``.  With ``out_dir`` frame f
+        of pair k goes to ``{out_dir}/{names[k]}_{f:02d}.png`` (default name: the left key frame's index, six digits, as
+        the validation dumps are named).  ``keep=True`` returns the uint8 frames (P, T, H, W, 3) on the host, else None."""
+        from .validation import FrameWriter
+        pairs = list(pairs)
+        if not pairs:
+            raise RefidHipError("SequenceInterpolator.run: no pairs")
+        if names is None:
+            names = [f"{p[0]:06d}" for p in pairs]
+        if len(names) != len(pairs):
+            raise RefidHipError(f"SequenceInterpolator.run: {len(names)} names for {len(pairs)} pairs")
+        asm, side = self.assembler, self.stream
+        cur = torch.cuda.current_stream(self.device)
+        asm.load(frames, events, bgr=bgr)
+        side.wait_stream(cur)                 # the upload was issued on the current stream
+        H, W = asm.height, asm.width
+        chunks = [pairs[i:i + self.max_minibatch] for i in range(0, len(pairs), self.max_minibatch)]
+
+        def preload(k):
+            if k >= len(chunks):
+                return None
+            with torch.cuda.stream(side):
+                return asm.assemble(chunks[k])
+
+        was_training = self.net.training
+        writer = FrameWriter(self.device) if out_dir is not None else None
+        kept = []
+        self.net.eval()
+        try:
+            with torch.no_grad():
+                nxt = preload(0)
+                for k, chunk in enumerate(chunks):
+                    cur.wait_stream(side)
+                    batch = nxt
+                    for v in batch.values():
+                        v.record_stream(cur)
+                    nxt = preload(k + 1)
+                    out = self.net(x=batch["lq"], event=batch["voxel"])
+                    u8 = metrics.val_tail(out[..., :H, :W], bgr=False).pred_u8       # (P, T, H, W, 3)
+                    t = u8.shape[1]
+                    if writer is not None:
+                        base = k * self.max_minibatch
+                        paths = [os.path.join(out_dir, f"{names[base + i]}_{f:02d}.png")
+                                 for i in range(len(chunk)) for f in range(t)]
+                        writer.dump([(u8.view(len(chunk) * t, H, W, 3), paths)])
+                    if keep:
+                        kept.append(u8)
+        finally:
+            self.net.train(was_training)
+            cur.wait_stream(side)
+            if writer is not None:
+                writer.close()
+        return torch.cat(kept, dim=0).cpu().numpy() if keep else None

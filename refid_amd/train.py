@@ -89,6 +89,8 @@ SCHEDULERS = ("TrueCosineAnnealingLR", "MultiStepLR", "MultiStepRestartLR", "Cos
 class TwoImageEventRecurrentRestorationModel:
     PIXEL_LOSSES = ("CharbonnierLoss",)            # the only one the reference's configs for this model use
     LOWLR_RATIO = 0.1                              # twoImage_event_recurrent_model.py:81 (`ratio`)
+    VAL_DATASET = "val"                            # the opt['datasets'] entry validation reads m and n from
+    TEST_ONLY = False                              # the Test* classes never build the training settings
 
     def __init__(self, opt):
         self.opt = opt
@@ -101,7 +103,7 @@ class TwoImageEventRecurrentRestorationModel:
                               opt["path"].get("param_key", "params"))
         self.rank, self.world = get_dist_info()
         self.log_dict = OrderedDict()
-        if self.is_train:
+        if self.is_train and not self.TEST_ONLY:
             self.init_training_settings()
 
     # ---- S3: optimiser / scheduler set-up -------------------------------------------------------
@@ -462,14 +464,12 @@ class TwoImageEventRecurrentRestorationModel:
         thing at its batch_size 1).  `rgb2bgr` is accepted and unused, as in the reference's loop."""
         from .validation import FrameWriter
         val = self.opt.get("val", {})
-        metrics.check_metric_options(val, use_image)
         dataset_name = self.opt.get("name")
         save_gt = val.get("save_gt", False)
-        self.m = self.opt["datasets"]["val"].get("num_end_interpolation")
-        self.n = self.opt["datasets"]["val"].get("num_inter_interpolation")
-        book = metrics.ValidationMetrics(val.get("metrics_deblur"), val.get("metrics_interpo"), self.m, self.n)
-        types = {o["type"] for o in list(book.opt_deblur.values()) + list(book.opt_interpo.values())} \
-            if book.with_metrics else set()
+        self.m = self.opt["datasets"][self.VAL_DATASET].get("num_end_interpolation")
+        self.n = self.opt["datasets"][self.VAL_DATASET].get("num_inter_interpolation")
+        book = self._val_book(val, use_image)
+        types = book.metric_types()
         was_training = self.net_g.training
         writer = FrameWriter(self.device) if save_img else None
         try:
@@ -503,16 +503,26 @@ class TwoImageEventRecurrentRestorationModel:
                 writer.close()
         current_metric = book.finish()
         if book.with_metrics:
-            self.metric_results_deblur, self.metric_results_interpo = book.deblur, book.interpo
-            self.metric_results_total = book.total
+            results = self._val_results(book)
             logger = logging.getLogger("basicsr")               # get_root_logger's name
             for line in book.log_lines(dataset_name):
                 logger.info(line)
             if tb_logger:
-                for res in (book.deblur, book.interpo):
+                for res in results:
                     for name, value in res.items():
                         tb_logger.add_scalar(f"metrics/{name}", value, current_iter)
         return current_metric
+
+    def _val_book(self, val, use_image):
+        """The bookkeeping of this class's validation loop: deblur / interpolation / total (:362-379, :460-512)."""
+        metrics.check_metric_options(val, use_image)
+        return metrics.ValidationMetrics(val.get("metrics_deblur"), val.get("metrics_interpo"), self.m, self.n)
+
+    def _val_results(self, book):
+        """Publishes the finished book as the reference's attributes; returns the dicts that go to tensorboard."""
+        self.metric_results_deblur, self.metric_results_interpo = book.deblur, book.interpo
+        self.metric_results_total = book.total
+        return book.deblur, book.interpo
 
     # ---- checkpoints (state-dict key names are a compatibility contract, SURVEY.md section 5) ------
     def save_network(self, net, net_label, current_iter, param_key="params"):
@@ -668,3 +678,60 @@ class ImageEventRestorationModel(TwoImageEventRecurrentRestorationModel):
                 i = j
             self.output = torch.cat(outs, dim=0)
         self.net_g.train()
+
+
+class TwoSharpImageEventRecurrentRestorationModel(TwoImageEventRecurrentRestorationModel):
+    """Sharp key frames (reference twoSharpImage_event_recurrent_model.py): the same network, step and validation loop;
+    ``feed_data`` requires ``seq`` and ``origin_index`` (:103-107), and the validation books keep ONE bucket -- every
+    output frame is an interpolation frame, the sums are divided by cnt * T, one ``[interpolation]`` line is logged
+    (:364-370, :478-502).  ``val.metrics_deblur`` is ignored, as in the reference."""
+
+    def feed_data(self, data):
+        super().feed_data(data)
+        self.seq_name = data["seq"][0]
+        self.origin_index = data["origin_index"][0]
+
+    def _val_book(self, val, use_image):
+        metrics.check_metric_options(val, use_image, groups=("metrics_interpo",))
+        return metrics.InterpolationMetrics(val.get("metrics_interpo"))
+
+    def _val_results(self, book):
+        self.metric_results_interpo = book.interpo
+        return (book.interpo,)
+
+
+class TestTwoImageEventRecurrentRestorationModel(TwoImageEventRecurrentRestorationModel):
+    """Test_twoImage_event_recurrent_model.py: m and n come from opt['datasets']['test'] (:260-261); no training settings."""
+    __test__ = False                               # (a model, not a pytest class)
+    VAL_DATASET = "test"
+    TEST_ONLY = True
+
+
+class Test_TwoSharpImageEventRecurrentRestorationModel(TwoSharpImageEventRecurrentRestorationModel):   # noqa: N801
+    """Test_twoSharpImage_event_recurrent_model.py: the sharp books, opt['datasets']['test'] (:359-360)."""
+    __test__ = False
+    VAL_DATASET = "test"
+    TEST_ONLY = True
+
+
+MODEL_CLASSES = {c.__name__: c for c in (TwoImageEventRecurrentRestorationModel, ImageEventRestorationModel,
+                                         TwoSharpImageEventRecurrentRestorationModel,
+                                         TestTwoImageEventRecurrentRestorationModel,
+                                         Test_TwoSharpImageEventRecurrentRestorationModel)}
+# the GoPro 7- and 15-skip test YAMLs spell the sharp test class without the underscore; the reference cannot resolve that
+MODEL_CLASSES["TestTwoSharpImageEventRecurrentRestorationModel"] = Test_TwoSharpImageEventRecurrentRestorationModel
+
+
+def model_class(model_type):
+    """opt['model_type'] -> class, as basicsr/models/__init__.py:28-36 resolves it (needs no GPU)."""
+    cls = MODEL_CLASSES.get(model_type)
+    if cls is None:
+        raise ValueError(f"Model {model_type} is not found.")
+    return cls
+
+
+def create_model(opt):
+    """basicsr/models/__init__.py:22-42."""
+    model = model_class(opt["model_type"])(opt)
+    logging.getLogger("basicsr").info(f"Model [{model.__class__.__name__}] is created.")
+    return model
