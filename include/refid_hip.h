@@ -234,10 +234,10 @@ typedef struct refid_wgrad_desc {
                                                    transforms (wgrad_wino24.hip; slabs [split][24][o][i]; pitches / channel
                                                    counts multiples of 4 floats, 16-byte aligned tensors, c_a % 32 == 0 for two
                                                    sources); deviation from the float64 gradient 3e-6 .. 6e-6 of scale;
-                                                   7 = conv_down (4x4 stride 2 pad 1, even input size): algo 5's kernel on the four
-                                                   parity phases of the input (a stride-2 conv is four 2x2-tap stride-1 convs on
-                                                   them): 12 instead of 16 fp32 MFMA-units per output pixel; slabs
-                                                   [split][phase][24][o][i];
+                                                   7 = conv_down (4x4 stride 2 pad 1, even input size): Winograd F(2,3) x F(2,4) tiles on the
+                                                   four parity phases of the input (a stride-2 conv is four 2x2-tap stride-1
+                                                   convs on them): 6.67 instead of 16 fp32 MFMA-units per output pixel; slabs
+                                                   [split][phase][20][o][i];
                                                    8 = the 2x2 stride-2 pad-0 weight gradient over NON-overlapping patches
                                                    (ConvTranspose2d(2,2) with the roles swapped, see above) as one streaming 1x1
                                                    weight gradient (wgrad_pws.hip): K = (dy, dx, c) over the even / odd rows of

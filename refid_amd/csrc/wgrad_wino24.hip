@@ -95,7 +95,7 @@ struct W24Args {
     int tilesX, tilesY, ntiles, nsplit;
     int CoP, CiP;
     int accum;
-    // DOWN form (conv_down, 4x4 stride 2 pad 1): H, W above are the PHASE image's size (= Ho, Wo), pad = 1
+    // wgrad_wino24_down_kernel only (conv_down, 4x4 stride 2 pad 1): H, W above are the PHASE image's size (= Ho, Wo)
     int Hin, Win, ncoT;
 };
 
@@ -163,25 +163,16 @@ struct W24Row {
     }
 };
 
-// DOWN = true: the weight gradient of conv_down (4x4, stride 2, pad 1; recurrent_sub_modules.py:12-14).  A stride-2 conv is four
-// stride-1 convs with 2x2 taps on the input's PARITY PHASES  P_pq[Y][X] = in[2Y + p][2X + q]:  tap ky reads phase p = (ky - 1) & 1
-// at row offset (ky - 1 - p) / 2, i.e. offsets {0, +1} for p = 0 and {-1, 0} for p = 1.  So per phase the wanted 2x2 taps are a
-// sub-block of the 3x3 correlation this kernel computes on (P_pq, dY) with pad 1 -- ky = 2u + p - 1 for u = 0..2 where that
-// lies in 0..3 --: 4 phases x 3 = 12 fp32 MFMA-units per output pixel instead of the direct form's 16.  The only differences:
-// the phase (grid z) selects the slab block, and the DMA gathers every other pixel of every other row (per-lane offsets, so it
-// costs nothing); the reduction scatters the 2x2 sub-blocks into the 4x4 gradient.
-// (Since wgrad_wino24_down_kernel -- F(2,3) x F(2,4), below -- this is the form behind REFID_W24_DOWN=0.)
-template <int NS, bool DOWN>
+template <int NS>
 __global__ __launch_bounds__(256, NS == 2 ? 2 : 3) void wgrad_wino24_kernel(const W24Args a) {
-    constexpr int OT = 32 * NS, BUF_BYTES = buf_bytes(NS), XPS = DOWN ? 2 : 1;     // XPS: input pixels per phase pixel
+    constexpr int OT = 32 * NS, BUF_BYTES = buf_bytes(NS);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 31, kh = lane >> 5;
-    const int phase = DOWN ? blockIdx.z / a.ncoT : 0, php = phase >> 1, phq = phase & 1;
-    const int co0 = (DOWN ? blockIdx.z % a.ncoT : blockIdx.z) * OT, ci0 = blockIdx.y * IT;
+    const int co0 = blockIdx.z * OT, ci0 = blockIdx.y * IT;
     const int split = blockIdx.x;
-    const int Hin = DOWN ? a.Hin : a.H, Win = DOWN ? a.Win : a.W;
+    const int Hin = a.H, Win = a.W;      // (for the address arithmetic; loaded here, their place in the prologue's schedule)
 
     // the input-channel tile lies in one source (host: c_a % 32 == 0 for two sources), so the descriptor is workgroup-uniform;
     // a tile beyond the sources (first recurrent step: no second source yet) keeps a valid descriptor, all lanes out of range
@@ -208,17 +199,17 @@ __global__ __launch_bounds__(256, NS == 2 ? 2 : 3) void wgrad_wino24_kernel(cons
     // an out-of-image ROW is a scalar select of an out-of-range base: one v_add per DMA instruction.  Otherwise out-of-range
     // columns / channels are forced out of range with OR masks.
     const int xq = ci0 + (lane & 7) * 4, xt = ci0 + (lane & 31), gq = co0 + (lane & 7) * 4;
-    const int xlc = ((lane >> 3) * XPS * xld + (xFromA ? xq : xq - a.Ca)) * 4;      // bytes from the piece's first pixel
-    const int xlt = ((lane >> 5) * XPS * xld + (xFromA ? xt : xt - a.Ca)) * 4;
+    const int xlc = ((lane >> 3) * xld + (xFromA ? xq : xq - a.Ca)) * 4;      // bytes from the piece's first pixel
+    const int xlt = ((lane >> 5) * xld + (xFromA ? xt : xt - a.Ca)) * 4;
     const int glc = ((lane >> 3) * a.ldG + gq) * 4;
     const bool fullch = ci0 + IT <= a.Ctot && co0 + OT <= a.Co;                     // workgroup-uniform
     constexpr int OOB = 0x7ff00000;                        // base of a dead row: + any lane constant (< 1 MB) stays out of range
     // Scalar state of the walk: the current time step's tensors (reloaded from the argument block only when the walk crosses
     // into the next step -- an s_load per request would put a full scalar-memory latency in front of every tile), the byte
     // offset of the next tile's first halo / gradient pixel (advanced by one tile width; recomputed at the end of a tile row)
-    const int xRowB = XPS * Win * xld * 4, gRowB = a.Wo * a.ldG * 4;      // bytes per (phase) image row
-    auto x_origin = [&](int n, int ty, int tx) {           // byte offset of phase pixel (ty GH - pad, tx GW - pad) of sample n
-        return ((n * Hin + XPS * (ty * GH - a.pad) + php) * Win + XPS * (tx * GW - a.pad) + phq) * xld * 4;
+    const int xRowB = Win * xld * 4, gRowB = a.Wo * a.ldG * 4;      // bytes per image row
+    auto x_origin = [&](int n, int ty, int tx) {           // byte offset of pixel (ty GH - pad, tx GW - pad) of sample n
+        return ((n * Hin + (ty * GH - a.pad)) * Win + (tx * GW - a.pad)) * xld * 4;
     };
     const float* gPtr = a.g[qg];
     const float* xPtr = xFromA ? a.inA[qg] : a.inB[qg];
@@ -231,7 +222,7 @@ __global__ __launch_bounds__(256, NS == 2 ? 2 : 3) void wgrad_wino24_kernel(cons
         const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xPtr), 0, limX, 0x00020000);
         char* xdst = smem + buf * BUF_BYTES;
         char* gdst = xdst + X_BYTES;
-        const bool fast = fullch && ix0 >= 0 && ix0 + XW <= a.W && ox0 + GW <= a.Wo && xld * 8 * XPS * 4 < 0x100000 && a.ldG * 8 * 4 < 0x100000;
+        const bool fast = fullch && ix0 >= 0 && ix0 + XW <= a.W && ox0 + GW <= a.Wo && xld * 8 * 4 < 0x100000 && a.ldG * 8 * 4 < 0x100000;
         // gradient (half, row) pairs q = 4 half + row of this wave: NS = 2: wave 0 q = 0, wave 1 q = 1, wave 2 q = 2..4, wave 3
         // q = 5..7 (with the halo rows: 8 / 8 / 9 / 9 DMA instructions); NS = 1: waves 2 / 3 two rows each (6 / 6 / 7 / 7)
         const int q0 = NS == 2 ? (wave < 2 ? wave : 3 * wave - 4) : 2 * (wave - 2), nq = NS == 2 ? (wave < 2 ? 1 : 3) : (wave < 2 ? 0 : 2);
@@ -243,8 +234,8 @@ __global__ __launch_bounds__(256, NS == 2 ? 2 : 3) void wgrad_wino24_kernel(cons
                     const int base = (unsigned)(iy0 + r) < (unsigned)a.H ? xTile + r * xRowB : OOB;
                     char* dst = xdst + r * (XW * IT * 4);
                     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_ptr24)dst, 16, base + xlc, 0, 0, 0);
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_ptr24)(dst + 1024), 16, base + 8 * XPS * xld * 4 + xlc, 0, 0, 0);
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_ptr24)(dst + 2048), 4, base + 16 * XPS * xld * 4 + xlt, 0, 0, 0);
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_ptr24)(dst + 1024), 16, base + 8 * xld * 4 + xlc, 0, 0, 0);
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_ptr24)(dst + 2048), 4, base + 16 * xld * 4 + xlt, 0, 0, 0);
                 }
             }
 #pragma unroll
@@ -275,9 +266,9 @@ __global__ __launch_bounds__(256, NS == 2 ? 2 : 3) void wgrad_wino24_kernel(cons
                     char* dst = xdst + r * (XW * IT * 4);
                     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_ptr24)dst, 16, (base + xlc) | xbadq | rbad | cx0, 0, 0, 0);
                     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_ptr24)(dst + 1024), 16,
-                                                             (base + 8 * XPS * xld * 4 + xlc) | xbadq | rbad | cx1, 0, 0, 0);
+                                                             (base + 8 * xld * 4 + xlc) | xbadq | rbad | cx1, 0, 0, 0);
                     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_ptr24)(dst + 2048), 4,
-                                                             (base + 16 * XPS * xld * 4 + xlt) | xbadt | rbad | cxt, 0, 0, 0);
+                                                             (base + 16 * xld * 4 + xlt) | xbadt | rbad | cxt, 0, 0, 0);
                 }
             }
 #pragma unroll
@@ -298,7 +289,7 @@ __global__ __launch_bounds__(256, NS == 2 ? 2 : 3) void wgrad_wino24_kernel(cons
         if (REFID_W24_ABLATE == 7) return;
         qx += 1;
         if (qx != a.tilesX) {
-            xTile += GW * XPS * xld * 4;
+            xTile += GW * xld * 4;
             gTile += GW * a.ldG * 4;
         } else {
             qx = 0;
@@ -412,8 +403,7 @@ __global__ __launch_bounds__(256, NS == 2 ? 2 : 3) void wgrad_wino24_kernel(cons
     // ---- slab: [split][xi][co][ci]; D[ci][co]: lane li = output channel, register quad = 4 ci ------
 #pragma unroll
     for (int j = 0; j < 6; ++j) {
-        // slab image of one split: [phase (DOWN: 4)][xi][co][ci]
-        float* sl = a.slabs + ((long long)((split * (DOWN ? 4 : 1) + phase) * NXI + wave * 6 + j) * a.CoP) * a.CiP;
+        float* sl = a.slabs + ((long long)(split * NXI + wave * 6 + j) * a.CoP) * a.CiP;
 #pragma unroll
         for (int sm = 0; sm < NS; ++sm) {
             const int co = co0 + sm * 32 + li;
@@ -429,7 +419,7 @@ __global__ __launch_bounds__(256, NS == 2 ? 2 : 3) void wgrad_wino24_kernel(cons
             }
         }
     }
-    if (a.bslabs != nullptr && blockIdx.y == 0 && phase == 0 && wave == 1) {
+    if (a.bslabs != nullptr && blockIdx.y == 0 && wave == 1) {
         // wave 1 holds the tile sums of the output channels: the two tile rows (kh) by one shuffle -- fixed order
 #pragma unroll
         for (int sm = 0; sm < NS; ++sm) {
@@ -466,18 +456,16 @@ __device__ __forceinline__ int w24_lane_again() {
     return l;
 }
 
-template <bool DOWN>
 __global__ __launch_bounds__(512, 1) void wgrad_wino24_pair_kernel(const W24Args a) {
-    constexpr int NS = 2, OT = 32 * NS, XPS = DOWN ? 2 : 1;
+    constexpr int NS = 2, OT = 32 * NS;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int row = wave & 3, hf = wave >> 2;              // F(3,2) row; which of the two input-channel tiles
     const int li = lane & 31, kh = lane >> 5;
-    const int phase = DOWN ? blockIdx.z / a.ncoT : 0, php = phase >> 1, phq = phase & 1;
-    const int co0 = (DOWN ? blockIdx.z % a.ncoT : blockIdx.z) * OT, ci0 = (2 * blockIdx.y + hf) * IT;
+    const int co0 = blockIdx.z * OT, ci0 = (2 * blockIdx.y + hf) * IT;
     const int split = blockIdx.x;
-    const int Hin = DOWN ? a.Hin : a.H, Win = DOWN ? a.Win : a.W;
+    const int Hin = a.H, Win = a.W;      // (for the address arithmetic; loaded here, their place in the prologue's schedule)
 
     // one X descriptor per half (wave-uniform): the halves may lie in different sources, or beyond them
     const bool xFromA = ci0 < a.Ca || ci0 >= a.Ctot;
@@ -497,14 +485,14 @@ __global__ __launch_bounds__(512, 1) void wgrad_wino24_pair_kernel(const W24Args
     }
     // ---- DMA roles: pieces, lane constants and the FAST / masked paths as in the four-wave kernel
     const int xq = ci0 + (lane & 7) * 4, xt = ci0 + (lane & 31), gq = co0 + (lane & 7) * 4;
-    const int xlc = ((lane >> 3) * XPS * xld + (xFromA ? xq : xq - a.Ca)) * 4;
-    const int xlt = ((lane >> 5) * XPS * xld + (xFromA ? xt : xt - a.Ca)) * 4;
+    const int xlc = ((lane >> 3) * xld + (xFromA ? xq : xq - a.Ca)) * 4;
+    const int xlt = ((lane >> 5) * xld + (xFromA ? xt : xt - a.Ca)) * 4;
     const int glc = ((lane >> 3) * a.ldG + gq) * 4;
     const bool fullch = ci0 + IT <= a.Ctot && co0 + OT <= a.Co;                     // wave-uniform
     constexpr int OOB = 0x7ff00000;
-    const int xRowB = XPS * Win * xld * 4, gRowB = a.Wo * a.ldG * 4;
+    const int xRowB = Win * xld * 4, gRowB = a.Wo * a.ldG * 4;
     auto x_origin = [&](int n, int ty, int tx) {
-        return ((n * Hin + XPS * (ty * GH - a.pad) + php) * Win + XPS * (tx * GW - a.pad) + phq) * xld * 4;
+        return ((n * Hin + (ty * GH - a.pad)) * Win + (tx * GW - a.pad)) * xld * 4;
     };
     const float* gPtr = a.g[qg];
     const float* xPtr = xFromA ? a.inA[qg] : a.inB[qg];
@@ -520,7 +508,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_wino24_pair_kernel(const W24Args
         const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xPtr), 0, limX, 0x00020000);
         char* xdst = smem + (hf * PAIR_STAGES + st) * X_BYTES;
         char* gdst = smem + PAIR_G0 + st * (2 * GS_BYTES) + hf * GS_BYTES;
-        const bool fast = fullch && ix0 >= 0 && ix0 + XW <= a.W && ox0 + GW <= a.Wo && xld * 8 * XPS * 4 < 0x100000 && a.ldG * 8 * 4 < 0x100000;
+        const bool fast = fullch && ix0 >= 0 && ix0 + XW <= a.W && ox0 + GW <= a.Wo && xld * 8 * 4 < 0x100000 && a.ldG * 8 * 4 < 0x100000;
         if (fast) {
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
@@ -529,8 +517,8 @@ __global__ __launch_bounds__(512, 1) void wgrad_wino24_pair_kernel(const W24Args
                     const int base = (unsigned)(iy0 + r) < (unsigned)a.H ? xTile + r * xRowB : OOB;
                     char* dst = xdst + r * (XW * IT * 4);
                     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_ptr24)dst, 16, base + xlc, 0, 0, 0);
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_ptr24)(dst + 1024), 16, base + 8 * XPS * xld * 4 + xlc, 0, 0, 0);
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_ptr24)(dst + 2048), 4, base + 16 * XPS * xld * 4 + xlt, 0, 0, 0);
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_ptr24)(dst + 1024), 16, base + 8 * xld * 4 + xlc, 0, 0, 0);
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_ptr24)(dst + 2048), 4, base + 16 * xld * 4 + xlt, 0, 0, 0);
                 }
             }
 #pragma unroll
@@ -560,9 +548,9 @@ __global__ __launch_bounds__(512, 1) void wgrad_wino24_pair_kernel(const W24Args
                     char* dst = xdst + r * (XW * IT * 4);
                     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_ptr24)dst, 16, (base + xlc) | xbadq | rbad | cx0, 0, 0, 0);
                     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_ptr24)(dst + 1024), 16,
-                                                             (base + 8 * XPS * xld * 4 + xlc) | xbadq | rbad | cx1, 0, 0, 0);
+                                                             (base + 8 * xld * 4 + xlc) | xbadq | rbad | cx1, 0, 0, 0);
                     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_ptr24)(dst + 2048), 4,
-                                                             (base + 16 * XPS * xld * 4 + xlt) | xbadt | rbad | cxt, 0, 0, 0);
+                                                             (base + 16 * xld * 4 + xlt) | xbadt | rbad | cxt, 0, 0, 0);
                 }
             }
 #pragma unroll
@@ -582,7 +570,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_wino24_pair_kernel(const W24Args
         if (REFID_W24_ABLATE == 7) return;
         qx += 1;
         if (qx != a.tilesX) {
-            xTile += GW * XPS * xld * 4;
+            xTile += GW * xld * 4;
             gTile += GW * a.ldG * 4;
         } else {
             qx = 0;
@@ -690,7 +678,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_wino24_pair_kernel(const W24Args
         if constexpr (I == 1) {
             // row 1 of the half that holds input tile 0 has the tile sums of the output channels: the two tile rows (kh) by
             // one shuffle -- fixed order
-            if (a.bslabs != nullptr && blockIdx.y == 0 && hf == 0 && phase == 0) {
+            if (a.bslabs != nullptr && blockIdx.y == 0 && hf == 0) {
                 const int le = w24_lane_again();
 #pragma unroll
                 for (int sm = 0; sm < NS; ++sm) {
@@ -715,7 +703,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_wino24_pair_kernel(const W24Args
     const int le = w24_lane_again(), lie = le & 31, khe = le >> 5;
 #pragma unroll
     for (int j = 0; j < 6; ++j) {
-        float* sl = a.slabs + ((long long)((split * (DOWN ? 4 : 1) + phase) * NXI + row * 6 + j) * a.CoP) * a.CiP;
+        float* sl = a.slabs + ((long long)(split * NXI + row * 6 + j) * a.CoP) * a.CiP;
 #pragma unroll
         for (int sm = 0; sm < NS; ++sm) {
             const int co = co0 + sm * 32 + lie;
@@ -733,11 +721,15 @@ __global__ __launch_bounds__(512, 1) void wgrad_wino24_pair_kernel(const W24Args
     }
 }
 
-// conv_down, F(2,3) x F(2,4) form (REFID_W24_DOWN, the default).  A parity phase needs only 2 taps per direction, so the
+// The weight gradient of conv_down (4x4, stride 2, pad 1; recurrent_sub_modules.py:12-14; refid_wgrad_desc.algo = 7), F(2,3) x
+// F(2,4) form.  A stride-2 conv is four stride-1 convs with 2x2 taps on the input's PARITY PHASES  P_pq[Y][X] = in[2Y + p][2X + q]:
+// tap ky reads phase p = (ky - 1) & 1 at row offset (ky - 1 - p) / 2, i.e. offsets {0, +1} for p = 0 (ky = 1, 3) and {-1, 0} for
+// p = 1 (ky = 0, 2); columns alike.  The phase (grid z) selects the slab block [split][phase][xi][co][ci], and the DMA gathers
+// every other pixel of every other row (per-lane offsets, so it costs nothing).  A phase needs only 2 taps per direction, so the
 // SAME four transform rows (By^T of F(2,3) is By^T of F(3,2): points 0, +-1, inf on a 4-row window) cover THREE gradient rows
 // instead of two, and five column points (0, +-1, 2, inf) cover 2 taps x FOUR gradient columns: per 3 x 4 gradient tile and
-// its 4 x 5 window 20 products per 12 pixels, 4 phases x 20 / 12 = 6.67 fp32 MFMA-units per output pixel instead of the
-// sub-block form's 12 -- and nothing computed is thrown away.
+// its 4 x 5 window 20 products per 12 pixels, 4 phases x 20 / 12 = 6.67 fp32 MFMA-units per output pixel instead of the direct
+// form's 16.  (An earlier form ran each phase as a 3x3 correlation on the stride-1 kernels above and kept its 2x2 sub-block: 12.)
 //     Gy rows {g0, g0+g1+g2, g0-g1+g2, g2}                        Ay^T = [1 1/2 1/2 0; 0 1/2 -1/2 1]  (By^T row 3 is d3 - d1)
 //     Gx rows {1,0,0,0} {1,1,1,1} {1,-1,1,-1} {1,2,4,8} {0,0,0,1}  Ax^T = [1 1 1 1 0; 0 1 -1 2 1] diag(1/2, -1/2, -1/6, 1/6, 1)
 //     Bx^T rows [2,-1,-2,1,0] [0,-2,-1,1,0] [0,2,-3,1,0] [0,-1,0,1,0] [0,2,-1,-2,1]
@@ -1060,7 +1052,7 @@ struct W24rArgs {
     const float* slabs; const float* bslabs; float* dw; float* db;
     int nsplit, Co, Ci, CoP, CiP, iBase, iTotal, perGroup;
     int nsplitW;                           // slabs behind `slabs` (= nsplit, or the folded count); bslabs always has nsplit rows
-    int down;                              // the conv_down form of the stage: 1 = 3x3 sub-blocks of 24 planes, 2 = F(2,3) x F(2,4)
+    int down;                              // 1: conv_down's stage (F(2,3) x F(2,4): four phases of 20 planes)
 };
 
 // First stage of the slab reduction.  Reading the slabs per (co, ci) element touches 64-256 contiguous bytes of each of 24 planes
@@ -1174,64 +1166,15 @@ __global__ __launch_bounds__(256) void wgrad_wino24_reduce_kernel(const W24rArgs
     w24_reduce_body(a, blockIdx.x, part);
 }
 
-// DOWN form: per (co, ci) the four phases' 24 planes -> four 3x3 blocks -> the 2x2 sub-block of each that exists in the 4x4
-// gradient (ky = 2u + p - 1, kx = 2v + q - 1), accumulated into OIHW (16 contiguous floats).  Reads the (folded) slab image
-// [split][phase][xi][co][ci]; one thread per element, slabs in order (deterministic).
+// conv_down: per (co, ci, phase) the 20 planes -> the phase's 2x2 taps dg = Ay^T dU Ax, scattered to ky = 2u + 1 - p,
+// kx = 2v + 1 - q (parity 0: taps 1, 3; parity 1: taps 0, 2), accumulated into OIHW (16 contiguous floats).  Reads the (folded)
+// slab image [split][phase][xi][co][ci]; one thread per (element, phase), slabs in order (deterministic).
 __device__ __forceinline__ void w24_reduce_down_body(const W24rArgs& a, const int blk) {
-    const long long plane = (long long)a.CoP * a.CiP;
-    const long long slabStride = 4 * NXI * plane;
-    const long long gid = (long long)blk * 256 + threadIdx.x;
-    const long long e = gid >> 2;                              // (co, ci), ci fastest; four threads = the four phases: every tap
-    const int ph = (int)(gid & 3);                             // of the 4x4 gradient belongs to exactly one of them
-    const bool live = e < (long long)a.Co * a.Ci;
-    const int ci = live ? (int)(e % a.Ci) : 0, co = live ? (int)(e / a.Ci) : 0;
-    if (live) {
-        const float* p = a.slabs + (long long)co * a.CiP + ci + ph * NXI * plane;
-        float u[NXI];
-#pragma unroll
-        for (int x = 0; x < NXI; ++x) u[x] = 0.f;
-        for (int k = 0; k < a.nsplitW; ++k) {
-#pragma unroll
-            for (int x = 0; x < NXI; ++x) u[x] += p[k * slabStride + x * plane];
-        }
-        constexpr float c4 = 0.25f, c6 = 1.f / 6.f, c12 = 1.f / 12.f, c24 = 1.f / 24.f;
-        float* dst = a.dw + ((long long)co * a.iTotal + a.iBase + ci) * 16;
-#pragma unroll
-        for (int pp = 0; pp < 3; ++pp) {
-            const int ky = 2 * pp + (ph >> 1) - 1;
-            float t[6];
-#pragma unroll
-            for (int j = 0; j < 6; ++j) {
-                const float m = 0.5f * (u[6 + j] + u[12 + j]), d = 0.5f * (u[6 + j] - u[12 + j]);
-                t[j] = pp == 0 ? u[j] + m : (pp == 1 ? d : m + u[18 + j]);
-            }
-            const float s12 = t[1] + t[2], d21 = t[2] - t[1], s34 = t[3] + t[4], d34 = t[3] - t[4];
-            const float r3[3] = {c4 * t[0] - c6 * s12 + c24 * s34, c6 * d21 + c12 * d34, c6 * (s34 - s12) + t[5]};
-            if (ky < 0 || ky > 3) continue;
-#pragma unroll
-            for (int q = 0; q < 3; ++q) {
-                const int kx = 2 * q + (ph & 1) - 1;
-                if (kx >= 0 && kx <= 3) dst[ky * 4 + kx] += r3[q];
-            }
-        }
-    }
-    if (a.db != nullptr && blk == 0) {
-        for (int c2 = threadIdx.x; c2 < a.Co; c2 += 256) {
-            float sacc = 0.f;
-            for (int k = 0; k < a.nsplit; ++k) sacc += a.bslabs[(long long)k * a.CoP + c2];
-            a.db[c2] += sacc;
-        }
-    }
-}
-
-// F(2,3) x F(2,4) form of conv_down: per (co, ci, phase) the 20 planes -> the phase's 2x2 taps dg = Ay^T dU Ax, scattered to
-// ky = 2u + 1 - p, kx = 2v + 1 - q (parity 0: taps 1, 3; parity 1: taps 0, 2).  Same thread mapping and slab order as above.
-__device__ __forceinline__ void w24_reduce_down23_body(const W24rArgs& a, const int blk) {
     const long long plane = (long long)a.CoP * a.CiP;
     const long long slabStride = 4 * NXD * plane;
     const long long gid = (long long)blk * 256 + threadIdx.x;
-    const long long e = gid >> 2;
-    const int ph = (int)(gid & 3);
+    const long long e = gid >> 2;                              // (co, ci), ci fastest; four threads = the four phases: every tap
+    const int ph = (int)(gid & 3);                             // of the 4x4 gradient belongs to exactly one of them
     const bool live = e < (long long)a.Co * a.Ci;
     const int ci = live ? (int)(e % a.Ci) : 0, co = live ? (int)(e / a.Ci) : 0;
     if (live) {
@@ -1271,8 +1214,7 @@ __device__ __forceinline__ void w24_reduce_down23_body(const W24rArgs& a, const 
 }
 
 __global__ __launch_bounds__(256) void wgrad_wino24_reduce_down_kernel(const W24rArgs a) {
-    if (a.down == 2) w24_reduce_down23_body(a, blockIdx.x);
-    else w24_reduce_down_body(a, blockIdx.x);
+    w24_reduce_down_body(a, blockIdx.x);
 }
 
 // every queued reduction of the family in ONE launch (refid_wgrad_desc.phase = 4 + refid_wgrad_finish_flush)
@@ -1283,8 +1225,7 @@ __global__ __launch_bounds__(256) void wgrad_wino24_reduce_batch_kernel(const W2
     int j = 0;
     for (int k = 1; k < b.n; ++k) j = (int)blockIdx.x >= b.blk0[k] ? k : j;       // (workgroup-uniform)
     const int blk = (int)blockIdx.x - b.blk0[j];
-    if (b.job[j].down == 2) w24_reduce_down23_body(b.job[j], blk);
-    else if (b.job[j].down) w24_reduce_down_body(b.job[j], blk);
+    if (b.job[j].down) w24_reduce_down_body(b.job[j], blk);
     else w24_reduce_body(b.job[j], blk, part);
 }
 
@@ -1294,25 +1235,16 @@ thread_local std::vector<W24rQueued> w24_queue;
 struct Geo24 { int ncoT, nciT, tilesX, tilesY, ntiles, nsplit, CoP, CiP; };
 
 int ns_of(const refid_wgrad_desc* d) { return d->c_o <= 32 ? 1 : 2; }      // 32-channel output tile for the thin layers
-bool is_down(const refid_wgrad_desc* d) { return d->kh == 4; }              // algo 7: conv_down through its parity phases
+bool is_down(const refid_wgrad_desc* d) { return d->kh == 4; }              // algo 7: conv_down (wgrad_wino24_down_kernel)
 
-// conv_down takes the F(2,3) x F(2,4) form (wgrad_wino24_down_kernel); REFID_W24_DOWN=0 keeps the 3x3 sub-block form of the
-// stride-1 kernels.  Read per call, like REFID_W24_PAIR: one process can alternate the forms (not between the launches and the
-// reduction of one set of slabs: the slab images differ).
-bool down_f23(const refid_wgrad_desc* d) {
-    if (!is_down(d)) return false;
-    const char* e = getenv("REFID_W24_DOWN");
-    return !e || atoi(e) != 0;
-}
-
-Geo24 geo24_of(const refid_wgrad_desc* d, bool f23) {
+Geo24 geo24_of(const refid_wgrad_desc* d) {
     Geo24 g;
     const int OT = 32 * ns_of(d);
     g.ncoT = cdiv(d->c_o, OT);
     const int ci_geo = (d->phase != 0) ? d->i_total - d->i_base : d->c_a + d->c_b;     // stable across steps
     g.nciT = cdiv(ci_geo > d->c_a + d->c_b ? ci_geo : d->c_a + d->c_b, IT);
     g.tilesX = cdiv(d->wo, GW);
-    g.tilesY = cdiv(d->ho, f23 ? DGH : GH);
+    g.tilesY = cdiv(d->ho, is_down(d) ? DGH : GH);
     g.ntiles = g.tilesX * g.tilesY * d->n;
     // two (NS = 1: three) workgroups per CU; a multiple of 8 splits keeps the workgroups of one K range on one XCD (grid x
     // is fastest)
@@ -1403,42 +1335,30 @@ int refid_wino24_finish_flush(hipStream_t st) {
 }
 
 namespace {
-long long slab_floats(const refid_wgrad_desc* d, const Geo24& g, bool f23) {
-    return (long long)(is_down(d) ? 4 : 1) * (f23 ? NXD : NXI) * g.CoP * g.CiP;
-}
-size_t workspace_bytes_of(const refid_wgrad_desc* d, bool f23) {
-    const Geo24 g = geo24_of(d, f23);
-    const long long slab = slab_floats(d, g, f23);
-    return ((size_t)g.nsplit * slab + (size_t)g.nsplit * g.CoP + (size_t)refid_slab_fold_count(slab, g.nsplit) * slab) * sizeof(float);
+long long slab_floats(const refid_wgrad_desc* d, const Geo24& g) {
+    return (long long)(is_down(d) ? 4 * NXD : NXI) * g.CoP * g.CiP;
 }
 }  // namespace
 
-// (conv_down: an upper bound for both of its forms -- a buffer sized once serves whichever form a later call takes)
 size_t refid_wgrad_wino24_workspace_bytes(const refid_wgrad_desc* d) {
-    const size_t w = workspace_bytes_of(d, false);
-    if (!is_down(d)) return w;
-    const size_t w23 = workspace_bytes_of(d, true);
-    return w23 > w ? w23 : w;
+    const Geo24 g = geo24_of(d);
+    const long long slab = slab_floats(d, g);
+    return ((size_t)g.nsplit * slab + (size_t)g.nsplit * g.CoP + (size_t)refid_slab_fold_count(slab, g.nsplit) * slab) * sizeof(float);
 }
 
 int refid_wgrad_wino24_launch(const refid_wgrad_desc* d, hipStream_t st) {
-    static std::atomic<unsigned long long> attr_done{0}, attr_done1{0}, attr_done2{0}, attr_done3{0};
-    if (int rc = refid_lds_attr_once(attr_done, &wgrad_wino24_kernel<2, false>, lds24_bytes(2), "wgrad_wino24")) return rc;
-    if (int rc = refid_lds_attr_once(attr_done1, &wgrad_wino24_kernel<1, false>, lds24_bytes(1), "wgrad_wino24<1>")) return rc;
-    if (int rc = refid_lds_attr_once(attr_done2, &wgrad_wino24_kernel<2, true>, lds24_bytes(2), "wgrad_wino24<down>")) return rc;
-    if (int rc = refid_lds_attr_once(attr_done3, &wgrad_wino24_kernel<1, true>, lds24_bytes(1), "wgrad_wino24<1, down>")) return rc;
-    static std::atomic<unsigned long long> attr_done4{0}, attr_done5{0};
-    if (int rc = refid_lds_attr_once(attr_done4, &wgrad_wino24_pair_kernel<false>, PAIR_LDS_BYTES, "wgrad_wino24<pair>")) return rc;
-    if (int rc = refid_lds_attr_once(attr_done5, &wgrad_wino24_pair_kernel<true>, PAIR_LDS_BYTES, "wgrad_wino24<pair, down>")) return rc;
-    static std::atomic<unsigned long long> attr_done6{0}, attr_done7{0};
-    if (int rc = refid_lds_attr_once(attr_done6, &wgrad_wino24_down_kernel<2>, down_lds_bytes(2), "wgrad_wino24_down")) return rc;
-    if (int rc = refid_lds_attr_once(attr_done7, &wgrad_wino24_down_kernel<1>, down_lds_bytes(1), "wgrad_wino24_down<1>")) return rc;
-    const bool down = is_down(d), f23 = down_f23(d);
-    const Geo24 g = geo24_of(d, f23);
-    const long long slab = slab_floats(d, g, f23);
+    static std::atomic<unsigned long long> attr_done{0}, attr_done1{0}, attr_done2{0}, attr_done3{0}, attr_done4{0};
+    if (int rc = refid_lds_attr_once(attr_done, &wgrad_wino24_kernel<2>, lds24_bytes(2), "wgrad_wino24")) return rc;
+    if (int rc = refid_lds_attr_once(attr_done1, &wgrad_wino24_kernel<1>, lds24_bytes(1), "wgrad_wino24<1>")) return rc;
+    if (int rc = refid_lds_attr_once(attr_done2, &wgrad_wino24_pair_kernel, PAIR_LDS_BYTES, "wgrad_wino24<pair>")) return rc;
+    if (int rc = refid_lds_attr_once(attr_done3, &wgrad_wino24_down_kernel<2>, down_lds_bytes(2), "wgrad_wino24_down")) return rc;
+    if (int rc = refid_lds_attr_once(attr_done4, &wgrad_wino24_down_kernel<1>, down_lds_bytes(1), "wgrad_wino24_down<1>")) return rc;
+    const bool down = is_down(d);
+    const Geo24 g = geo24_of(d);
+    const long long slab = slab_floats(d, g);
     const int pmode = pair_mode();
-    const bool pair = !f23 && pmode != 0 && pair_fits(d, g);     // (the F(2,3) x F(2,4) form has no pair layout)
-    REFID_CHECK(pair || pmode != 2 || f23, "wgrad (Winograd 2x4 tiles): REFID_W24_PAIR=2, but this launch takes the four-wave form "
+    const bool pair = !down && pmode != 0 && pair_fits(d, g);    // (conv_down's kernel has no pair layout)
+    REFID_CHECK(pair || pmode != 2 || down, "wgrad (Winograd 2x4 tiles): REFID_W24_PAIR=2, but this launch takes the four-wave form "
                                     "(c_o <= 32 or an odd number of input-channel tiles)");
     if (down)
         REFID_CHECK(d->kw == 4 && d->stride == 2 && d->pad == 1 && d->h % 2 == 0 && d->w % 2 == 0 && d->ho == d->h / 2 && d->wo == d->w / 2,
@@ -1473,30 +1393,22 @@ int refid_wgrad_wino24_launch(const refid_wgrad_desc* d, hipStream_t st) {
     a.bslabs = d->db ? d->slabs + (size_t)g.nsplit * slab : nullptr;
     a.N = d->n; a.H = d->h; a.W = d->w; a.Ho = d->ho; a.Wo = d->wo; a.pad = d->pad;
     a.Hin = d->h; a.Win = d->w; a.ncoT = g.ncoT;
-    if (down) { a.H = d->ho; a.W = d->wo; a.pad = 1; }      // the phase image
+    if (down) { a.H = d->ho; a.W = d->wo; }                 // the phase image
     a.tilesX = g.tilesX; a.tilesY = g.tilesY; a.ntiles = g.ntiles; a.nsplit = g.nsplit;
     a.CoP = g.CoP; a.CiP = g.CiP;
     a.accum = (d->phase == 2);
     if (d->phase != 3) {
-        if (f23) {
+        if (down) {
             if (ns_of(d) == 1)
                 hipLaunchKernelGGL((wgrad_wino24_down_kernel<1>), dim3(g.nsplit, g.nciT, 4 * g.ncoT), dim3(256), down_lds_bytes(1), st, a);
             else
                 hipLaunchKernelGGL((wgrad_wino24_down_kernel<2>), dim3(g.nsplit, g.nciT, 4 * g.ncoT), dim3(256), down_lds_bytes(2), st, a);
-        } else if (pair) {
-            if (down)
-                hipLaunchKernelGGL((wgrad_wino24_pair_kernel<true>), dim3(g.nsplit, g.nciT / 2, 4 * g.ncoT), dim3(512), PAIR_LDS_BYTES, st, a);
-            else
-                hipLaunchKernelGGL((wgrad_wino24_pair_kernel<false>), dim3(g.nsplit, g.nciT / 2, g.ncoT), dim3(512), PAIR_LDS_BYTES, st, a);
-        } else if (down) {
-            if (ns_of(d) == 1)
-                hipLaunchKernelGGL((wgrad_wino24_kernel<1, true>), dim3(g.nsplit, g.nciT, 4 * g.ncoT), dim3(256), lds24_bytes(1), st, a);
-            else
-                hipLaunchKernelGGL((wgrad_wino24_kernel<2, true>), dim3(g.nsplit, g.nciT, 4 * g.ncoT), dim3(256), lds24_bytes(2), st, a);
-        } else if (ns_of(d) == 1)
-            hipLaunchKernelGGL((wgrad_wino24_kernel<1, false>), dim3(g.nsplit, g.nciT, g.ncoT), dim3(256), lds24_bytes(1), st, a);
+        } else if (pair)
+            hipLaunchKernelGGL(wgrad_wino24_pair_kernel, dim3(g.nsplit, g.nciT / 2, g.ncoT), dim3(512), PAIR_LDS_BYTES, st, a);
+        else if (ns_of(d) == 1)
+            hipLaunchKernelGGL((wgrad_wino24_kernel<1>), dim3(g.nsplit, g.nciT, g.ncoT), dim3(256), lds24_bytes(1), st, a);
         else
-            hipLaunchKernelGGL((wgrad_wino24_kernel<2, false>), dim3(g.nsplit, g.nciT, g.ncoT), dim3(256), lds24_bytes(2), st, a);
+            hipLaunchKernelGGL((wgrad_wino24_kernel<2>), dim3(g.nsplit, g.nciT, g.ncoT), dim3(256), lds24_bytes(2), st, a);
         REFID_LAUNCH_CHECK("wgrad_wino24");
     }
     if (d->phase == 1 || d->phase == 2) return 0;          // reduction deferred (phase 3)
@@ -1518,7 +1430,7 @@ int refid_wgrad_wino24_launch(const refid_wgrad_desc* d, hipStream_t st) {
     while (lpe < 16 && (long long)lpe * 2 * total <= 65536 && lpe * 2 <= nred) lpe *= 2;
     r.perGroup = lpe;
     r.nsplitW = nred;
-    r.down = down ? (f23 ? 2 : 1) : 0;
+    r.down = down;
     if (refid_finish_defer_now()) {
         for (const W24rQueued& q : w24_queue)              // (two jobs on one gradient block would race: flush first)
             if (q.r.dw == r.dw && q.r.iBase == r.iBase) {

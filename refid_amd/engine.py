@@ -138,19 +138,16 @@ def _pad4(c):
 # forces the direct implicit-GEMM tile everywhere.
 USE_WINOGRAD = os.environ.get("REFID_WINOGRAD", "1") != "0"
 USE_POINTWISE = os.environ.get("REFID_POINTWISE", "1") != "0"     # register-operand tile for 1x1 convs
-# weight-gradient kernels on a side HIP stream (REFID_OVERLAP_WGRAD=0: everything on one stream)
-# Default since the end of round 5: OFF -- the weight gradients run on the main stream, in 8-step (large batches) or 24-step
-# (small batches) groups.  The side stream dates from rounds 1-2, when the dependent input-gradient chain left the chip idle
-# between its kernels; with today's kernels a B=8 step is 100 % busy on one stream, and the second compute stream only
-# costs: B=8 412.0-413.8 ms with it vs 406.1-406.9 without (three alternating runs on one box), B=1 108.9 vs 103.5 (there it
-# is also the sixth stream on four hardware queues).  REFID_OVERLAP_WGRAD=1 turns it back on (tests/test_hip_streams.py keeps
-# its write-after-read hazard check alive).
-_OVL_ENV = os.environ.get("REFID_OVERLAP_WGRAD", "0")
-OVERLAP_WGRAD = _OVL_ENV not in ("0", "auto")
-
-
-def overlap_wgrad():
-    return bool(OVERLAP_WGRAD)
+# The weight gradients run on the caller's stream.  Rounds 1-4 issued them on a side stream; off since round 5, where it
+# only cost, and removed since.  Switches of removed paths raise instead of being ignored.
+OVERLAP_WGRAD = False      # only bench.py's save / restore around its --full legs touches this name; nothing reads it
+for _var, _gone in (("REFID_OVERLAP_WGRAD", lambda v: v not in ("", "0", "auto")),
+                    ("REFID_WGRAD_BATCH", lambda v: True),
+                    ("REFID_W24_DOWN", lambda v: v == "0")):
+    _val = os.environ.get(_var)
+    if _val is not None and _gone(_val):
+        raise RefidHipError(f"{_var}={_val}: the path this switch selected was removed (DESIGN.md sections 5 and 7); "
+                            "unset it")
 # EGACA forward as 6 launches (LayerNorm prologues, squeeze-excite + scale inside conv3, GELU second output) instead of
 # 12; REFID_EGACA_FUSED=0: one kernel per reference op
 EGACA_FUSED = os.environ.get("REFID_EGACA_FUSED", "1") != "0"
@@ -160,9 +157,9 @@ EGACA_FUSED = os.environ.get("REFID_EGACA_FUSED", "1") != "0"
 # previous step; the bottleneck / decoders / pred of step t need step t's encoder outputs and their own states of the previous
 # step.  So level 0 (t+2), level 1 (t+1), level 2 (t) and the decoders (t-1) are independent kernel chains: each gets its own
 # stream, joined by one cross-stream dependency per level and step.  The ramp-up / tail of one chain's launches and the small
-# grids of the deep levels overlap the other chains (B=1: 124 -> 112 ms/step; B=8: < 1 %).  BPTT stays on one stream + the
-# weight-gradient side stream: the same wavefront over BPTT measured SLOWER (B=1 120 ms, B=8 544 ms: the weight-gradient
-# stream then has to wait for every chain).  REFID_PIPELINE=0: one chain; 1: always; default "auto": only while the batch
+# grids of the deep levels overlap the other chains (B=1: 124 -> 112 ms/step; B=8: < 1 %).  BPTT stays on one stream:
+# the same wavefront over BPTT measured SLOWER (B=1 120 ms, B=8 544 ms, round 4: the then weight-gradient side stream had
+# to wait for every chain).  REFID_PIPELINE=0: one chain; 1: always; default "auto": only while the batch
 # leaves the chip room (B H W <= PIPELINE_MAX_PIX: B <= 4 at 256 x 256).  Every stream beyond the device's four hardware
 # queues shares a queue with another one: with the three chain streams next to the weight-gradient stream, the input
 # prefetch stream and RCCL's stream, a B=8 step lost 2 % -- and 4.5 % (18 ms) with a process group up -- to copies and
@@ -204,7 +201,6 @@ LINEAR_SPLIT = os.environ.get("REFID_LINEAR_SPLIT", "1") != "0"
 class _SideStreams:
     def __init__(self):
         self._s = {}
-        self.pending = []                    # deferred weight-gradient launches: (op, g, a, b)
 
     def get(self, device):
         if device.type != "cuda":
@@ -214,21 +210,9 @@ class _SideStreams:
             s = self._s[device.index] = torch.cuda.Stream(device=device)
         return s
 
-    def join(self, device):
-        """Make the current stream wait for everything issued on the side stream."""
-        flush_wgrads(device)
-        s = self._s.get(device.index)
-        if s is not None:
-            torch.cuda.current_stream().wait_stream(s)
 
-
-WGRAD_STREAM = _SideStreams()
 DEC_STREAM = _SideStreams()                  # the decoder chain of the forward-sweep pipeline (PIPELINE)
 LV_STREAMS = (_SideStreams(), _SideStreams(), _SideStreams())   # EvR levels 1, 2 (and 3: num_encoders = 4); level 0 runs on the caller's stream
-WGRAD_BATCH = int(os.environ.get("REFID_WGRAD_BATCH", "8"))     # deferred launches per cross-stream dependency
-# The weight gradients of up to this many consecutive time steps of one conv are ONE launch (the weights are shared over
-# T: their partial-sum slabs -- 134-537 MB of read-modify-write per launch at B=8 -- are then touched once per group
-# instead of once per step; 3x3 and 4x4/stride-2 convs; 1 = off)
 # Winograd-domain GEMMs of the 3x3 convs with more than 32 output channels on the bf16 matrix cores, six exact-split
 # bf16 products per fp32 product (refid_conv2d algo 5, csrc/conv_wino6.hip): same error class as the fp32 Winograd tile at
 # 2.67x fewer matrix-pipe cycles.  0 = fp32 Winograd tile everywhere.
@@ -253,14 +237,12 @@ WINO6_THIN = os.environ.get("REFID_WINO6_THIN", "1") != "0"        # pred's forw
 DOWN_SPLIT = int(os.environ.get("REFID_DOWN_SPLIT", "6"))
 # smallest output-channel count whose 3x3 weight gradient goes to the Winograd tile (64 x 32 channel tiles)
 WGRAD_WINO_MIN_CO = int(os.environ.get("REFID_WGRAD_WINO_MIN_CO", "32"))
-# Time steps per weight-gradient launch (the ABI takes up to 24): all T steps of a sweep in ONE launch write the partial-sum slabs
-# once instead of read-modify-writing them per group.  Round 4 (weight gradients on a side stream): 8, because a later start of
-# the weight-gradient kernels cost more overlap than the slab passes saved (B=8 460.5 vs 458.3 ms at 24 vs 8).  Round 5: the
-# weight gradients run on the MAIN stream at every batch size, a launch is a link of the one chain, and 24 wins everywhere:
-# B=8 400.2 / 399.9 vs 404.9 / 403.5 ms (alternating, one box; 12 steps: 405.0 / 402.8), B=1 99.6 -> 98.0 ms.
+# Time steps per weight-gradient launch of one conv (3x3, 1x1 and 4x4/stride-2 convs; the ABI takes up to 24; 1 = off): the
+# weights are shared over T, so all T steps of a sweep in ONE launch write the partial-sum slabs (134-537 MB per launch at B=8)
+# once instead of read-modify-writing them per group.  It was 8 while the weight gradients had a side stream (round 4); on
+# the one stream 24 wins at every batch size.
 _WG_ENV = os.environ.get("REFID_WGRAD_GROUP")
-WGRAD_GROUP = max(1, min(24, int(_WG_ENV))) if _WG_ENV else (8 if OVERLAP_WGRAD else 24)
-WGRAD_GROUP_SMALL = max(1, min(24, int(_WG_ENV))) if _WG_ENV else 24
+WGRAD_GROUP = max(1, min(24, int(_WG_ENV))) if _WG_ENV else 24
 # What a waiting weight-gradient call keeps alive: the (gradient, input) tensors of its step, which BPTT would otherwise have
 # released -- measured 128 GB (all 23 steps per launch) against 90 GB (8 per launch) at B=8, 256 x 256: ~4.9 KB per pixel and
 # time step.  Engine._set_wgrad_groups shrinks the group when that would not fit into half of the HBM still free when BPTT
@@ -275,8 +257,8 @@ WGRAD_KEEP_BYTES_PER_PIXEL_STEP = 4900
 PWS_WGRAD = os.environ.get("REFID_PWS_WGRAD", "1") != "0"
 WGRAD_F4 = os.environ.get("REFID_WGRAD_F4", "1") != "0"
 WGRAD_F4_MIN_HW = int(os.environ.get("REFID_WGRAD_F4_MIN_HW", "16"))
-# conv_down's weight gradient (4x4 stride 2) on the same kernel through the input's four parity phases (algo 7: 12 instead of
-# 16 fp32 MFMA-units per output pixel).  REFID_WGRAD_DOWN_F4=0: the direct tile.
+# conv_down's weight gradient (4x4 stride 2) as Winograd F(2,3) x F(2,4) tiles on the input's four parity phases (algo 7: 6.67
+# instead of 16 fp32 MFMA-units per output pixel).  REFID_WGRAD_DOWN_F4=0: the direct tile.
 WGRAD_DOWN_F4 = os.environ.get("REFID_WGRAD_DOWN_F4", "1") != "0"
 
 
@@ -291,20 +273,6 @@ def wgrad_group_cap(n, pixels, device, free_bytes=None):
         free_bytes = torch.cuda.mem_get_info(device)[0] + (torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device))
     per_step = pixels * WGRAD_KEEP_BYTES_PER_PIXEL_STEP
     return max(1, min(n, int(free_bytes // 2 // per_step)))
-
-
-def flush_wgrads(device):
-    """Launch the deferred weight-gradient kernels on the side stream, after everything enqueued so far on the
-    current stream (their operands' producers)."""
-    pend = WGRAD_STREAM.pending
-    if not pend:
-        return
-    side = WGRAD_STREAM.get(device)
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        for op, g, a, b, bias, i_base in pend:
-            op._wgrad(g, a, b, bias, i_base)
-    pend.clear()
 
 
 FILL_MIN_WG = int(os.environ.get("REFID_FILL_MIN_WG", "256"))     # workgroups from which conv_down takes the split tile
@@ -735,21 +703,7 @@ class ConvOp:
         linearity split): one-shot launch straight into that column block of the gradient, no bias share.
 
         Weight gradients are off BPTT's critical path (only input gradients feed the next step): the calls of the T steps
-        wait in w_pend and go out as ONE launch per sweep on the main stream (_wgrad_issue / _launch_group); with
-        REFID_OVERLAP_WGRAD=1 they are issued on a side stream instead, as in rounds 1-4."""
-        side = WGRAD_STREAM.get(g.device) if overlap_wgrad() else None
-        if side is None:
-            return self._wgrad(g, a, b, bias, i_base)
-        for t in (g, a, b):
-            if t is not None:
-                t.record_stream(side)                       # allocator must not recycle them early
-        # deferred: the launch happens at the next flush_wgrads() -- ONE cross-stream dependency per batch instead
-        # of one event record + wait per weight-gradient call (~1500 per step; each left a ~7 us bubble)
-        WGRAD_STREAM.pending.append((self, g, a, b, bias, i_base))
-        if len(WGRAD_STREAM.pending) >= WGRAD_BATCH:
-            flush_wgrads(g.device)
-
-    def _wgrad(self, g, a, b=None, bias=True, i_base=0):
+        wait in w_pend and go out as ONE launch per sweep on the main stream (_wgrad_issue / _launch_group)."""
         if i_base:
             if self.kind != "conv" or b is not None or bias:
                 raise RefidHipError(f"{self.name}: a column-block weight gradient is one source, no bias, stride-1 conv")
@@ -778,7 +732,7 @@ class ConvOp:
         if self.kind == "down" and WGRAD_DOWN_F4 and USE_WINOGRAD and self.co >= 32 and self.ci >= 32 and a.shape[3] % 32 == 0 and \
                 (b is None or b.shape[3] % 32 == 0) and a.shape[1] % 2 == 0 and a.shape[2] % 2 == 0 and \
                 min(g.shape[1], g.shape[2]) >= WGRAD_F4_MIN_HW and g.shape[3] % 4 == 0:
-            algo = 7          # the 2x4-tile Winograd kernel on the four parity phases of the input
+            algo = 7          # Winograd F(2,3) x F(2,4) tiles on the four parity phases of the input
         if self.bf16 and self.kind == "conv" and self.k == 3 and self.co > 32 and self.ci > 32:
             algo = 2          # bf16 matrix-core operands, fp32 accumulation (compute_dtype: bf16)
         return self._wgrad_issue(g, a, b, bias, algo)
@@ -848,18 +802,8 @@ class ConvOp:
         """Reduce the accumulated slabs into the parameter gradient (once per step, after BPTT).  batched: the element-wise
         stage is only queued (phase 4); the caller ends its loop over the ops with ops.wgrad_finish_flush()
         (finish_wgrads below)."""
-        side = WGRAD_STREAM.get(self.w.device) if overlap_wgrad() else None
-        if side is not None:
-            flush_wgrads(self.w.device)                    # this op's launches may still be deferred
         if self.w_calls == 0 and not self.w_pend:
             return
-        if side is not None:
-            with torch.cuda.stream(side):
-                self._finish_wgrad()
-        else:
-            self._finish_wgrad(batched)
-
-    def _finish_wgrad(self, batched=False):
         if self.w_pend:
             self._launch_group()                           # the last, possibly shorter, group
         g, a, b, algo = self.w_last
@@ -873,7 +817,7 @@ def finish_wgrads(op_list):
     """finish_wgrad() of every op, with the ~130 small element-wise reduction stages of a step issued as one launch per
     kernel family (refid_wgrad_desc.phase 4 + refid_wgrad_finish_flush; REFID_FINISH_BATCH=0: one launch per op).  The ops'
     gradient tensors are distinct, so the queued stages are independent."""
-    batched = FINISH_BATCH and not overlap_wgrad()
+    batched = FINISH_BATCH
     try:
         for o in op_list:
             o.finish_wgrad(batched)
@@ -1033,11 +977,11 @@ class Engine:
         img_ops = {id(o) for e in self.img for o in e.values()} | {id(self.head_img), id(self.head_ev)}
         self.recurrent_ops = [o for o in self.all_ops if id(o) not in img_ops]
 
-    def _set_wgrad_groups(self, T, small=False, pixels=0):
+    def _set_wgrad_groups(self, T, pixels=0):
         """Group size of the deferred weight-gradient launches: min(WGRAD_GROUP, T) on the recurrent convs (a group
-        never outlives a sweep; small batches: WGRAD_GROUP_SMALL), 1 elsewhere; capped by the HBM that is still free
-        (`pixels` = B H W of the step: a waiting call keeps its step's tensors alive)."""
-        n = max(1, min(WGRAD_GROUP_SMALL if small else WGRAD_GROUP, T))
+        never outlives a sweep), 1 elsewhere; capped by the HBM that is still free (`pixels` = B H W of the step: a
+        waiting call keeps its step's tensors alive)."""
+        n = max(1, min(WGRAD_GROUP, T))
         n = wgrad_group_cap(n, pixels, self.device)
         for o in self.recurrent_ops:
             o.w_group = n
@@ -1471,15 +1415,14 @@ class Engine:
         c = self.ctx
         if c is None:
             raise RefidHipError("backward: no saved forward (call forward(save=True) first)")
-        WGRAD_STREAM.pending.clear()          # leftovers of a backward that raised must never be launched
-        for o in self.all_ops:                # ... nor may its half-filled slabs be added to (phase 2) or reduced
-            o.w_calls, o.w_last, o.w_pend = 0, None, []
+        for o in self.all_ops:                # leftovers of a backward that raised: its waiting calls must never be launched,
+            o.w_calls, o.w_last, o.w_pend = 0, None, []     # nor its half-filled slabs be added to (phase 2) or reduced
         self.fold_scratch.zero_()             # folded-weight gradients of THIS backward only (see ConvOp.__init__)
         self.ctx = None
         if ROWS_DEFER:
             ops.rows_sum_defer()              # per-channel gradient sums of this half: queued until finish_wgrads
         B, T, H, W = c["B"], c["T"], c["H"], c["W"]
-        self._set_wgrad_groups(T, use_pipeline(B, H, W), B * H * W)
+        self._set_wgrad_groups(T, B * H * W)
         dev = gout.device
         gout = gout.contiguous()
         xb, head, e_all, Sb = c["xb"], c["head"], c["e_all"], c["Sb"]
@@ -1575,13 +1518,12 @@ class Engine:
         # folded EGACA convs, un-folded now so the early bucket is complete
         self._egaca_img_bwd(self.enc_f[1].att, xb[0], g_xb[0], c["ip_f"])
         finish_wgrads(self.early_ops)
-        WGRAD_STREAM.join(dev)
         self._egaca_fold_back(self.enc_f[1].att)
-        return dict(c=c, B=B, dev=dev, g_xb=g_xb, g_Sb=g_Sb, g_e=g_e, g_head=g_head)
+        return dict(c=c, B=B, g_xb=g_xb, g_Sb=g_Sb, g_e=g_e, g_head=g_head)
 
     def backward_late(self, state):
         """Second half of BPTT: the backward sweep (walked t = 0 .. T-1), event head and image branch."""
-        c, B, dev, g_xb, g_Sb, g_e, g_head = (state[k] for k in ("c", "B", "dev", "g_xb", "g_Sb", "g_e", "g_head"))
+        c, B, g_xb, g_Sb, g_e, g_head = (state[k] for k in ("c", "B", "g_xb", "g_Sb", "g_e", "g_head"))
         xb, head, e_all = c["xb"], c["head"], c["e_all"]
         if ROWS_DEFER:
             ops.rows_sum_defer()
@@ -1629,7 +1571,6 @@ class Engine:
                 g = E["conv_1"].dgrad(g_c1, res=t1, mask=head, slope_mask=0.2)
         self.head_img.wgrad(g, c["x_in"])
         finish_wgrads(self.all_ops)
-        WGRAD_STREAM.join(dev)
         self._egaca_fold_back(self.enc_b[1].att)
 
     def _lin_level2_tail(self, L, gu, xb, g_xb, first):

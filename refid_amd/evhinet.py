@@ -16,7 +16,7 @@ import torch
 
 from . import ops
 from ._lib import RefidHipError
-from .engine import ConvOp, ParamArena, WGRAD_STREAM, _pad4, finish_wgrads
+from .engine import ConvOp, ParamArena, _pad4, finish_wgrads
 
 
 def param_shapes(in_chn=3, ev_chn=6, wf=64, depth=3, fac_place=2, hin_position_left=0, hin_position_right=4):
@@ -237,9 +237,8 @@ class EvhinetEngine:
         c = self.ctx
         if c is None:
             raise RefidHipError("backward: no saved forward (call forward(save=True) first)")
-        WGRAD_STREAM.pending.clear()          # leftovers of a backward that raised must never be launched
-        for o in self.all_ops:                # ... nor may its half-filled slabs be added to / reduced
-            o.w_calls, o.w_last, o.w_pend = 0, None, []
+        for o in self.all_ops:                # leftovers of a backward that raised: its waiting calls must never be launched,
+            o.w_calls, o.w_last, o.w_pend = 0, None, []     # nor its half-filled slabs be added to / reduced
         Bn, H, W = c["shape"]
         gout = gout.to(self.device, torch.float32).contiguous()
         g4 = ops.nchw_to_nhwc(gout, _pad4(self.in_chn))
@@ -276,7 +275,6 @@ class EvhinetEngine:
             g_e1 = self._block_bwd(Bk, g_out, c["ev"][i])
         self.conv_ev1.wgrad(g_e1, c["ev_in"])
         finish_wgrads(self.all_ops)
-        WGRAD_STREAM.join(self.device)
         if grad_sync is not None:
             grad_sync("early")
             grad_sync("late")

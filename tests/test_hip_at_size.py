@@ -59,11 +59,11 @@ def _per_tensor_err(eng, a, b):
 
 
 def test_config2_train_step_gradient_properties():
-    """B=8, 256x256, T=23 BPTT with the production settings (side-stream weight gradients, persistent slabs, split-K):
-    (1) stream overlap on == off; (2) Winograd split-K 'sample' == never, within 1e-5 of each tensor's scale;
+    """B=8, 256x256, T=23 BPTT with the production settings (persistent slabs, split-K):
+    (2) Winograd split-K 'sample' == never, within 1e-5 of each tensor's scale;
     (3) the gradient is linear in the samples: backward of a 2-sample batch == the two samples run one after the
     other into the same arena (which also exercises gradient accumulation at size)."""
-    from refid_amd import engine as E, ops
+    from refid_amd import ops
     P = _params(26, 11)
     net = _net(26, P)
     eng = net.engine
@@ -85,15 +85,6 @@ def test_config2_train_step_gradient_properties():
     assert bool(torch.isfinite(pred).all())
     base = eng.arena.flat_g.clone()
     assert bool(torch.isfinite(base).all()) and float(base.abs().max()) > 0
-    # (1) the weight gradients on the side stream (the default is the main stream since round 5) give the same gradients
-    old = E.OVERLAP_WGRAD
-    E.OVERLAP_WGRAD = not old
-    try:
-        run(x, ev, gt)
-    finally:
-        E.OVERLAP_WGRAD = old
-    e1, k1 = _per_tensor_err(eng, eng.arena.flat_g, base)
-    assert e1 <= 1e-5, (e1, k1)                      # only the atomically accumulated LN / depthwise sums may differ
     # (2) no split-K in the Winograd tile
     olds, ops.WINO_SPLIT = ops.WINO_SPLIT, 0
     try:

@@ -783,8 +783,8 @@ def test_convop_two_source_weight_gradient_any_split(ca, cb, group):
         x = rnd(N, ci, H, W, seed=10 + t)
         g = rnd(N, co, H, W, seed=20 + t)
         F.conv2d(x, w, bias, 1, 1).backward(g)
-        op._wgrad(nhwc(g), nhwc(x[:, :ca]), nhwc(x[:, ca:]))
-    op._finish_wgrad()
+        op.wgrad(nhwc(g), nhwc(x[:, :ca]), nhwc(x[:, ca:]))
+    op.finish_wgrad()
     torch.cuda.synchronize()
     np.testing.assert_allclose(A.g("c.weight").cpu().numpy(), w.grad.numpy(), rtol=1e-4, atol=1e-4)
     np.testing.assert_allclose(A.g("c.bias").cpu().numpy(), bias.grad.numpy(), rtol=1e-4, atol=1e-4)

@@ -726,7 +726,6 @@ def _egaca_hip(eng, ev, img, gout, fused):
     saved = {k: getattr(ops, k) for k in names}
     old, E.EGACA_FUSED = E.EGACA_FUSED, fused
     calls = []
-    E.WGRAD_STREAM.pending.clear()
     for o in eng.all_ops:
         o.w_calls, o.w_last, o.w_pend = 0, None, []
     eng.fold_scratch.zero_()
@@ -744,7 +743,6 @@ def _egaca_hip(eng, ev, img, gout, fused):
         g_ev = eng._egaca_bwd(A, gd, img_grad, ip, st)
         eng._egaca_img_bwd(A, imgd, img_grad, ip)
         E.finish_wgrads(A.ops())
-        E.WGRAD_STREAM.join(evd.device)
         eng._egaca_fold_back(A)
         torch.cuda.synchronize()
     finally:

@@ -1,6 +1,6 @@
 """conv_down's weight gradient in its F(2,3) x F(2,4) form (csrc/wgrad_wino24.hip: wgrad_wino24_down_kernel, 3 x 4 gradient
 tiles and a 4 x 5 window per parity phase, 20 transform planes) against a float64 per-tap GEMM on the CPU, and against the
-3x3 sub-block form it replaces (REFID_W24_DOWN=0).
+direct tile (algo 0).
 
 Exact data is family (g) of test_hip_wgrad_precision (integers times 2^s per channel, the gradient 1/128 dense): every product
 and partial sum of the K loop, the slabs and the fold is an integer below 2^24 units whatever its order, so the only rounding is
@@ -55,10 +55,10 @@ def gpu_step(g, x, Ca=None):
     return gf, xf[..., :Ca].contiguous(), xf[..., Ca:].contiguous()
 
 
-def one_shot(step, Co, Ci):
+def one_shot(step, Co, Ci, **geo):
     g, a, b = step
     dw = torch.zeros(Co, Ci, 4, 4, device="cuda"); db = torch.zeros(Co, device="cuda")
-    _ops().conv2d_wgrad(g, a, dw, in_b=b, db=db, i_total=Ci, **GEO)
+    _ops().conv2d_wgrad(g, a, dw, in_b=b, db=db, i_total=Ci, **{**GEO, **geo})
     torch.cuda.synchronize()
     return dw.double().cpu(), db.double().cpu()
 
@@ -79,25 +79,27 @@ def test_exact_data_every_tap(shape):
 
 
 @pytest.mark.parametrize("shape", SHAPES, ids=IDS)
-def test_random_data_against_the_sub_block_form(monkeypatch, shape):
-    """|new - old| < 3e-5 max|dW| (the bar test_hip_conv sets between algo 7 and the direct tile), db against sum g < 1e-5."""
+def test_random_data_against_the_direct_tile(shape):
+    """|F23 - direct| < 3e-5 max|dW| (the bar test_hip_conv::test_conv_down_wgrad_through_parity_phases sets between algo 7 and
+    the direct tile), db against sum g < 1e-5, and each side against float64 per tap, so a failure says which side moved."""
     N, Ho, Wo = shape
     gen = torch.Generator().manual_seed(11 + Ho)
     g = (torch.rand(N, Ho, Wo, 64, generator=gen) * 2 - 1).cuda()
     x = (torch.rand(N, 2 * Ho, 2 * Wo, 64, generator=gen) * 2 - 1).cuda()
     dw1, db1 = one_shot((g, x, None), 64, 64)
-    monkeypatch.setenv("REFID_W24_DOWN", "0")
-    dw0, db0 = one_shot((g, x, None), 64, 64)
-    monkeypatch.delenv("REFID_W24_DOWN")
+    dw0, db0 = one_shot((g, x, None), 64, 64, algo=0)
     d = float((dw1 - dw0).abs().max() / dw0.abs().max())
-    print(f"new vs old form at {shape}: {d:.3g} of max|dW|")
-    assert not torch.equal(dw1, dw0), "the switch selected the same form twice"
+    print(f"F(2,3) x F(2,4) vs direct tile at {shape}: {d:.3g} of max|dW|")
+    assert not torch.equal(dw1, dw0), "both calls took the same kernel"
     assert d < 3e-5
     dbr = g.double().cpu().sum((0, 1, 2))
     assert float((db1 - dbr).abs().max() / dbr.abs().max()) < 1e-5
     # and against float64 per tap
     dW, _, _, _ = ref_direct(g.double().cpu(), x.double().cpu(), 4, 2, 1)
-    assert float((dw1 - dW).abs().max() / dW.abs().max()) < 3e-5
+    d1, d0 = (float((dw - dW).abs().max() / dW.abs().max()) for dw in (dw1, dw0))
+    print(f"vs float64 at {shape}: F(2,3) x F(2,4) {d1:.3g}, direct tile {d0:.3g} of max|dW|")
+    assert d1 < 3e-5
+    assert d0 < 3e-5
 
 
 @pytest.mark.parametrize("Co,Ci", [(32, 64), (64, 32), (32, 32)], ids=["co32", "ci32", "co32_ci32"])
@@ -174,7 +176,7 @@ def test_short_k_ranges(monkeypatch, wgs):
 
 
 def test_pair_switch_has_no_effect(monkeypatch):
-    """REFID_W24_PAIR does not touch this form (=2 must not raise), and REFID_W24_DOWN=0 still routes through it."""
+    """REFID_W24_PAIR does not touch this form: =0 and =2 (which must not raise) give the default's bits."""
     N, Ho, Wo = SHAPES[1]
     steps, _ = exact_steps(N, Ho, Wo, 64, 64)
     gs = gpu_step(*steps[0])

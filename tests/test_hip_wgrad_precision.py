@@ -199,8 +199,9 @@ def split_plan(name, n, ho, wo):
         ncot, ncit = _cdiv(co, ot), _cdiv(ci, 32)
         want = _cdiv(512 * 3 // 2 if ot == 32 else 512, ncot * ncit * (4 if algo == 7 else 1))
         want = want // 8 * 8 if want >= 8 else want
-        ns = max(1, min(want, _cdiv(wo, 16) * _cdiv(ho, 4) * n))
-        cop, cip, ntaps = ncot * ot, ncit * 32, 24 * (4 if algo == 7 else 1)
+        # K tiles of 4 x 16 gradient pixels and 24 planes; conv_down (F(2,3) x F(2,4)): 6 x 16 pixels, four phases of 20 planes
+        ns = max(1, min(want, _cdiv(wo, 16) * _cdiv(ho, 6 if algo == 7 else 4) * n))
+        cop, cip, ntaps = ncot * ot, ncit * 32, (4 * 20 if algo == 7 else 24)
     else:
         if algo == 1:
             cot, cit, th, tw, ntaps, fold = 64, 32, 4, 32, 16, False
@@ -481,7 +482,7 @@ def test_split_plan_mirrors_the_workspace_request():
     assert odd >= 2, "no form at these sizes folds a split count that is not a multiple of the fold count"
 
 
-# ---- (2) the engine's issue path end to end: ConvOp._wgrad over T = 23 steps, engine.finish_wgrads ---------------------------
+# ---- (2) the engine's issue path end to end: ConvOp.wgrad over T = 23 steps, engine.finish_wgrads ---------------------------
 # name: (kind, weight shape, has bias, N, H, W of the gradient); "c3" runs two sources, a first step without the second source and a
 # mid-pass change of the source split (32 | 32 -> 40 | 24 -> 32 | 32: algo 5 -> 0 -> 5, ConvOp._slab_layout); "pwi" adds the
 # time-independent column block (i_base = 64) of a linearity split; "s00".."s41" queue 42 more phase-4 jobs than the rest,
@@ -563,7 +564,7 @@ def test_convop_issue_path_end_to_end(w_group):
 
 
 def _e2e_pass(oplist, refs, ops):
-    """One backward pass of E2E_OPS: T_E2E steps of every op through ConvOp._wgrad, float64 sums into refs[name]."""
+    """One backward pass of E2E_OPS: T_E2E steps of every op through ConvOp.wgrad, float64 sums into refs[name]."""
     for t in range(T_E2E):
         for j, (name, op) in enumerate(oplist.items()):
             kind, (o, i, k, _), _, N, H, W = E2E_OPS[name]
@@ -573,30 +574,30 @@ def _e2e_pass(oplist, refs, ops):
             if kind == "convT":
                 part = ref_direct(g, x, 2, 2, 0)
                 bias = (x.reshape(-1, i).sum(0),)
-                op._wgrad(x.float().cuda(), g.float().cuda())     # (output gradient, layer input): ConvOp swaps the roles
+                op.wgrad(x.float().cuda(), g.float().cuda())     # (output gradient, layer input): ConvOp swaps the roles
             else:
                 part = ref_direct(g, x, k, 2 if kind == "down" else 1, 1 if kind == "down" else k // 2)
                 bias = (part[2][:o],)
                 gg, xx = g.float().cuda(), x.float().cuda()
                 if name == "c3":
                     ca = 40 if 12 <= t < 18 else 32
-                    op._wgrad(gg, xx[..., :ca].contiguous(), None if t == 0 else xx[..., ca:].contiguous())
+                    op.wgrad(gg, xx[..., :ca].contiguous(), None if t == 0 else xx[..., ca:].contiguous())
                 elif name == "pw":                            # two sources; the first step has none yet
                     if t == 0:
                         x[..., 32:] = 0
                         part = ref_direct(g, x, 1, 1, 0)
-                    op._wgrad(gg, xx[..., :32].contiguous(), None if t == 0 else xx[..., 32:].contiguous())
+                    op.wgrad(gg, xx[..., :32].contiguous(), None if t == 0 else xx[..., 32:].contiguous())
                 elif name == "pwi":
                     part = ref_direct(g, x[..., :64], k, 1, 0)
-                    op._wgrad(gg, xx[..., :64].contiguous())
+                    op.wgrad(gg, xx[..., :64].contiguous())
                 else:
-                    op._wgrad(gg, xx)
+                    op.wgrad(gg, xx)
             sw = wino_scale(g, x, 5 if name == "c3" else 7) if name in ("c3", "down") else None
             new = [part[0][:o], bias[0], sw]
             refs[name] = new if name not in refs else [a + b if a is not None else None for a, b in zip(refs[name], new)]
     # the time-independent half of the linearity split: once per pass, straight into columns 64..95
     gsum, x32 = _e2e_step("pwi", 99, seed=5000)
-    oplist["pwi"]._wgrad(gsum.float().cuda(), x32[..., :32].float().cuda().contiguous(), None, bias=False, i_base=64)
+    oplist["pwi"].wgrad(gsum.float().cuda(), x32[..., :32].float().cuda().contiguous(), None, bias=False, i_base=64)
     refs["pwi"][0] = torch.cat([refs["pwi"][0], ref_direct(gsum, x32[..., :32], 1, 1, 0)[0]], 1)
 
 

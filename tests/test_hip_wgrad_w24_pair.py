@@ -138,7 +138,8 @@ def test_grouped_time_steps_and_accum(monkeypatch, phase4):
 
 
 def test_down_form(monkeypatch):
-    """conv_down (4x4, stride 2) through its parity phases on a 24 x 80 input: grid z carries the four phases."""
+    """conv_down (4x4, stride 2; a 24 x 80 input) has a kernel of its own with no pair layout: REFID_W24_PAIR=2 does not raise
+    for it, and =0 / =1 give the same bits, one-shot and phased."""
     N, H, W, Ca, Cb, Co = 1, 24, 80, 64, 0, 64
     steps = make_steps(2, N, H, W, Ca, Cb, Co, down=True)
     assert takes_pair(monkeypatch, steps, Ca, Cb, Co, down=True)

@@ -384,8 +384,8 @@ def test_every_shipped_yaml_of_the_reference_parses_and_builds(monkeypatch):
 
 def test_batched_finish_always_flushes_and_fallback_packs_stay_out_of_the_plan(monkeypatch):
     """Host logic of two round-5 changes, no GPU: (1) engine.finish_wgrads queues every op's element-wise reduction stage
-    (phase 4) and ALWAYS ends with refid_wgrad_finish_flush -- also when an op fails, so nothing stays queued in the library;
-    with the side-stream switch on it falls back to per-op launches.  (2) The fp32 Winograd packings of convs that run on their
+    (phase 4) and ALWAYS ends with refid_wgrad_finish_flush -- also when an op fails, so nothing stays queued in the library.
+    (2) The fp32 Winograd packings of convs that run on their
     Winograd x six planes are not in the per-step pack plan (packed on demand), everything else is."""
     from refid_amd import engine, ops
     calls = []
@@ -401,7 +401,6 @@ def test_batched_finish_always_flushes_and_fallback_packs_stay_out_of_the_plan(m
                 raise RuntimeError("boom")
 
     monkeypatch.setattr(engine, "FINISH_BATCH", True)
-    monkeypatch.setattr(engine, "OVERLAP_WGRAD", 0)
     engine.finish_wgrads([Op(), Op()])
     assert calls == [("finish", True), ("finish", True), "flush"]
     calls.clear()
@@ -501,7 +500,26 @@ def test_weight_gradient_group_is_capped_by_free_memory():
     assert engine.wgrad_group_cap(23, 4 * pix, "cpu", free_bytes=160 << 30) == 8       # four times the pixels: a third of the steps
     assert engine.wgrad_group_cap(1, pix, "cpu", free_bytes=0) == 1 and engine.wgrad_group_cap(23, 0, "cpu") == 23
     assert engine.wgrad_group_cap(23, pix, "cpu") == 23                                # (no CUDA device: unchanged)
-    assert engine.WGRAD_GROUP == (8 if engine.OVERLAP_WGRAD else 24)                   # derived from overlap_wgrad(), not the raw env string
+    assert engine.WGRAD_GROUP == 24                                                    # (REFID_WGRAD_GROUP unset)
+
+
+@pytest.mark.parametrize("var,val,raises", [("REFID_OVERLAP_WGRAD", "1", True), ("REFID_WGRAD_BATCH", "4", True),
+                                            ("REFID_W24_DOWN", "0", True), ("REFID_OVERLAP_WGRAD", "0", False),
+                                            ("REFID_W24_DOWN", "1", False)])
+def test_switches_of_removed_paths_raise_at_import(var, val, raises):
+    """The weight-gradient side stream (REFID_OVERLAP_WGRAD, REFID_WGRAD_BATCH) and conv_down's 3x3 sub-block weight gradient
+    (REFID_W24_DOWN=0) are gone: asking for one must fail loudly at `import refid_amd.engine`, naming the variable, instead of
+    silently running the default; the values that meant the default still import.  A fresh interpreter per case; no GPU."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("REFID_OVERLAP_WGRAD", "REFID_WGRAD_BATCH", "REFID_W24_DOWN")}
+    env[var] = val
+    r = subprocess.run([sys.executable, "-c", "import refid_amd.engine"], cwd=root, env=env, capture_output=True, text=True)
+    if raises:
+        assert r.returncode != 0 and "RefidHipError" in r.stderr and var in r.stderr and "removed" in r.stderr, r.stderr
+    else:
+        assert r.returncode == 0, r.stderr
 
 
 def test_streaming_weight_gradient_eligibility_mirrors_the_library():

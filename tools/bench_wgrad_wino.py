@@ -6,9 +6,8 @@ tile (algo 1, "regs") against the 2x4-tile form (algo 5, "f24").  Not bit-equal:
                                             side, ALTERNATING in one process (ROUNDS rounds per layer; median and min..max
                                             of each form, so a difference can be held against the spread of the same form);
                                             the conv_down shapes (algo 7) included; results compared bit for bit.
-  python tools/bench_wgrad_wino.py down     conv_down's 3x3 sub-block form and its F(2,3) x F(2,4) form (REFID_W24_DOWN=0 / 1)
-                                            at the three DOWN_SHAPES, alternating in one process in the same way; the largest
-                                            relative difference of the two gradients is printed (not bit-equal)."""
+  python tools/bench_wgrad_wino.py down     conv_down's weight gradient (algo 7, F(2,3) x F(2,4) tiles) at the three DOWN_SHAPES:
+                                            ROUNDS timings per layer, median and min..max."""
 import os
 import subprocess
 import sys
@@ -110,30 +109,19 @@ def run_down():
     from bench_kernels import timeit, B
     G, rounds = int(os.environ.get("GROUPS", 8)), int(os.environ.get("ROUNDS", 5))
     only = os.environ.get("ONLY_SHAPE")
-    print(f"# B={B} grouped steps={G} rounds={rounds}: us per launch, median (min..max); sub = 3x3 sub-block form, f23 = F(2,3)xF(2,4)")
+    print(f"# B={B} grouped steps={G} rounds={rounds}: us per launch, median (min..max)")
     for name, H, Ca, Co in (DOWN_SHAPES if only is None else [DOWN_SHAPES[int(only)]]):
         torch.manual_seed(1)
         steps = [(torch.randn(B, H // 2, H // 2, Co, device="cuda") * 0.01, torch.randn(B, H, H, Ca, device="cuda"), None)
                  for t in range(G)]
         g0, a0, b0 = steps[0]
         geo = dict(kh=4, kw=4, stride=2, pad=1, algo=7)
-        times, grads = {"0": [], "1": []}, {}
-        for r in range(rounds):
-            for mode in ("0", "1"):
-                os.environ["REFID_W24_DOWN"] = mode
-                dw = torch.zeros(Co, Ca, 4, 4, device="cuda"); db = torch.zeros(Co, device="cuda")
+        dw = torch.zeros(Co, Ca, 4, 4, device="cuda"); db = torch.zeros(Co, device="cuda")
 
-                def go():
-                    return ops.conv2d_wgrad(g0, a0, dw, in_b=b0, db=db, phase=1, more=steps[1:], **geo)
-                times[mode].append(timeit(go) * 1e6)
-                if r == 0:
-                    ops.conv2d_wgrad(g0, a0, dw, in_b=b0, db=db, phase=3, slabs=go(), **geo)
-                    grads[mode] = (dw.clone(), db.clone())
-        rel = float((grads["0"][0] - grads["1"][0]).abs().max() / grads["0"][0].abs().max())
-        m0, m1 = statistics.median(times["0"]), statistics.median(times["1"])
-        print(f"{name:26s} sub {m0:8.1f} ({min(times['0']):8.1f}..{max(times['0']):8.1f})  f23 {m1:8.1f} "
-              f"({min(times['1']):8.1f}..{max(times['1']):8.1f})  f23/sub {m1 / m0:5.3f}  rel diff dw {rel:.1e}", flush=True)
-    os.environ.pop("REFID_W24_DOWN", None)
+        def go():
+            return ops.conv2d_wgrad(g0, a0, dw, in_b=b0, db=db, phase=1, more=steps[1:], **geo)
+        times = [timeit(go) * 1e6 for r in range(rounds)]
+        print(f"{name:26s} {statistics.median(times):8.1f} ({min(times):8.1f}..{max(times):8.1f})", flush=True)
 
 
 if __name__ == "__main__":

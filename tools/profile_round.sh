@@ -21,16 +21,16 @@ import wino6_ablate as a, wgrad_wino_ablate as b
 a.check_fresh(a.lib_path(0)); b.check_fresh(b.lib_path(0))
 PY
 bash $R/tools/prof_step.sh ${tag}_bench_n1 --steps 3 --warmup 1 --full --no-cpu-baseline > /dev/null
-REFID_OVERLAP_WGRAD=0 REFID_PIPELINE=0 bash $R/tools/prof_step.sh ${tag}_bench_n1_nooverlap --steps 3 --warmup 1 --no-cpu-baseline --no-roofline > /dev/null
+REFID_PIPELINE=0 bash $R/tools/prof_step.sh ${tag}_bench_n1_nooverlap --steps 3 --warmup 1 --no-cpu-baseline --no-roofline > /dev/null
 [ "$LIGHT" = 2 ] || bash $R/tools/prof_step.sh ${tag}_b1 --batch 1 --steps 3 --warmup 1 --no-cpu-baseline --no-roofline > /dev/null
 for b in 1 2 4; do python $R/bench.py --batch $b --steps 8 --warmup 3 --no-cpu-baseline --no-roofline 2>/dev/null | tail -1 > "$OUT/${tag}_b${b}_bench_untraced.json"; done
-[ "$LIGHT" = 2 ] || REFID_OVERLAP_WGRAD=0 REFID_PIPELINE=0 bash $R/tools/prof_step.sh ${tag}_bf16_nooverlap --dtype bf16 --steps 3 --warmup 1 --no-cpu-baseline --no-roofline > /dev/null
+[ "$LIGHT" = 2 ] || REFID_PIPELINE=0 bash $R/tools/prof_step.sh ${tag}_bf16_nooverlap --dtype bf16 --steps 3 --warmup 1 --no-cpu-baseline --no-roofline > /dev/null
 cd /tmp
 PASSES="FETCH_SIZE WRITE_SIZE SQ_VALU_MFMA_BUSY_CYCLES,SQ_BUSY_CU_CYCLES,GRBM_GUI_ACTIVE SQ_LDS_BANK_CONFLICT,SQ_LDS_IDX_ACTIVE,SQ_INSTS_VALU,SQ_INSTS_LDS"
 i=0
 for c in $PASSES; do
   i=$((i+1)); rm -rf /tmp/pmc_$i
-  REFID_OVERLAP_WGRAD=0 REFID_PIPELINE=0 rocprofv3 --kernel-trace --pmc ${c//,/ } --output-format csv -d /tmp/pmc_$i -- python $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-roofline > /dev/null 2>&1
+  REFID_PIPELINE=0 rocprofv3 --kernel-trace --pmc ${c//,/ } --output-format csv -d /tmp/pmc_$i -- python $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-roofline > /dev/null 2>&1
 done
 f=$(find /tmp/pmc_1 -name "*counter_collection.csv" | head -1)
 w=$(find /tmp/pmc_2 -name "*counter_collection.csv" | head -1)
@@ -38,7 +38,7 @@ python $R/tools/pmc_traffic.py "$f" "$w" "$OUT/${tag}_pmc_traffic.json"
 # the same two passes for the bf16 mode (roofline.traffic of `bench.py --dtype bf16`)
 [ "$LIGHT" = 2 ] || for c in FETCH_SIZE WRITE_SIZE; do
   rm -rf /tmp/pmcb_$c
-  REFID_OVERLAP_WGRAD=0 REFID_PIPELINE=0 rocprofv3 --kernel-trace --pmc $c --output-format csv -d /tmp/pmcb_$c -- python $R/bench.py --dtype bf16 --steps 1 --warmup 0 --no-cpu-baseline --no-roofline > /dev/null 2>&1
+  REFID_PIPELINE=0 rocprofv3 --kernel-trace --pmc $c --output-format csv -d /tmp/pmcb_$c -- python $R/bench.py --dtype bf16 --steps 1 --warmup 0 --no-cpu-baseline --no-roofline > /dev/null 2>&1
 done
 [ "$LIGHT" = 2 ] || python $R/tools/pmc_traffic.py "$(find /tmp/pmcb_FETCH_SIZE -name '*counter_collection.csv' | head -1)" "$(find /tmp/pmcb_WRITE_SIZE -name '*counter_collection.csv' | head -1)" "$OUT/${tag}_pmc_traffic_bf16.json"
 cd $R
@@ -58,7 +58,7 @@ fi
 DTYPES="fp32 bf16x3 bf16"; [ "$LIGHT" = 2 ] && DTYPES="fp32"
 for d in $DTYPES; do python bench.py --dtype $d --steps 5 --warmup 2 --full 2>/dev/null | tail -1 > "$OUT/${tag}_bench_n1_$d.json"; done
 # GPU busy fraction without a tracer in the timed run: serial kernel time (traced durations) / untraced single-stream step
-REFID_OVERLAP_WGRAD=0 REFID_PIPELINE=0 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-roofline 2>/dev/null | tail -1 > "$OUT/${tag}_bench_n1_single_stream_untraced.json"
+REFID_PIPELINE=0 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-roofline 2>/dev/null | tail -1 > "$OUT/${tag}_bench_n1_single_stream_untraced.json"
 python tools/busy_report.py --stats "$OUT/${tag}_bench_n1_nooverlap_kernel_stats.csv" --stat-steps 4 \
   --single "$OUT/${tag}_bench_n1_single_stream_untraced.json" --default "$OUT/${tag}_bench_n1_fp32.json" > "$OUT/${tag}_gpu_busy.txt" 2>&1
 # the driver's command line

@@ -10,7 +10,6 @@ from refid_amd.train import TwoImageEventRecurrentRestorationModel
 class A: pass
 a = A(); a.img_chn = 26; a.batch = int(os.environ.get("B", 8)); a.T = int(os.environ.get("T", 23)); a.size = 256; a.dtype = os.environ.get("DTYPE", "fp32")
 from refid_amd import engine
-engine.OVERLAP_WGRAD = False          # kernels run alone: per-kernel times mean something
 engine.PIPELINE = False               # (forward wavefront over four streams off as well)
 model = TwoImageEventRecurrentRestorationModel(bench.options(a))
 x, ev, gt = bench.synthetic_batch(a.batch, a.T, a.size, a.size, 26, 1, torch.device("cuda"))
