@@ -15,9 +15,6 @@
 // slabs [split][tap][o][i] with plain coalesced stores (no atomics, deterministic); a
 // second kernel reduces the slabs and ACCUMULATES into the parameter-layout gradient,
 // because weights are shared over the T recurrent steps.
-#include "common.h"
-#include <vector>
-#include <cstring>
 #include "wgrad_args.h"
 #include <cstdlib>
 
@@ -726,27 +723,15 @@ __global__ __launch_bounds__(256) void wgrad_reduce_batch_kernel(const RedBatch 
     wgrad_reduce_body(b.job[j], (int)blockIdx.x - b.blk0[j]);
 }
 
-struct RedQueued { RedArgs r; int nblocks; };
-thread_local std::vector<RedQueued> red_queue;
-thread_local bool defer_now = false;
+thread_local WgFinishQueue<RedArgs, RedBatch> red_queue;
 
 int red_flush(hipStream_t st) {
-    size_t at = 0;
-    while (at < red_queue.size()) {
-        RedBatch b;
-        memset(&b, 0, sizeof(b));
-        int n = 0, blk = 0;
-        for (; n < REFID_FINISH_BATCH && at < red_queue.size(); ++n, ++at) {
-            b.job[n] = red_queue[at].r;
-            b.blk0[n] = blk;
-            blk += red_queue[at].nblocks;
-        }
-        b.blk0[n] = blk; b.n = n;
+    return red_queue.flush([&](const RedBatch& b, int blk) {
         hipLaunchKernelGGL(wgrad_reduce_batch_kernel, dim3(blk), dim3(256), 0, st, b);
-        if (hipGetLastError() != hipSuccess) { red_queue.clear(); refid_set_error("wgrad_reduce_batch: launch failed"); return 1; }
-    }
-    red_queue.clear();
-    return 0;
+        if (hipGetLastError() == hipSuccess) return true;
+        refid_set_error("wgrad_reduce_batch: launch failed");
+        return false;
+    });
 }
 
 // <KH,KW,S, TPW, SM,SN, WR,WC,WT, TH,TW>
@@ -791,27 +776,13 @@ Plan plan_of(int kh, int kw, int s, int co, int ci) {
     return {P_NONE, 0, 0, 0, 0, 0, false};
 }
 
-struct Geo { int ncoT, nciT, tilesX, tilesY, ntiles, nsplit, CoP, CiP; };
-
-Geo geo_of(const refid_wgrad_desc* d, const Plan& p) {
-    Geo g;
-    g.ncoT = cdiv(d->c_o, p.cot);
-    const int ci_geo = (d->phase != 0) ? d->i_total - d->i_base : d->c_a + d->c_b;   // stable across steps
-    g.nciT = cdiv(ci_geo > d->c_a + d->c_b ? ci_geo : d->c_a + d->c_b, p.cit);
-    g.tilesX = cdiv(d->wo, p.tw);
-    g.tilesY = cdiv(d->ho, p.th);
-    g.ntiles = g.tilesX * g.tilesY * d->n;
-    int want = cdiv(512, g.ncoT * g.nciT);           // 2 resident workgroups per CU on 256 CUs, one round
-    if (want < 1) want = 1;
-    if (want > g.ntiles) want = g.ntiles;
-    g.nsplit = want;
-    g.CoP = g.ncoT * p.cot;
-    g.CiP = g.nciT * p.cit;
-    return g;
+// 2 resident workgroups per CU on 256 CUs, one round; the streaming 1x1 form (wgrad_pws.hip) has its own slab geometry
+WgSplit geo_of(const refid_wgrad_desc* d, const Plan& p) {
+    return refid_wgrad_pws_ok(d) ? refid_wgrad_pws_geo(d) : refid_wgrad_split(d, p.cot, p.cit, p.th, p.tw, 512, false);
 }
 
 template <class C>
-int launch_w(const WgKArgs& a, const Geo& g, hipStream_t st) {
+int launch_w(const WgKArgs& a, const WgSplit& g, hipStream_t st) {
     static std::atomic<unsigned long long> attr_done{0};
     if (int rc = refid_lds_attr_once(attr_done, &wgrad_kernel<C>, C::LDS_BYTES, "wgrad")) return rc;
     dim3 grid(g.nsplit, g.nciT, g.ncoT);
@@ -821,13 +792,6 @@ int launch_w(const WgKArgs& a, const Geo& g, hipStream_t st) {
 }
 
 }  // namespace
-
-// wgrad_wino.hip
-size_t refid_wgrad_wino_workspace_bytes(const refid_wgrad_desc* d);
-int refid_wgrad_wino_launch(const refid_wgrad_desc* d, hipStream_t st);
-// wgrad_wino24.hip: Winograd over 2x4 tiles, F(3,2) x F(3,4) (algo 5)
-size_t refid_wgrad_wino24_workspace_bytes(const refid_wgrad_desc* d);
-int refid_wgrad_wino24_launch(const refid_wgrad_desc* d, hipStream_t st);
 
 // algo 8: the weight gradient of a 2x2 stride-2 conv over NON-overlapping patches (ConvTranspose2d(2,2) with the roles swapped,
 // refid_hip.h) as ONE streaming 1x1 weight gradient: an output pixel's patch is two contiguous runs of 2 c_a floats (rows 2y and
@@ -848,7 +812,7 @@ static bool patch_translate(const refid_wgrad_desc* d, refid_wgrad_desc* t, int*
     for (int k = 0; k + 1 < REFID_WGRAD_MAX_GROUPS; ++k)
         t->in_b_more[k] = d->in_a_more[k] ? d->in_a_more[k] + (long long)d->w * d->ld_a : nullptr;
     *patchW = d->wo; *patchRow = 2 * d->w * d->ld_a;
-    if (!refid_wgrad_pws_ok(t) || (long long)d->n * d->h * d->w * d->ld_a * 4 >= 0x7fffffffLL) return false;
+    if (!refid_wgrad_pws_ok(t) || !refid_wgrad_offsets_fit(d)) return false;
     // a patch row must fill whole ring buffers (the launch checks the same: the workspace query and the launch agree)
     const int pb = refid_wgrad_pws_pixels_per_buffer(t);
     return pb > 0 && *patchW % pb == 0;
@@ -868,28 +832,22 @@ extern "C" size_t refid_wgrad_workspace_bytes(const refid_wgrad_desc* d) {
     if (thin_ok(d)) return (size_t)thin_nsplit(d) * 4 * (WT_MAXG * 1024 + 32) * sizeof(float);
     const Plan p = plan_of(d->kh, d->kw, d->stride, d->c_o, d->phase != 0 ? d->i_total - d->i_base : d->c_a + d->c_b);
     if (!p.ok) return 0;
-    Geo g = geo_of(d, p);
-    if (refid_wgrad_pws_ok(d)) refid_wgrad_pws_geo(d, &g.ncoT, &g.nciT, &g.nsplit, &g.CoP, &g.CiP);
+    const WgSplit g = geo_of(d, p);
     const size_t slab = (size_t)p.ntaps * g.CoP * g.CiP;
     return ((size_t)g.nsplit * slab + (size_t)g.nsplit * g.CoP + (size_t)refid_slab_fold_count((long long)slab, g.nsplit) * slab) * sizeof(float);
 }
 
-bool refid_finish_defer_now() { return defer_now; }
-
-static int conv2d_wgrad_impl(const refid_wgrad_desc* d, hipStream_t st);
+static int conv2d_wgrad_impl(const refid_wgrad_desc* d, hipStream_t st, bool defer);
 
 extern "C" int refid_conv2d_wgrad(const refid_wgrad_desc* d, void* stream) {
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     REFID_CHECK(d != nullptr, "wgrad: null descriptor");
-    if (d->phase != 4) return conv2d_wgrad_impl(d, st);
+    if (d->phase != 4) return conv2d_wgrad_impl(d, st, false);
     // phase 4 = phase 3 with the element-wise stage queued for refid_wgrad_finish_flush (the families that have no batched
     // form -- algo 1's tile, the thin-input tile -- run theirs at once)
     refid_wgrad_desc dd = *d;
     dd.phase = 3;
-    defer_now = true;
-    const int rc = conv2d_wgrad_impl(&dd, st);
-    defer_now = false;
-    return rc;
+    return conv2d_wgrad_impl(&dd, st, true);
 }
 
 extern "C" int refid_wgrad_finish_flush(void* stream) {
@@ -900,7 +858,7 @@ extern "C" int refid_wgrad_finish_flush(void* stream) {
     return rc0 ? rc0 : (rc ? rc : rc2);
 }
 
-static int conv2d_wgrad_impl(const refid_wgrad_desc* d, hipStream_t st) {
+static int conv2d_wgrad_impl(const refid_wgrad_desc* d, hipStream_t st, bool defer) {
     refid_wgrad_desc tt;
     int patchW = 0, patchRow = 0, permCo = 0;
     if (d->algo == 8) {
@@ -927,14 +885,13 @@ static int conv2d_wgrad_impl(const refid_wgrad_desc* d, hipStream_t st) {
     REFID_CHECK(d->algo == 0 || ((d->algo >= 1 && d->algo <= 6) && d->kh == 3 && d->kw == 3 && d->stride == 1) ||
                     (d->algo == 7 && d->kh == 4 && d->kw == 4 && d->stride == 2 && d->pad == 1),
                 "wgrad: algo %d needs a 3x3 stride-1 conv (algo 7: a 4x4 stride-2 pad-1 conv)", d->algo);
-    REFID_CHECK(d->groups <= REFID_WGRAD_MAX_GROUPS, "wgrad: at most %d grouped time steps", REFID_WGRAD_MAX_GROUPS);
     const bool pws = refid_wgrad_pws_ok(d);               // streaming 1x1 form (wgrad_pws.hip): its own slab geometry
     REFID_CHECK(d->groups <= 1 || (d->phase != 3 && !thin_ok(d) && (d->algo != 0 || p.id != P_PW || pws)),
                 "wgrad: grouped time steps are not implemented by the thin-input and 1x1 register tiles (and mean nothing in phase 3)");
     REFID_CHECK(d->algo != 2 || (p.id == P_W3 && d->pad == 1),
                 "wgrad: algo 2 (bf16 operands) needs more than 32 output and input channels and pad 1");
     if (d->algo == 1 || d->algo == 3 || d->algo == 4) return refid_wgrad_wino_launch(d, st);
-    if (d->algo == 5 || d->algo == 7) return refid_wgrad_wino24_launch(d, st);
+    if (d->algo == 5 || d->algo == 7) return refid_wgrad_wino24_launch(d, st, defer);
     REFID_CHECK(d->algo != 6, "wgrad: algo 6 (Winograd F(3x3,4x4)) was an experiment that did not beat algo 5 (round 5, "
                               "DESIGN.md section 7); it is no longer built");
     if (thin_ok(d)) {
@@ -958,27 +915,10 @@ static int conv2d_wgrad_impl(const refid_wgrad_desc* d, hipStream_t st) {
         REFID_LAUNCH_CHECK("wgrad_thin_reduce");
         return 0;
     }
-    Geo g = geo_of(d, p);
-    if (pws) refid_wgrad_pws_geo(d, &g.ncoT, &g.nciT, &g.nsplit, &g.CoP, &g.CiP);
+    const WgSplit g = geo_of(d, p);
+    const long long slab = (long long)p.ntaps * g.CoP * g.CiP;
     WgKArgs a;
-    const int ngrp = d->groups > 1 ? d->groups : 1;
-    for (int k = 0; k < REFID_WGRAD_MAX_GROUPS; ++k) {
-        const bool on = k > 0 && k < ngrp;
-        a.g[k] = on ? d->g_more[k - 1] : d->g;
-        a.inA[k] = on ? d->in_a_more[k - 1] : d->in_a;
-        a.inB[k] = on ? d->in_b_more[k - 1] : d->in_b;
-        REFID_CHECK(a.g[k] && a.inA[k] && (d->c_b == 0 || a.inB[k]), "wgrad: null tensor pointer in group %d", k);
-    }
-    a.groups = ngrp;
-    a.ldG = d->ld_g; a.Co = d->c_o;
-    a.ldA = d->ld_a; a.ldB = d->ld_b;
-    a.Ca = d->c_a; a.Ctot = d->c_a + d->c_b;
-    a.slabs = d->slabs;
-    a.bslabs = d->db ? d->slabs + (size_t)g.nsplit * p.ntaps * g.CoP * g.CiP : nullptr;
-    a.N = d->n; a.H = d->h; a.W = d->w; a.Ho = d->ho; a.Wo = d->wo; a.pad = d->pad;
-    a.tilesX = g.tilesX; a.tilesY = g.tilesY; a.ntiles = g.ntiles; a.nsplit = g.nsplit;
-    a.CoP = g.CoP; a.CiP = g.CiP;
-    a.accum = (d->phase == 2);
+    if (int rc = refid_wgrad_fill(a, d, g, slab, pws && d->phase != 3, "1x1 streaming")) return rc;
     a.patchW = patchW; a.patchRow = patchRow;
     REFID_CHECK(!patchW || pws, "wgrad (algo 8): the streaming 1x1 form is switched off (REFID_PWS_WGRAD)");
     REFID_CHECK(d->phase >= 0 && d->phase <= 3, "wgrad: bad phase %d", d->phase);
@@ -988,9 +928,7 @@ static int conv2d_wgrad_impl(const refid_wgrad_desc* d, hipStream_t st) {
     } else if (d->phase != 3 && p.id == P_PW) {
         const long long npix = (long long)d->n * d->h * d->w;
         REFID_CHECK(d->c_b == 0 || d->c_a % 32 == 0, "wgrad: pointwise tile needs c_a %% 32 == 0 for two sources");
-        REFID_CHECK(npix * d->ld_g * 4 < 0x7fffffffLL && npix * d->ld_a * 4 < 0x7fffffffLL &&
-                        (d->c_b == 0 || npix * d->ld_b * 4 < 0x7fffffffLL),
-                    "wgrad: tensor too large for the pointwise tile's 32-bit offsets");
+        REFID_CHECK(refid_wgrad_offsets_fit(d), "wgrad: tensor too large for the pointwise tile's 32-bit offsets");
         WpArgs w;
         w.g = d->g; w.ldG = d->ld_g; w.Co = d->c_o;
         w.inA = d->in_a; w.inB = d->in_b; w.ldA = d->ld_a; w.ldB = d->ld_b; w.Ca = d->c_a; w.Ctot = d->c_a + d->c_b;
@@ -1006,7 +944,7 @@ static int conv2d_wgrad_impl(const refid_wgrad_desc* d, hipStream_t st) {
         REFID_LAUNCH_CHECK("wgrad_pw");
         rc = 0;
     } else if (d->phase != 3 && p.id == P_W3_32x32 && thinout_ok(d)) {
-        for (int k = 0; k < ngrp; ++k)
+        for (int k = 0; k < a.groups; ++k)
             REFID_CHECK((uintptr_t)a.g[k] % 16 == 0, "wgrad (thin output): the gradient tensor must be 16-byte aligned (group %d)", k);
         dim3 grid(g.nsplit);
         switch (d->o_real) {
@@ -1041,10 +979,9 @@ static int conv2d_wgrad_impl(const refid_wgrad_desc* d, hipStream_t st) {
     r.permCo = permCo;
     {   // streaming first stage: S partial slabs (wgrad_wino24.hip::refid_launch_slab_fold; the element-wise stage below read
         // 100 MB of slabs at 0.09 of HBM)
-        const long long slab = (long long)p.ntaps * g.CoP * g.CiP;
         if (const int S = refid_slab_fold_count(slab, g.nsplit)) {
             float* part = d->slabs + (size_t)g.nsplit * slab + (size_t)g.nsplit * g.CoP;
-            if (int rc2 = refid_launch_slab_fold(a.slabs, part, slab, g.nsplit, S, st)) return rc2;
+            if (int rc2 = refid_launch_slab_fold(a.slabs, part, slab, g.nsplit, S, st, defer)) return rc2;
             r.slabs = part;
             r.nsplitW = S;
         }
@@ -1053,23 +990,16 @@ static int conv2d_wgrad_impl(const refid_wgrad_desc* d, hipStream_t st) {
     r.CoP = g.CoP; r.CiP = g.CiP;
     r.iBase = d->i_base; r.iTotal = d->i_total;
     const long long total4 = (long long)p.ntaps * g.CoP * (g.CiP / 4);
-    const int nb = (int)((total4 + 255) / 256);
     // lanes per element: only where one thread per float4 would leave the chip idle (small weight tensors)
     int lpe = 1;
     while (lpe < 8 && (long long)lpe * 2 * total4 <= 65536 && lpe * 2 <= r.nsplitW) lpe *= 2;
     r.perGroup = lpe;
     const int nblocks = (int)((total4 * lpe + 255) / 256);
-    if (defer_now) {
-        // two queued jobs must not add into the same gradient block (they would run concurrently): flush first
-        for (const RedQueued& q : red_queue)
-            if (q.r.dw == r.dw && q.r.iBase == r.iBase) {
-                if (int rc2 = refid_slab_fold_flush(st)) return rc2;
-                if (int rc2 = red_flush(st)) return rc2;
-                break;
-            }
-        red_queue.push_back({r, nblocks});
-        return 0;
-    }
+    if (defer)
+        return red_queue.push(r, nblocks, [&]() {
+            const int rc2 = refid_slab_fold_flush(st);
+            return rc2 ? rc2 : red_flush(st);
+        });
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(nblocks), dim3(256), 0, st, r);
     REFID_LAUNCH_CHECK("wgrad_reduce");
     return 0;

@@ -18,7 +18,6 @@
 // reduction of conv_wgrad.hip); pixel phases are added in order through LDS at the end; the bias gradient is the sum of the
 // gradient operand as it goes by.  Pixels past the end of a tensor need no test: their offsets lie beyond the buffer
 // descriptor's range and the DMA fills zeros.
-#include "common.h"
 #include "wgrad_args.h"
 #include <cstdlib>
 
@@ -205,9 +204,7 @@ bool refid_wgrad_pws_ok(const refid_wgrad_desc* d) {
     if (d->c_o < 64 || d->c_o % 32 || d->c_a % 32 || d->c_b % 32 || (d->i_total - d->i_base) % 32) return false;
     if (d->ld_g % 4 || d->ld_a % 4 || (d->c_b && d->ld_b % 4)) return false;
     PwsPlan p;
-    if (!pws_plan(d, p)) return false;
-    const long long npix = (long long)d->n * d->h * d->w, lim = 0x7fffffffLL;
-    return npix * d->ld_g * 4 < lim && npix * d->ld_a * 4 < lim && (!d->c_b || npix * d->ld_b * 4 < lim);
+    return pws_plan(d, p) && refid_wgrad_offsets_fit(d);
 }
 
 // pixels per ring buffer of the tile this geometry takes (the patch form's row width must be a multiple of it); 0: not eligible
@@ -217,30 +214,16 @@ int refid_wgrad_pws_pixels_per_buffer(const refid_wgrad_desc* d) {
     return pws_pb(p.ow, p.wi);
 }
 
-void refid_wgrad_pws_geo(const refid_wgrad_desc* d, int* ncoT, int* nciT, int* nsplit, int* CoP, int* CiP) {
+// two workgroups per CU; the K tiles are the ring buffers' runs of pixels
+WgSplit refid_wgrad_pws_geo(const refid_wgrad_desc* d) {
     PwsPlan p;
     pws_plan(d, p);
-    const int ci_geo = (d->phase != 0) ? d->i_total - d->i_base : d->c_a + d->c_b;
-    const int ci = ci_geo > d->c_a + d->c_b ? ci_geo : d->c_a + d->c_b;
-    *ncoT = cdiv(d->c_o, 32 * p.ow);
-    *nciT = cdiv(ci, 32 * p.wi);
-    const long long npix = (long long)d->n * d->h * d->w;
-    const long long tiles = (npix + pws_pb(p.ow, p.wi) - 1) / pws_pb(p.ow, p.wi);
-    int want = cdiv(512, *ncoT * *nciT);                    // two workgroups per CU
-    if (want >= 8) want = want / 8 * 8;
-    if (want > tiles) want = (int)tiles;
-    if (want < 1) want = 1;
-    *nsplit = want;
-    *CoP = *ncoT * 32 * p.ow;
-    *CiP = *nciT * 32 * p.wi;
+    return refid_wgrad_split(d, 32 * p.ow, 32 * p.wi, 0, pws_pb(p.ow, p.wi), 512, true);
 }
 
 int refid_wgrad_pws_launch(const refid_wgrad_desc* d, const WgKArgs& a, int nciT, int ncoT, hipStream_t st) {
     PwsPlan p;
     pws_plan(d, p);
-    for (int k = 0; k < a.groups; ++k)
-        REFID_CHECK(((uintptr_t)a.g[k] | (uintptr_t)a.inA[k] | (uintptr_t)(d->c_b ? a.inB[k] : nullptr)) % 16 == 0,
-                    "wgrad (1x1 streaming): tensors must be 16-byte aligned (group %d)", k);
     REFID_CHECK(!a.patchW || a.patchW % pws_pb(p.ow, p.wi) == 0, "wgrad (streaming, patch form): the row width must be a multiple of %d pixels",
                 pws_pb(p.ow, p.wi));
     const dim3 grid(a.nsplit, nciT, ncoT);

@@ -13,75 +13,45 @@
 // tiles (gradient tile 4x32 pixels x 64 o, input halo 6x34 pixels x 32 i; conflict-free
 // ds_read_b32 of 32 consecutive channels) -- no transformed copy is ever stored.  Split-K over pixel
 // tiles into private slabs [split][xi][o][i]; bias gradient rides along as in conv_wgrad.hip.
-#include "common.h"
-#include <cstdlib>
+#include "wgrad_args.h"
 #include <type_traits>
 
 // Timing experiments only (tools/probes/wgrad_wino_ablate.py builds the variants; results are wrong for n != 0):
-//   product tile:   1: tiles are not re-staged (no ds_write pass, no second barrier)   2: no global tile loads
-//                   3: neither, no barrier   4: 3 + operands from registers -- 3 and 4 are NOT bounds: with nothing left in
-//                   the loop that writes LDS or synchronises, the compiler hoists every LDS read out of it
-//   LDS-DMA tile (experimental builds, algo 4):   5: no DMA in the K loop   6: no wait / barrier
-//                   11: every request dead (DMA issued, all offsets out of range: zero fill, no memory traffic)
-//                   12: no DMA, no wait / barrier, scheduling fences kept (the LDS-fed loop by itself)
+//   1: tiles are not re-staged (no ds_write pass, no second barrier)   2: no global tile loads
+//   3: neither, no barrier   4: 3 + operands from registers -- 3 and 4 are NOT bounds: with nothing left in the loop that
+//   writes LDS or synchronises, the compiler hoists every LDS read out of it
 #ifndef REFID_WW_ABLATE
 #define REFID_WW_ABLATE 0
 #endif
-#define WW_DMA_ON (REFID_WW_ABLATE == 0 || REFID_WW_ABLATE == 6 || REFID_WW_ABLATE == 11)
-#define WW_BAR_ON (REFID_WW_ABLATE == 0 || REFID_WW_ABLATE == 5 || REFID_WW_ABLATE == 11)
 
 namespace {
 
 constexpr int TH = 4, TW = 32;                 // output pixels per K tile (2 x 16 Winograd tiles)
-constexpr int TH_FP32 = TH;
 constexpr int COT = 64, CIT = 32;
 constexpr int PX = TH * TW;
 constexpr int HWD = TW + 2, HP = (TH + 2) * HWD;
 constexpr int G4 = COT / 4, X4 = CIT / 4;
 constexpr int G_TOTAL = PX * G4, X_TOTAL = HP * X4;
 constexpr int X_ITEMS = (X_TOTAL + 255) / 256;
-constexpr int lds_bytes_ww(int iw) { return (G_TOTAL + iw * X_TOTAL) * 16 + COT * 4; }
-constexpr int LDS_BYTES = lds_bytes_ww(1);
+constexpr int LDS_BYTES = (G_TOTAL + X_TOTAL) * 16 + COT * 4;
 
-struct WwArgs {
-    // up to REFID_WGRAD_MAX_GROUPS time steps of the same convolution (same geometry): their tiles are one K range
-    const float* g[REFID_WGRAD_MAX_GROUPS]; const float* inA[REFID_WGRAD_MAX_GROUPS]; const float* inB[REFID_WGRAD_MAX_GROUPS];
-    int groups;
-    int ldG, Co;
-    int ldA, ldB, Ca, Ctot;
-    float* slabs; float* bslabs;
-    int N, H, W, Ho, Wo, pad;
-    int tilesX, tilesY, ntiles, nsplit;
-    int CoP, CiP;
-    int accum;
-};
-
-// IW = 32-channel input sub-tiles per workgroup.  IW = 1: 4 waves, two workgroups per CU (the product form).  IW = 2 (round 4
-// experiment, REFID_WGRAD_WINO_IW=2): 8 waves, one workgroup per CU -- waves 0-3 and 4-7 are two copies of the tile above for two
-// NEIGHBOURING input-channel tiles that share ONE staged gradient tile (the 64 x 32-pixel dY tile is fetched once per
-// input-channel tile: 2 x at 64 input channels, 8 x at 256): same waves per SIMD, same per-wave loop, 28 % fewer staged bytes
-// per MFMA at 64 channels -- and measured 0-4 % slower (see the launcher).  Each half stages its own input halo with its own
-// (wave-uniform) source descriptor, so a two-source conv may change source between the halves.
-template <int IW>
-__global__ __launch_bounds__(256 * IW, IW == 1 ? 2 : 1) void wgrad_wino_kernel(const WwArgs a) {
-    constexpr int NT = 256 * IW;
-    constexpr int GI = G_TOTAL / NT;                       // gradient-tile items per thread
+__global__ __launch_bounds__(256, 2) void wgrad_wino_kernel(const WgKArgs a) {
+    constexpr int GI = G_TOTAL / 256;                      // gradient-tile items per thread
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid0 = threadIdx.x;
-    const int half = IW == 2 ? __builtin_amdgcn_readfirstlane(tid0 >> 8) : 0;     // wave-uniform
     f32x4* sG4 = reinterpret_cast<f32x4*>(smem);
-    f32x4* sX4 = sG4 + G_TOTAL + half * X_TOTAL;
-    float* sBias = reinterpret_cast<float*>(sG4 + G_TOTAL + IW * X_TOTAL);
+    f32x4* sX4 = sG4 + G_TOTAL;
     const float* sG = reinterpret_cast<const float*>(sG4);
     const float* sX = reinterpret_cast<const float*>(sX4);
 
-    const int tid = tid0 & 255;                            // thread inside its half (input-halo staging, compute roles)
+    // (two names for one value: the mask is a no-op under the launch bound, but the gradient-tile staging written on tid0 and
+    //  the halo staging / compute roles on tid is the form whose instruction schedule was measured; device code stays as it is)
+    const int tid0 = threadIdx.x;
+    const int tid = tid0 & 255;
     const int lane = tid & 63, wave = tid >> 6;
     const int li = lane & 31, kh = lane >> 5;
     const int ti = wave;                                   // transform row owned by this wave
-    const int co0 = blockIdx.z * COT, ci0 = (blockIdx.y * IW + half) * CIT;
+    const int co0 = blockIdx.z * COT, ci0 = blockIdx.y * CIT;
     const int split = blockIdx.x;
-
 
     const int gq = tid0 % G4, xq = tid % X4;
     const int gco = co0 + gq * 4;
@@ -125,7 +95,7 @@ __global__ __launch_bounds__(256 * IW, IW == 1 ? 2 : 1) void wgrad_wino_kernel(c
         const int xbase = ((n * a.H + iy0) * a.W + ix0) * xld * 4 + xcc * 4;
 #pragma unroll
         for (int it = 0; it < GI; ++it) {
-            const int p = tid0 / G4 + it * (NT / G4);
+            const int p = tid0 / G4 + it * (256 / G4);
             const int dy = p / TW, dx = p % TW;
             const bool ok = gcok && oy0 + dy < a.Ho && ox0 + dx < a.Wo;
             const int vo = ok ? gbase + (dy * a.Wo + dx) * a.ldG * 4 : -1;
@@ -144,7 +114,7 @@ __global__ __launch_bounds__(256 * IW, IW == 1 ? 2 : 1) void wgrad_wino_kernel(c
     auto store_tile = [&]() {
 #pragma unroll
         for (int it = 0; it < GI; ++it) {
-            const int p = tid0 / G4 + it * (NT / G4);
+            const int p = tid0 / G4 + it * (256 / G4);
             sG4[p * G4 + gq] = rg[it];
             bsum += rg[it];          // bias partial: summed HERE, not at load time -- using a prefetched register right
                                      // after its load was issued forced a vmcnt(0) before the MFMA section
@@ -279,8 +249,7 @@ __global__ __launch_bounds__(256 * IW, IW == 1 ? 2 : 1) void wgrad_wino_kernel(c
         }
         __syncthreads();
         if (tid0 < COT) {
-            float tot = ((sred[tid0] + sred[COT + tid0]) + sred[2 * COT + tid0]) + sred[3 * COT + tid0];
-            if (IW == 2) tot += ((sred[4 * COT + tid0] + sred[5 * COT + tid0]) + sred[6 * COT + tid0]) + sred[7 * COT + tid0];
+            const float tot = ((sred[tid0] + sred[COT + tid0]) + sred[2 * COT + tid0]) + sred[3 * COT + tid0];
             float* dst = a.bslabs + (long long)split * a.CoP + co0 + tid0;
             *dst = a.accum ? *dst + tot : tot;
         }
@@ -350,82 +319,29 @@ __global__ __launch_bounds__(256) void wgrad_wino_reduce_kernel(const WrArgs a) 
     }
 }
 
-struct Geo { int ncoT, nciT, tilesX, tilesY, ntiles, nsplit, CoP, CiP; };
-
-Geo geo_of(const refid_wgrad_desc* d) {
-    const int TH = TH_FP32;
-    Geo g;
-    const int cot = COT;
-    g.ncoT = cdiv(d->c_o, cot);
-    const int ci_geo = (d->phase != 0) ? d->i_total - d->i_base : d->c_a + d->c_b;   // stable across steps
-    g.nciT = cdiv(ci_geo > d->c_a + d->c_b ? ci_geo : d->c_a + d->c_b, CIT);
-    g.tilesX = cdiv(d->wo, TW);
-    g.tilesY = cdiv(d->ho, TH);
-    g.ntiles = g.tilesX * g.tilesY * d->n;
-    int want = cdiv(512, g.ncoT * g.nciT);
-    if (want < 1) want = 1;
-    if (want > g.ntiles) want = g.ntiles;
-    g.nsplit = want;
-    g.CoP = g.ncoT * cot;
-    g.CiP = g.nciT * CIT;
-    return g;
-}
+// 2 resident workgroups per CU on 256 CUs, one round
+WgSplit geo_of(const refid_wgrad_desc* d) { return refid_wgrad_split(d, COT, CIT, TH, TW, 512, false); }
 
 }  // namespace
 
 size_t refid_wgrad_wino_workspace_bytes(const refid_wgrad_desc* d) {
-    const Geo g = geo_of(d);
+    const WgSplit g = geo_of(d);
     return ((size_t)g.nsplit * 16 * g.CoP * g.CiP + (size_t)g.nsplit * g.CoP) * sizeof(float);
 }
 
 int refid_wgrad_wino_launch(const refid_wgrad_desc* d, hipStream_t st) {
-    static std::atomic<unsigned long long> attr_done{0}, attr_doneW{0};
-    if (int rc = refid_lds_attr_once(attr_done, &wgrad_wino_kernel<1>, lds_bytes_ww(1), "wgrad_wino")) return rc;
-    if (int rc = refid_lds_attr_once(attr_doneW, &wgrad_wino_kernel<2>, lds_bytes_ww(2), "wgrad_wino/8 waves")) return rc;
+    static std::atomic<unsigned long long> attr_done{0};
+    if (int rc = refid_lds_attr_once(attr_done, &wgrad_wino_kernel, LDS_BYTES, "wgrad_wino")) return rc;
     REFID_CHECK(d->algo != 3 && d->algo != 4,
                 "wgrad: algo 3 (Winograd, six bf16 products) and algo 4 (Winograd, LDS-DMA staging) were experiments that did not "
                 "beat algo 1 (DESIGN.md section 7); they are no longer built");
-    const Geo g = geo_of(d);
+    const WgSplit g = geo_of(d);
     REFID_CHECK(d->c_b == 0 || d->c_a % CIT == 0, "wgrad (Winograd): c_a must be a multiple of %d for two sources", CIT);
-    {
-        const long long lim = 0x7fffffffLL;
-        REFID_CHECK((long long)d->n * d->ho * d->wo * d->ld_g * 4 < lim && (long long)d->n * d->h * d->w * d->ld_a * 4 < lim &&
-                        (d->c_b == 0 || (long long)d->n * d->h * d->w * d->ld_b * 4 < lim),
-                    "wgrad (Winograd): tensor too large for 32-bit buffer offsets (use algo 0)");
-    }
-    WwArgs a;
-    const int ngrp = d->groups > 1 ? d->groups : 1;
-    REFID_CHECK(ngrp <= REFID_WGRAD_MAX_GROUPS, "wgrad: at most %d grouped time steps", REFID_WGRAD_MAX_GROUPS);
-    for (int k = 0; k < REFID_WGRAD_MAX_GROUPS; ++k) {
-        const bool on = k > 0 && k < ngrp;
-        a.g[k] = k == 0 ? d->g : (on ? d->g_more[k - 1] : d->g);
-        a.inA[k] = k == 0 ? d->in_a : (on ? d->in_a_more[k - 1] : d->in_a);
-        a.inB[k] = k == 0 ? d->in_b : (on ? d->in_b_more[k - 1] : d->in_b);
-        REFID_CHECK(a.g[k] && a.inA[k] && (d->c_b == 0 || a.inB[k]), "wgrad: null tensor pointer in group %d", k);
-    }
-    a.groups = ngrp;
-    a.ldG = d->ld_g; a.Co = d->c_o;
-    a.ldA = d->ld_a; a.ldB = d->ld_b;
-    a.Ca = d->c_a; a.Ctot = d->c_a + d->c_b;
-    a.slabs = d->slabs;
-    a.bslabs = d->db ? d->slabs + (size_t)g.nsplit * 16 * g.CoP * g.CiP : nullptr;
-    a.N = d->n; a.H = d->h; a.W = d->w; a.Ho = d->ho; a.Wo = d->wo; a.pad = d->pad;
-    a.tilesX = g.tilesX; a.tilesY = g.tilesY; a.ntiles = g.ntiles; a.nsplit = g.nsplit;
-    a.CoP = g.CoP; a.CiP = g.CiP;
-    a.accum = (d->phase == 2);
+    REFID_CHECK(refid_wgrad_offsets_fit(d), "wgrad (Winograd): tensor too large for 32-bit buffer offsets (use algo 0)");
+    WgKArgs a;
+    if (int rc = refid_wgrad_fill(a, d, g, 16ll * g.CoP * g.CiP, false, "Winograd")) return rc;
     if (d->phase != 3) {
-        {
-            // REFID_WGRAD_WINO_IW=2: two neighbouring input-channel tiles per workgroup (8 waves, the gradient tile staged once
-            // for both) whenever the tile count is even.  Measured (tools/bench_wgrad_wino.py regs, round 4): 0-4 % SLOWER than
-            // the 4-wave form on every config-2 shape (95.6 vs 95.3 TF/s at 64->64 @256^2, 105-106 vs 109-110 at the 128- and
-            // 256-channel layers; train step 472-474 vs 471 ms) -- the staged bytes it saves were not what limits this tile,
-            // the eight-wave barriers cost more.  Off; same weight-gradient bits, bias partials in a different fixed order.
-            static const int iw_max = []() { const char* e = getenv("REFID_WGRAD_WINO_IW"); return e ? atoi(e) : 1; }();
-            if (iw_max >= 2 && g.nciT % 2 == 0)
-                hipLaunchKernelGGL(wgrad_wino_kernel<2>, dim3(g.nsplit, g.nciT / 2, g.ncoT), dim3(512), lds_bytes_ww(2), st, a);
-            else
-                hipLaunchKernelGGL(wgrad_wino_kernel<1>, dim3(g.nsplit, g.nciT, g.ncoT), dim3(256), lds_bytes_ww(1), st, a);
-        }
+        hipLaunchKernelGGL(wgrad_wino_kernel, dim3(g.nsplit, g.nciT, g.ncoT), dim3(256), LDS_BYTES, st, a);
         REFID_LAUNCH_CHECK("wgrad_wino");
     }
     if (d->phase == 1 || d->phase == 2) return 0;          // reduction deferred (phase 3)

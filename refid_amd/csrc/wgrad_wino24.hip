@@ -36,12 +36,9 @@
 // (coordinates advance by scalar increments).
 // Split-K slabs [split][24][o][i] persist over the T recurrent steps exactly like wgrad_wino.hip's (phase 1 / 2 / 3); the
 // bias gradient is the transform point (1, 1) of Gy dY Gx^T (rows {1,1} x {1,1,1,1}: the tile sum), summed by wave 1.
-#include "common.h"
 #include "wgrad_args.h"
 #include <cstdlib>
-#include <cstring>
 #include <type_traits>
-#include <vector>
 
 // Timing experiments only (tools/probes/w24_ablate.py builds the variants; results are wrong for n != 0):
 //   1: no DMA requests (stale tiles: no global traffic, no LDS writes)   2: no MFMAs (operands kept alive)
@@ -85,19 +82,11 @@ __device__ __forceinline__ f32x2 w24_pair(f32x2 a, f32x2 b) {
     return d;
 }
 
-struct W24Args {
-    const float* g[REFID_WGRAD_MAX_GROUPS]; const float* inA[REFID_WGRAD_MAX_GROUPS]; const float* inB[REFID_WGRAD_MAX_GROUPS];
-    int groups;
-    int ldG, Co;
-    int ldA, ldB, Ca, Ctot;
-    float* slabs; float* bslabs;
-    int N, H, W, Ho, Wo, pad;
-    int tilesX, tilesY, ntiles, nsplit;
-    int CoP, CiP;
-    int accum;
+struct W24Args : WgArgs {
     // wgrad_wino24_down_kernel only (conv_down, 4x4 stride 2 pad 1): H, W above are the PHASE image's size (= Ho, Wo)
     int Hin, Win, ncoT;
 };
+static_assert(sizeof(W24Args) == sizeof(WgArgs) + 8, "three ints behind accum: one in the base's tail padding, two more");
 
 // The transforms of one wave (F(3,2) row I), PACKED over two consecutive tile columns (steps s, s+1): a ds_read2st64 of
 // (column c, column c + 4) lands in a register pair, every transform instruction is a v_pk_* on such pairs, and the MFMAs
@@ -1229,43 +1218,25 @@ __global__ __launch_bounds__(256) void wgrad_wino24_reduce_batch_kernel(const W2
     else w24_reduce_body(b.job[j], blk, part);
 }
 
-struct W24rQueued { W24rArgs r; int nblocks; };
-thread_local std::vector<W24rQueued> w24_queue;
-
-struct Geo24 { int ncoT, nciT, tilesX, tilesY, ntiles, nsplit, CoP, CiP; };
+thread_local WgFinishQueue<W24rArgs, W24rBatch> w24_queue;
 
 int ns_of(const refid_wgrad_desc* d) { return d->c_o <= 32 ? 1 : 2; }      // 32-channel output tile for the thin layers
 bool is_down(const refid_wgrad_desc* d) { return d->kh == 4; }              // algo 7: conv_down (wgrad_wino24_down_kernel)
 
-Geo24 geo24_of(const refid_wgrad_desc* d) {
-    Geo24 g;
-    const int OT = 32 * ns_of(d);
-    g.ncoT = cdiv(d->c_o, OT);
-    const int ci_geo = (d->phase != 0) ? d->i_total - d->i_base : d->c_a + d->c_b;     // stable across steps
-    g.nciT = cdiv(ci_geo > d->c_a + d->c_b ? ci_geo : d->c_a + d->c_b, IT);
-    g.tilesX = cdiv(d->wo, GW);
-    g.tilesY = cdiv(d->ho, is_down(d) ? DGH : GH);
-    g.ntiles = g.tilesX * g.tilesY * d->n;
-    // two (NS = 1: three) workgroups per CU; a multiple of 8 splits keeps the workgroups of one K range on one XCD (grid x
-    // is fastest)
-    // (read per call, like REFID_W24_PAIR: a test walks the split plan through the ring's short ranges in one process)
+// two (NS = 1: three) workgroups per CU; a multiple of 8 splits keeps the workgroups of one K range on one XCD.  REFID_W24_WGS is
+// read per call, like REFID_W24_PAIR: a test walks the split plan through the ring's short ranges in one process.
+WgSplit geo24_of(const refid_wgrad_desc* d) {
     const char* wgsEnv = getenv("REFID_W24_WGS");
     const int wgs = wgsEnv ? atoi(wgsEnv) : 512;
-    int want = cdiv(ns_of(d) == 1 ? wgs * 3 / 2 : wgs, g.ncoT * g.nciT * (is_down(d) ? 4 : 1));
-    if (want >= 8) want = want / 8 * 8;
-    if (want < 1) want = 1;
-    if (want > g.ntiles) want = g.ntiles;
-    g.nsplit = want;
-    g.CoP = g.ncoT * OT;
-    g.CiP = g.nciT * IT;
-    return g;
+    return refid_wgrad_split(d, 32 * ns_of(d), IT, is_down(d) ? DGH : GH, GW, ns_of(d) == 1 ? wgs * 3 / 2 : wgs, true,
+                             is_down(d) ? 4 : 1);
 }
 
 // The pair form (eight waves, two input-channel tiles per workgroup) takes every 64-channel-tile launch with an even number
 // of input tiles; REFID_W24_PAIR=0 keeps the four-wave form everywhere, =2 makes a launch the pair form cannot take an
 // error instead of a fallback (tests observe the routing through it).  Read per call: one process can alternate the forms.
 int pair_mode() { const char* e = getenv("REFID_W24_PAIR"); return e ? atoi(e) : 1; }
-bool pair_fits(const refid_wgrad_desc* d, const Geo24& g) { return ns_of(d) == 2 && g.nciT % 2 == 0; }
+bool pair_fits(const refid_wgrad_desc* d, const WgSplit& g) { return ns_of(d) == 2 && g.nciT % 2 == 0; }
 
 }  // namespace
 
@@ -1280,9 +1251,9 @@ int refid_slab_fold_count(long long slabFloats, int nsplit) {
     if (S >= nsplit) S = nsplit / 2;
     return S < 1 ? 1 : S;
 }
-int refid_launch_slab_fold(const float* slabs, float* part, long long slabFloats, int nsplit, int S, hipStream_t st) {
+int refid_launch_slab_fold(const float* slabs, float* part, long long slabFloats, int nsplit, int S, hipStream_t st, bool defer) {
     static const bool batch_folds = !(getenv("REFID_FOLD_BATCH") && getenv("REFID_FOLD_BATCH")[0] == '0');
-    if (batch_folds && refid_finish_defer_now()) {         // phase 4: with the other queued folds (refid_slab_fold_flush)
+    if (batch_folds && defer) {         // phase 4: with the other queued folds (refid_slab_fold_flush)
         fold_queue.push_back({slabs, part, slabFloats, nsplit, S});
         return 0;
     }
@@ -1316,37 +1287,27 @@ int refid_slab_fold_flush(hipStream_t st) {
 }
 
 int refid_wino24_finish_flush(hipStream_t st) {
-    size_t at = 0;
-    while (at < w24_queue.size()) {
-        W24rBatch b;
-        memset(&b, 0, sizeof(b));
-        int n = 0, blk = 0;
-        for (; n < REFID_FINISH_BATCH && at < w24_queue.size(); ++n, ++at) {
-            b.job[n] = w24_queue[at].r;
-            b.blk0[n] = blk;
-            blk += w24_queue[at].nblocks;
-        }
-        b.blk0[n] = blk; b.n = n;
+    return w24_queue.flush([&](const W24rBatch& b, int blk) {
         hipLaunchKernelGGL(wgrad_wino24_reduce_batch_kernel, dim3(blk), dim3(256), 0, st, b);
-        if (hipGetLastError() != hipSuccess) { w24_queue.clear(); refid_set_error("wgrad_wino24_reduce_batch: launch failed"); return 1; }
-    }
-    w24_queue.clear();
-    return 0;
+        if (hipGetLastError() == hipSuccess) return true;
+        refid_set_error("wgrad_wino24_reduce_batch: launch failed");
+        return false;
+    });
 }
 
 namespace {
-long long slab_floats(const refid_wgrad_desc* d, const Geo24& g) {
+long long slab_floats(const refid_wgrad_desc* d, const WgSplit& g) {
     return (long long)(is_down(d) ? 4 * NXD : NXI) * g.CoP * g.CiP;
 }
 }  // namespace
 
 size_t refid_wgrad_wino24_workspace_bytes(const refid_wgrad_desc* d) {
-    const Geo24 g = geo24_of(d);
+    const WgSplit g = geo24_of(d);
     const long long slab = slab_floats(d, g);
     return ((size_t)g.nsplit * slab + (size_t)g.nsplit * g.CoP + (size_t)refid_slab_fold_count(slab, g.nsplit) * slab) * sizeof(float);
 }
 
-int refid_wgrad_wino24_launch(const refid_wgrad_desc* d, hipStream_t st) {
+int refid_wgrad_wino24_launch(const refid_wgrad_desc* d, hipStream_t st, bool defer) {
     static std::atomic<unsigned long long> attr_done{0}, attr_done1{0}, attr_done2{0}, attr_done3{0}, attr_done4{0};
     if (int rc = refid_lds_attr_once(attr_done, &wgrad_wino24_kernel<2>, lds24_bytes(2), "wgrad_wino24")) return rc;
     if (int rc = refid_lds_attr_once(attr_done1, &wgrad_wino24_kernel<1>, lds24_bytes(1), "wgrad_wino24<1>")) return rc;
@@ -1354,7 +1315,7 @@ int refid_wgrad_wino24_launch(const refid_wgrad_desc* d, hipStream_t st) {
     if (int rc = refid_lds_attr_once(attr_done3, &wgrad_wino24_down_kernel<2>, down_lds_bytes(2), "wgrad_wino24_down")) return rc;
     if (int rc = refid_lds_attr_once(attr_done4, &wgrad_wino24_down_kernel<1>, down_lds_bytes(1), "wgrad_wino24_down<1>")) return rc;
     const bool down = is_down(d);
-    const Geo24 g = geo24_of(d);
+    const WgSplit g = geo24_of(d);
     const long long slab = slab_floats(d, g);
     const int pmode = pair_mode();
     const bool pair = !down && pmode != 0 && pair_fits(d, g);    // (conv_down's kernel has no pair layout)
@@ -1367,36 +1328,11 @@ int refid_wgrad_wino24_launch(const refid_wgrad_desc* d, hipStream_t st) {
     REFID_CHECK(d->ld_g % 4 == 0 && d->ld_a % 4 == 0 && (d->c_b == 0 || d->ld_b % 4 == 0) && d->c_o % 4 == 0 &&
                     d->c_a % 4 == 0 && d->c_b % 4 == 0,
                 "wgrad (Winograd 2x4 tiles): pitches and channel counts must be multiples of 4 floats (16-byte LDS-DMA pieces)");
-    {
-        const long long lim = 0x7fffffffLL;
-        REFID_CHECK((long long)d->n * d->ho * d->wo * d->ld_g * 4 < lim && (long long)d->n * d->h * d->w * d->ld_a * 4 < lim &&
-                        (d->c_b == 0 || (long long)d->n * d->h * d->w * d->ld_b * 4 < lim),
-                    "wgrad (Winograd 2x4 tiles): tensor too large for 32-bit buffer offsets (use algo 0)");
-    }
+    REFID_CHECK(refid_wgrad_offsets_fit(d), "wgrad (Winograd 2x4 tiles): tensor too large for 32-bit buffer offsets (use algo 0)");
     W24Args a;
-    const int ngrp = d->groups > 1 ? d->groups : 1;
-    REFID_CHECK(ngrp <= REFID_WGRAD_MAX_GROUPS, "wgrad: at most %d grouped time steps", REFID_WGRAD_MAX_GROUPS);
-    for (int k = 0; k < REFID_WGRAD_MAX_GROUPS; ++k) {
-        const bool on = k > 0 && k < ngrp;
-        a.g[k] = k == 0 ? d->g : (on ? d->g_more[k - 1] : d->g);
-        a.inA[k] = k == 0 ? d->in_a : (on ? d->in_a_more[k - 1] : d->in_a);
-        a.inB[k] = k == 0 ? d->in_b : (on ? d->in_b_more[k - 1] : d->in_b);
-        REFID_CHECK(a.g[k] && a.inA[k] && (d->c_b == 0 || a.inB[k]), "wgrad: null tensor pointer in group %d", k);
-        REFID_CHECK(((uintptr_t)a.g[k] | (uintptr_t)a.inA[k] | (uintptr_t)(d->c_b ? a.inB[k] : nullptr)) % 16 == 0,
-                    "wgrad (Winograd 2x4 tiles): tensors must be 16-byte aligned (group %d)", k);
-    }
-    a.groups = ngrp;
-    a.ldG = d->ld_g; a.Co = d->c_o;
-    a.ldA = d->ld_a; a.ldB = d->ld_b;
-    a.Ca = d->c_a; a.Ctot = d->c_a + d->c_b;
-    a.slabs = d->slabs;
-    a.bslabs = d->db ? d->slabs + (size_t)g.nsplit * slab : nullptr;
-    a.N = d->n; a.H = d->h; a.W = d->w; a.Ho = d->ho; a.Wo = d->wo; a.pad = d->pad;
+    if (int rc = refid_wgrad_fill(a, d, g, slab, true, "Winograd 2x4 tiles")) return rc;
     a.Hin = d->h; a.Win = d->w; a.ncoT = g.ncoT;
     if (down) { a.H = d->ho; a.W = d->wo; }                 // the phase image
-    a.tilesX = g.tilesX; a.tilesY = g.tilesY; a.ntiles = g.ntiles; a.nsplit = g.nsplit;
-    a.CoP = g.CoP; a.CiP = g.CiP;
-    a.accum = (d->phase == 2);
     if (d->phase != 3) {
         if (down) {
             if (ns_of(d) == 1)
@@ -1417,9 +1353,8 @@ int refid_wgrad_wino24_launch(const refid_wgrad_desc* d, hipStream_t st) {
     r.nsplit = g.nsplit; r.Co = d->o_real;
     int nred = g.nsplit;                   // slabs the element-wise stage reads
     if (const int S = refid_slab_fold_count(slab, g.nsplit)) {
-        const long long slabFloats = slab;
         float* part = d->slabs + (size_t)g.nsplit * slab + (size_t)g.nsplit * g.CoP;      // (behind the bias slabs)
-        if (int rc = refid_launch_slab_fold(a.slabs, part, slabFloats, g.nsplit, S, st)) return rc;
+        if (int rc = refid_launch_slab_fold(a.slabs, part, slab, g.nsplit, S, st, defer)) return rc;
         r.slabs = part;
         nred = S;
     }
@@ -1431,22 +1366,18 @@ int refid_wgrad_wino24_launch(const refid_wgrad_desc* d, hipStream_t st) {
     r.perGroup = lpe;
     r.nsplitW = nred;
     r.down = down;
-    if (refid_finish_defer_now()) {
-        for (const W24rQueued& q : w24_queue)              // (two jobs on one gradient block would race: flush first)
-            if (q.r.dw == r.dw && q.r.iBase == r.iBase) {
-                if (int rc = refid_slab_fold_flush(st)) return rc;
-                if (int rc = refid_wino24_finish_flush(st)) return rc;
-                break;
-            }
-        w24_queue.push_back({r, down ? (int)((total * 4 + 255) / 256) : (int)((total + 256 / lpe - 1) / (256 / lpe))});
-        return 0;
-    }
+    const int nblocks = down ? (int)((total * 4 + 255) / 256) : (int)((total + 256 / lpe - 1) / (256 / lpe));
+    if (defer)
+        return w24_queue.push(r, nblocks, [&]() {
+            const int rc = refid_slab_fold_flush(st);
+            return rc ? rc : refid_wino24_finish_flush(st);
+        });
     if (down) {
-        hipLaunchKernelGGL(wgrad_wino24_reduce_down_kernel, dim3((int)((total * 4 + 255) / 256)), dim3(256), 0, st, r);
+        hipLaunchKernelGGL(wgrad_wino24_reduce_down_kernel, dim3(nblocks), dim3(256), 0, st, r);
         REFID_LAUNCH_CHECK("wgrad_wino24_reduce_down");
         return 0;
     }
-    hipLaunchKernelGGL(wgrad_wino24_reduce_kernel, dim3((int)((total + 256 / lpe - 1) / (256 / lpe))), dim3(256), 0, st, r);
+    hipLaunchKernelGGL(wgrad_wino24_reduce_kernel, dim3(nblocks), dim3(256), 0, st, r);
     REFID_LAUNCH_CHECK("wgrad_wino24_reduce");
     return 0;
 }

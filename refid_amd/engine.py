@@ -143,7 +143,8 @@ USE_POINTWISE = os.environ.get("REFID_POINTWISE", "1") != "0"     # register-ope
 OVERLAP_WGRAD = False      # only bench.py's save / restore around its --full legs touches this name; nothing reads it
 for _var, _gone in (("REFID_OVERLAP_WGRAD", lambda v: v not in ("", "0", "auto")),
                     ("REFID_WGRAD_BATCH", lambda v: True),
-                    ("REFID_W24_DOWN", lambda v: v == "0")):
+                    ("REFID_W24_DOWN", lambda v: v == "0"),
+                    ("REFID_WGRAD_WINO_IW", lambda v: v.isdigit() and int(v) >= 2)):
     _val = os.environ.get(_var)
     if _val is not None and _gone(_val):
         raise RefidHipError(f"{_var}={_val}: the path this switch selected was removed (DESIGN.md sections 5 and 7); "

@@ -165,9 +165,9 @@ LONG_E = ["w3_direct", "wino22", "wino24", "wino24_2src", "wino24_co32", "down_w
 
 
 def split_plan(name, n, ho, wo):
-    """(nsplit, slab floats, workspace bytes) of a form's launch -- a mirror of geo_of / plan_of (conv_wgrad.hip), geo_of
-    (wgrad_wino.hip), geo24_of (wgrad_wino24.hip), refid_wgrad_pws_geo (wgrad_pws.hip), thin_nsplit and refid_slab_fold_count, for
-    the phased calls (ci = i_total)."""
+    """(nsplit, slab floats, workspace bytes) of a form's launch -- a mirror of refid_wgrad_split (wgrad_args.h) with each
+    family's tile constants (plan_of in conv_wgrad.hip, pws_plan in wgrad_pws.hip), of thin_nsplit and of refid_slab_fold_count,
+    for the phased calls (ci = i_total)."""
     k, s, p, co, ca, cb, algo, _ = FORMS[name]
     ci = ca + cb
     ntaps = k * k

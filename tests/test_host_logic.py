@@ -505,15 +505,17 @@ def test_weight_gradient_group_is_capped_by_free_memory():
 
 @pytest.mark.parametrize("var,val,raises", [("REFID_OVERLAP_WGRAD", "1", True), ("REFID_WGRAD_BATCH", "4", True),
                                             ("REFID_W24_DOWN", "0", True), ("REFID_OVERLAP_WGRAD", "0", False),
-                                            ("REFID_W24_DOWN", "1", False)])
+                                            ("REFID_W24_DOWN", "1", False), ("REFID_WGRAD_WINO_IW", "2", True),
+                                            ("REFID_WGRAD_WINO_IW", "1", False)])
 def test_switches_of_removed_paths_raise_at_import(var, val, raises):
-    """The weight-gradient side stream (REFID_OVERLAP_WGRAD, REFID_WGRAD_BATCH) and conv_down's 3x3 sub-block weight gradient
-    (REFID_W24_DOWN=0) are gone: asking for one must fail loudly at `import refid_amd.engine`, naming the variable, instead of
+    """The weight-gradient side stream (REFID_OVERLAP_WGRAD, REFID_WGRAD_BATCH), conv_down's 3x3 sub-block weight gradient
+    (REFID_W24_DOWN=0) and the eight-wave form of the 2x2 Winograd weight gradient (REFID_WGRAD_WINO_IW=2) are gone: asking for one must fail loudly at `import refid_amd.engine`, naming the variable, instead of
     silently running the default; the values that meant the default still import.  A fresh interpreter per case; no GPU."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = {k: v for k, v in os.environ.items() if k not in ("REFID_OVERLAP_WGRAD", "REFID_WGRAD_BATCH", "REFID_W24_DOWN")}
+    env = {k: v for k, v in os.environ.items() if k not in ("REFID_OVERLAP_WGRAD", "REFID_WGRAD_BATCH", "REFID_W24_DOWN",
+                                                             "REFID_WGRAD_WINO_IW")}
     env[var] = val
     r = subprocess.run([sys.executable, "-c", "import refid_amd.engine"], cwd=root, env=env, capture_output=True, text=True)
     if raises:
@@ -551,6 +553,96 @@ def test_streaming_weight_gradient_eligibility_mirrors_the_library():
                     assert not lib_ok, (ci, co, w_lo)
                 else:
                     assert not lib_ok or py_ok, (ci, co, w_lo)
+
+
+# (k, stride, pad, c_o, c_a, c_b, n, ho, wo, algo, phase, i_base, i_total (0: c_a + c_b), workspace bytes).  The byte counts were
+# produced by the library as it stood BEFORE the four launchers' geometry functions became one split plan
+# (refid_wgrad_split, csrc/wgrad_args.h); they are data, never to be refreshed from the code under test.
+WGRAD_WORKSPACE_TABLE = [
+    # the four 3x3 direct plans, and the thin-output rows of the 32 x 32 one
+    (3, 1, 1, 64, 64, 0, 2, 64, 64, 0, 0, 0, 0, 21266432),
+    (3, 1, 1, 64, 32, 0, 2, 64, 64, 0, 0, 0, 0, 10649600),
+    (3, 1, 1, 32, 64, 0, 2, 64, 64, 0, 0, 0, 0, 10633216),
+    (3, 1, 1, 32, 32, 0, 2, 64, 64, 0, 0, 0, 0, 5324800),
+    (3, 1, 1, 4, 32, 0, 2, 64, 64, 0, 1, 0, 0, 5324800),
+    (3, 1, 1, 128, 64, 64, 2, 32, 32, 0, 1, 0, 0, 27738112),
+    # 1x1 below the streaming form: the register tile (channels in 32s) and the LDS tile
+    (1, 1, 0, 32, 64, 0, 2, 64, 64, 0, 0, 0, 0, 2375680),
+    (1, 1, 0, 32, 24, 0, 2, 64, 64, 0, 0, 0, 0, 9502720),
+    # 4x4 stride 2 and 2x2 stride 2, direct
+    (4, 2, 1, 64, 32, 0, 2, 32, 32, 0, 0, 0, 0, 10502144),
+    (2, 2, 0, 32, 64, 0, 2, 32, 32, 0, 0, 0, 0, 5259264),
+    # 5x5 with 4 input channels: the thin-input tile
+    (5, 1, 2, 32, 4, 0, 6, 64, 64, 0, 0, 0, 0, 12681216),
+    (5, 1, 2, 32, 4, 0, 46, 128, 128, 0, 1, 0, 0, 50724864),
+    # algo 1
+    (3, 1, 1, 64, 64, 0, 2, 64, 64, 1, 0, 0, 0, 16793600),
+    (3, 1, 1, 128, 64, 64, 2, 32, 32, 1, 1, 0, 0, 16785408),
+    # algo 5: 32- and 64-channel output tiles
+    (3, 1, 1, 32, 32, 0, 2, 64, 64, 5, 0, 0, 0, 14172160),
+    (3, 1, 1, 64, 64, 0, 2, 64, 64, 5, 0, 0, 0, 56655872),
+    (3, 1, 1, 256, 128, 128, 2, 32, 32, 5, 1, 0, 0, 113262592),
+    # algo 7
+    (4, 2, 1, 64, 32, 0, 2, 32, 32, 7, 0, 0, 0, 24254464),
+    (4, 2, 1, 128, 96, 0, 2, 48, 48, 7, 1, 0, 0, 74719232),
+    (4, 2, 1, 32, 32, 0, 2, 32, 32, 7, 1, 0, 0, 13110272),
+    # streaming 1x1: one source, two sources, a c_a that narrows the input tile (4 -> 1 and 4 -> 2 sub-tiles)
+    (1, 1, 0, 64, 64, 0, 2, 64, 64, 0, 0, 0, 0, 4521984),
+    (1, 1, 0, 128, 64, 64, 2, 64, 64, 0, 1, 0, 0, 17956864),
+    (1, 1, 0, 64, 32, 96, 2, 64, 64, 0, 1, 0, 0, 4751360),
+    (1, 1, 0, 128, 64, 192, 2, 64, 64, 0, 1, 0, 0, 18939904),
+    # algo 8 (ConvTranspose2d(2, 2) as a streaming patch GEMM): c_o = the layer's input channels
+    (2, 2, 0, 64, 32, 0, 2, 8, 32, 8, 1, 0, 0, 790528),
+    (2, 2, 0, 128, 64, 0, 2, 16, 64, 8, 1, 0, 0, 18939904),
+    # the first recurrent step: no second source yet, i_total > c_a + c_b; phase 0 sizes by the sources, phase 1 by i_total
+    (3, 1, 1, 64, 64, 0, 2, 64, 64, 0, 0, 0, 128, 21266432),
+    (3, 1, 1, 64, 64, 0, 2, 64, 64, 0, 1, 0, 128, 42500096),
+    (3, 1, 1, 64, 64, 0, 2, 64, 64, 1, 0, 0, 128, 16793600),
+    (3, 1, 1, 64, 64, 0, 2, 64, 64, 1, 1, 0, 128, 33570816),
+    (3, 1, 1, 64, 64, 0, 2, 64, 64, 5, 0, 0, 128, 56655872),
+    (3, 1, 1, 64, 64, 0, 2, 64, 64, 5, 1, 0, 128, 109346816),
+    (1, 1, 0, 64, 64, 0, 2, 64, 64, 0, 0, 0, 128, 4521984),
+    (1, 1, 0, 64, 64, 0, 2, 64, 64, 0, 1, 0, 128, 8978432),
+    (3, 1, 1, 64, 64, 0, 2, 64, 64, 5, 1, 64, 128, 56655872),
+    # an image so small that the tile count caps the split count
+    (3, 1, 1, 64, 64, 0, 1, 8, 8, 0, 0, 0, 0, 885760),
+    (3, 1, 1, 64, 64, 0, 1, 8, 8, 1, 0, 0, 0, 524800),
+    (3, 1, 1, 64, 64, 0, 1, 12, 40, 5, 0, 0, 0, 5114112),
+    (4, 2, 1, 64, 32, 0, 1, 13, 15, 7, 0, 0, 0, 2622208),
+    (1, 1, 0, 64, 64, 0, 1, 9, 33, 0, 0, 0, 0, 248320),
+    # images large enough that the round-to-8 rule bites (171 -> 168, 43 -> 40, 171 -> 168); the first folds 168 slabs into 15
+    (3, 1, 1, 64, 96, 0, 2, 128, 128, 5, 0, 0, 0, 107980800),
+    (4, 2, 1, 64, 96, 0, 2, 64, 64, 7, 0, 0, 0, 88483840),
+    (1, 1, 0, 320, 64, 0, 2, 64, 64, 0, 0, 0, 0, 18345984),
+    # the direct plan's own split (no rounding): 171 slabs folded into 4
+    (3, 1, 1, 64, 192, 0, 2, 128, 128, 0, 0, 0, 0, 82766592),
+]
+
+
+def test_weight_gradient_workspace_sizes_are_pinned():
+    """refid_wgrad_workspace_bytes = nsplit slabs + nsplit bias slabs + the folded partial slabs, so it moves with every part of
+    the split plan: channel tiles, pixel tiles, the workgroup target, the round-to-8 rule, conv_down's four phase grids, the tile
+    count's cap and refid_slab_fold_count.  Held to a recorded table over every family's plan: the four 3x3 direct plans, 1x1 below
+    the streaming form, 4x4 / 2x2 stride 2, the thin-input tile, algos 1, 5 (32- and 64-channel output tiles), 7 and 8, the
+    streaming 1x1 form (one and two sources, input tiles narrowed by c_a), first recurrent steps (i_total > c_a + c_b) in phase
+    0 and 1, images whose tile count caps the split count, images where rounding to 8 bites, and split counts the fold count
+    does not divide.  Host arithmetic: no GPU, and the pointers are never dereferenced."""
+    import ctypes as C
+    from refid_amd import _lib
+    L = _lib.lib()
+    assert len(WGRAD_WORKSPACE_TABLE) >= 30
+    for (k, s, p, co, ca, cb, n, ho, wo, algo, phase, ib, it, want) in WGRAD_WORKSPACE_TABLE:
+        d = _lib.WgradDesc()
+        d.g, d.in_a, d.dw, d.slabs = 4096, 8192, 12288, 16384
+        if cb:
+            d.in_b = 20480
+        d.ld_g, d.c_o, d.ld_a, d.c_a, d.ld_b, d.c_b = co, co, ca, ca, cb, cb
+        d.n, d.ho, d.wo, d.h, d.w = n, ho, wo, ho * s, wo * s
+        d.kh, d.kw, d.stride, d.pad = k, k, s, p
+        d.i_base, d.i_total, d.o_real, d.algo, d.phase = ib, it or ca + cb, co, algo, phase
+        got = L.refid_wgrad_workspace_bytes(C.byref(d))
+        assert got == want, ((k, s, p, co, ca, cb, n, ho, wo, algo, phase, ib, it), got, want)
+
 
 
 def test_cached_conv_descriptors_equal_the_validating_path_byte_for_byte(monkeypatch):
