@@ -5,7 +5,7 @@
 //   * FAC_bias (au:421-426): out = feat * filt[:, :C] + filt[:, C:]  -- forward and backward.
 // NHWC fp32, 16 bytes per lane per access.  All HBM-bound streaming / reduction kernels.  The per-(sample,
 // channel) reductions are two-stage (per-workgroup partials, then a fixed-order final sum in double): no
-// atomics, bit-reproducible.
+// atomics, bit-reproducible.  The HIN statistics take two such reductions: the mean, then the sums of x - mean.
 #include "common.h"
 
 namespace {
@@ -37,12 +37,36 @@ __device__ __forceinline__ void part_sums(F f, int HW, int Q, int ch, float* __r
 __global__ __launch_bounds__(256) void hin_stats_kernel(const float* __restrict__ x, int ldx, int HW, int Q, int ch,
                                                        float* __restrict__ parts) {
     part_sums([&](long long pix, int q, f32x4& sa, f32x4& sb) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(x + pix * ldx + q * 4);
-        sa += v; sb += v * v;
+        sa += *reinterpret_cast<const f32x4*>(x + pix * ldx + q * 4);
     }, HW, Q, ch, parts);
 }
 
-// mean / rstd per (n, c) from the partials (fixed order, double)
+// first-pass mean per (n, c) from the partial sums of x (fixed order, double) -> stats[n][0][c]
+__global__ __launch_bounds__(256) void hin_mean_kernel(const float* __restrict__ parts, int nparts, int HW, int ch,
+                                                      float* __restrict__ stats) {
+    const int n = blockIdx.x;
+    for (int c = threadIdx.x; c < ch; c += 256) {
+        double s = 0.0;
+        for (int k = 0; k < nparts; ++k) s += parts[((long long)n * nparts + k) * 2 * ch + c];
+        stats[(long long)n * 2 * ch + c] = (float)(s / HW);
+    }
+}
+
+// second pass: A = sum d, B = sum d^2 with d = x - (first-pass mean).  The variance is formed from numbers of the size of the
+// deviations, never from E[x^2] - mean^2: a channel whose mean is many standard deviations from zero (ordinary for a conv
+// output) loses nothing to cancellation in the fp32 partials.
+__global__ __launch_bounds__(256) void hin_centred_stats_kernel(const float* __restrict__ x, int ldx,
+                                                               const float* __restrict__ stats, int HW, int Q, int ch,
+                                                               float* __restrict__ parts) {
+    const float* st = stats + (long long)blockIdx.y * 2 * ch;
+    part_sums([&](long long pix, int q, f32x4& sa, f32x4& sb) {
+        const f32x4 d = *reinterpret_cast<const f32x4*>(x + pix * ldx + q * 4) - *reinterpret_cast<const f32x4*>(st + q * 4);
+        sa += d; sb += d * d;
+    }, HW, Q, ch, parts);
+}
+
+// mean / rstd per (n, c) from the centred partials (fixed order, double): the mean is the first-pass mean m0 plus the mean of
+// the deviations (its rounding residue), the variance is taken about that corrected mean, sum d^2 / HW - (sum d / HW)^2.
 __global__ __launch_bounds__(256) void hin_finalize_kernel(const float* __restrict__ parts, int nparts, int HW, int ch,
                                                           float eps, float* __restrict__ stats) {
     const int n = blockIdx.x;
@@ -52,10 +76,12 @@ __global__ __launch_bounds__(256) void hin_finalize_kernel(const float* __restri
             const float* p = parts + ((long long)n * nparts + k) * 2 * ch;
             s += p[c]; s2 += p[ch + c];
         }
-        const double m = s / HW;
-        double var = s2 / HW - m * m;
+        const double dm = s / HW;
+        double var = s2 / HW - dm * dm;
+        // still live: on a constant channel d is the same rounding residue at every pixel, sum d^2 / HW and dm^2 are equal up
+        // to the rounding of the fp32 partials, and their difference can come out a few ulps below zero
         if (var < 0.0) var = 0.0;
-        stats[(long long)n * 2 * ch + c] = (float)m;
+        stats[(long long)n * 2 * ch + c] = (float)((double)stats[(long long)n * 2 * ch + c] + dm);
         stats[(long long)n * 2 * ch + ch + c] = (float)(1.0 / sqrt(var + (double)eps));
     }
 }
@@ -206,6 +232,10 @@ extern "C" int refid_hin_lrelu_fwd(const float* x, int ld_x, const float* gamma,
         const int np = refid_hin_parts(hw);
         hipLaunchKernelGGL(hin_stats_kernel, dim3(np, n), dim3(256), 0, st, x, ld_x, hw, ch / 4, ch, parts);
         REFID_LAUNCH_CHECK("hin_stats");
+        hipLaunchKernelGGL(hin_mean_kernel, dim3(n), dim3(256), 0, st, parts, np, hw, ch, stats);
+        REFID_LAUNCH_CHECK("hin_mean");
+        hipLaunchKernelGGL(hin_centred_stats_kernel, dim3(np, n), dim3(256), 0, st, x, ld_x, stats, hw, ch / 4, ch, parts);
+        REFID_LAUNCH_CHECK("hin_centred_stats");
         hipLaunchKernelGGL(hin_finalize_kernel, dim3(n), dim3(256), 0, st, parts, np, hw, ch, eps, stats);
         REFID_LAUNCH_CHECK("hin_finalize");
     }

@@ -851,15 +851,16 @@ def charbonnier(pred, gt, grad=None, eps=1e-12, grad_scale=None):
     return buf[:1]
 
 
-def psnr_loss(pred, gt, grad=None, weight=1.0):
-    """PSNRLoss (losses.py:95-120) of (B, ...) tensors; returns the 1-element double device tensor holding the loss."""
+def psnr_loss(pred, gt, grad=None, weight=1.0, want_sq=False):
+    """PSNRLoss (losses.py:95-120) of (B, ...) tensors; returns the 1-element double device tensor holding the loss
+    (want_sq: and the per-sample sums of squared differences, (B,) doubles)."""
     nb = pred.shape[0]
     per = pred.numel() // nb
     buf = torch.empty(nb + 1 + lib().refid_psnr_loss_parts(nb, per), dtype=torch.float64, device=pred.device)
     check(lib().refid_psnr_loss(_c(pred, "pred"), _c(gt, "gt"), grad.data_ptr() if grad is not None else None,
                                 buf.data_ptr(), buf[nb:].data_ptr(), buf[nb + 1:].data_ptr(), nb, per, weight, _stream()),
           "refid_psnr_loss")
-    return buf[nb:nb + 1]
+    return (buf[nb:nb + 1], buf[:nb]) if want_sq else buf[nb:nb + 1]
 
 
 SQNORM_WORDS = 2049
@@ -893,66 +894,75 @@ def clip_adamw_dev(p, g, m, v, sqnorm, hyper, *, max_norm, betas, eps, weight_de
 # ---------------------------------------------------------------------------------------------
 # SingleMultiConnectEVHINet non-GEMM pieces (csrc/evhinet.hip)
 # ---------------------------------------------------------------------------------------------
-def hin_lrelu_fwd(x, gamma, beta, slope=0.2, eps=1e-5):
+def hin_lrelu_fwd(x, gamma, beta, slope=0.2, eps=1e-5, out=None):
     """LeakyReLU([InstanceNorm(x[..., :ch]) * gamma + beta | x[..., ch:]]), ch = len(gamma) (None: plain LeakyReLU).
-    Returns (out, stats) with stats (n, 2, ch) = mean / rstd (None when ch == 0)."""
+    Returns (out, stats) with stats (n, 2, ch) = mean / rstd (None when ch == 0); `out` may be a channel slice."""
     px, ld = _nhwc(x, "x")
     n, h, w, c = x.shape
     ch = 0 if gamma is None else gamma.numel()
-    out = torch.empty((n, h, w, c), dtype=torch.float32, device=x.device)
+    if out is None:
+        out = torch.empty((n, h, w, c), dtype=torch.float32, device=x.device)
+    po, ldo = _nhwc(out, "out")
     stats = parts = None
     if ch:
         stats = torch.empty((n, 2, ch), dtype=torch.float32, device=x.device)
         parts = torch.empty((n, lib().refid_hin_parts(h * w), 2, ch), dtype=torch.float32, device=x.device)
     check(lib().refid_hin_lrelu_fwd(px, ld, _c(gamma, "gamma") if ch else None, _c(beta, "beta") if ch else None,
-                                    out.data_ptr(), c, stats.data_ptr() if ch else None,
+                                    po, ldo, stats.data_ptr() if ch else None,
                                     parts.data_ptr() if ch else None, n, h * w, c, ch, eps, slope, _stream()),
           "refid_hin_lrelu_fwd")
     return out, stats
 
 
-def hin_lrelu_bwd(g, out, x, gamma, stats, dgamma, dbeta, slope=0.2):
-    """Gradient w.r.t. x of hin_lrelu_fwd; dgamma / dbeta accumulate."""
+def hin_lrelu_bwd(g, out, x, gamma, stats, dgamma, dbeta, slope=0.2, gx=None):
+    """Gradient w.r.t. x of hin_lrelu_fwd; dgamma / dbeta accumulate; `gx` may be a channel slice."""
     pg, ldg = _nhwc(g, "g")
     po, ldo = _nhwc(out, "out")
     n, h, w, c = out.shape
     ch = 0 if gamma is None else gamma.numel()
-    gx = torch.empty((n, h, w, c), dtype=torch.float32, device=g.device)
+    if gx is None:
+        gx = torch.empty((n, h, w, c), dtype=torch.float32, device=g.device)
+    pgx, ldgx = _nhwc(gx, "gx")
     px, ldx = _nhwc(x, "x") if ch else (None, 0)
     sums = parts = None
     if ch:
         sums = torch.empty((n, 2, ch), dtype=torch.float32, device=g.device)
         parts = torch.empty((n, lib().refid_hin_parts(h * w), 2, ch), dtype=torch.float32, device=g.device)
     check(lib().refid_hin_lrelu_bwd(pg, ldg, po, ldo, px, ldx, _c(gamma, "gamma") if ch else None,
-                                    _c(stats, "stats") if ch else None, gx.data_ptr(), c,
+                                    _c(stats, "stats") if ch else None, pgx, ldgx,
                                     _c(dgamma, "dgamma") if ch else None, _c(dbeta, "dbeta") if ch else None,
                                     sums.data_ptr() if ch else None, parts.data_ptr() if ch else None, n, h * w, c, ch,
                                     slope, _stream()), "refid_hin_lrelu_bwd")
     return gx
 
 
-def fac_fwd(feat, filt):
+def fac_fwd(feat, filt, out=None):
     """FAC_bias: feat * filt[..., :C] + filt[..., C:]."""
     pf, ldf = _nhwc(feat, "feat")
     pi, ldi = _nhwc(filt, "filt")
     n, h, w, c = feat.shape
     if filt.shape[3] != 2 * c:
         raise _lib.RefidHipError(f"fac_fwd: filter has {filt.shape[3]} channels, expected {2 * c}")
-    out = torch.empty((n, h, w, c), dtype=torch.float32, device=feat.device)
-    check(lib().refid_fac_fwd(pf, ldf, pi, ldi, out.data_ptr(), c, n * h * w, c, _stream()), "refid_fac_fwd")
+    if out is None:
+        out = torch.empty((n, h, w, c), dtype=torch.float32, device=feat.device)
+    po, ldo = _nhwc(out, "out")
+    check(lib().refid_fac_fwd(pf, ldf, pi, ldi, po, ldo, n * h * w, c, _stream()), "refid_fac_fwd")
     return out
 
 
-def fac_bwd(g, feat, filt):
-    """Returns (g_feat, g_filt)."""
+def fac_bwd(g, feat, filt, gfeat=None, gfilt=None):
+    """Returns (g_feat, g_filt); either may be given as a channel slice of a wider buffer."""
     pg, ldg = _nhwc(g, "g")
     pf, ldf = _nhwc(feat, "feat")
     pi, ldi = _nhwc(filt, "filt")
     n, h, w, c = feat.shape
-    gfeat = torch.empty((n, h, w, c), dtype=torch.float32, device=g.device)
-    gfilt = torch.empty((n, h, w, 2 * c), dtype=torch.float32, device=g.device)
-    check(lib().refid_fac_bwd(pg, ldg, pf, ldf, pi, ldi, gfeat.data_ptr(), c, gfilt.data_ptr(), 2 * c, n * h * w, c,
-                              _stream()), "refid_fac_bwd")
+    if gfeat is None:
+        gfeat = torch.empty((n, h, w, c), dtype=torch.float32, device=g.device)
+    if gfilt is None:
+        gfilt = torch.empty((n, h, w, 2 * c), dtype=torch.float32, device=g.device)
+    pgf, ldgf = _nhwc(gfeat, "gfeat")
+    pgfi, ldgfi = _nhwc(gfilt, "gfilt")
+    check(lib().refid_fac_bwd(pg, ldg, pf, ldf, pi, ldi, pgf, ldgf, pgfi, ldgfi, n * h * w, c, _stream()), "refid_fac_bwd")
     return gfeat, gfilt
 
 
