@@ -40,6 +40,15 @@ __device__ __forceinline__ void lrelu4(f32x4& v, float slope, bool on) {
     }
 }
 
+// GELU (erf form) and its derivative Phi(x) + x phi(x): EGACA's activation (egaca.hip) and the pointwise tile's fused
+// second output / derivative mask (conv_epilogue.h)
+__device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752440f)); }
+__device__ __forceinline__ float gelu_d(float x) {
+    const float cdf = 0.5f * (1.f + erff(x * 0.70710678118654752440f));
+    const float pdf = 0.39894228040143267794f * __expf(-0.5f * x * x);
+    return cdf + x * pdf;
+}
+
 // Deterministic sum over the threads of a wave that share q = lane % LPP (LPP a power of two): fixed xor-shuffle tree;
 // the total ends up in every lane.  (Reductions of parameter gradients never use floating-point atomics: a step's
 // bits do not depend on arrival order.)

@@ -1,5 +1,6 @@
 // Kernel-side argument block shared by the conv tiles (direct implicit GEMM and Winograd).
 #pragma once
+#include <functional>
 
 struct ConvKArgs {
     const float* inA; const float* inB;
@@ -18,7 +19,6 @@ struct ConvKArgs {
     int bf16;                  // bf16 MFMA operands (packed weights are bf16), fp32 everything else
     int ksplit = 1;            // Winograd tile: K (input-channel chunk) ranges per output tile, grid.y (small grids)
     long long wsStride = 0;    // floats between the partial outputs of two K ranges
-    int gridTiles = 0;         // persistent Winograd tile: number of virtual blocks (XCD-aware tile enumeration)
     // second output: out2 = out + add2 (the skip sums the reference builds right after a conv -- arch:16-17,199-203,211 --
     // and their backward counterparts leave with the producing tile instead of a separate add kernel); NULL = off
     const float* add2 = nullptr; float* out2 = nullptr; int ldA2 = 0, ldO2 = 0;
@@ -33,10 +33,19 @@ struct ConvKArgs {
 
 
 // conv_wino.hip
+// Split-K of a small grid, shared by the fp32 Winograd, Winograd six-product and direct tiles.
+// K ranges per output tile: 512 / nwg, at most 8 and at most nchunks / div; 1 (no split) above wgLimit workgroups or below
+// minChunks K chunks
+int refid_splitk_count(int nwg, int nchunks, int wgLimit, int minChunks, int div);
+// bytes of ks partial outputs of npix pixels x cout channels (padded to 4); 0 for ks == 1
+size_t refid_splitk_bytes(int ks, long long npix, int cout);
+// One split launch: checks the caller's workspace, hands `partial` the arguments of the pass that writes ks raw partial outputs
+// into it (ksplit, wsStride, out = ws, no second output), then launches the pass that sums them and applies a's epilogue.
+int refid_launch_splitk(const char* tile, const ConvKArgs& a, int ks, long long npix, float* ws, size_t ws_bytes,
+                        const std::function<int(const ConvKArgs&)>& partial, hipStream_t st);
 // ws / ws_bytes: caller-provided split-K workspace (refid_wino3x3_workspace_bytes; NULL = never split)
 size_t refid_wino3x3_workspace_bytes(const ConvKArgs& a, int split_mode);
-int refid_launch_wino3x3(const ConvKArgs& a, float* ws, size_t ws_bytes, int split_mode, int tile_hint, hipStream_t st);
-int refid_launch_splitk_finish(const ConvKArgs& f, const float* ws, int ldW, long long npix, hipStream_t st);
+int refid_launch_wino3x3(const ConvKArgs& a, float* ws, size_t ws_bytes, int split_mode, hipStream_t st);
 // conv_wino6.hip: Winograd F(2x2,3x3) with six bf16 products per fp32 product (algo 5)
 bool refid_wino6_eligible(const ConvKArgs& a);
 size_t refid_wino6_workspace_bytes(const ConvKArgs& a, int split_mode);

@@ -32,6 +32,8 @@
 //     touched with 16-byte accesses.
 #include "common.h"
 #include "conv_args.h"
+#include "conv_epilogue.h"
+#include "conv_planes.h"
 
 namespace {
 
@@ -56,8 +58,6 @@ struct Cfg {
     static_assert(WM * WN == 4, "4 waves per workgroup");
     static_assert(256 % NQ == 0, "thread -> channel-quad mapping must be static");
 };
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 // BF = true: bf16 MFMA operands (v_mfma_f32_32x32x16_bf16), fp32 accumulate / epilogue / tensors.
 // A 16-byte LDS slot then holds 8 bf16 channels instead of 4 fp32 ones, so a K chunk is 16*NSUB
@@ -254,14 +254,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvKArgs a) {
             if (C::MODE == 1) { const int qd = j0 / Co1; ch = j0 - qd * Co1; sy = qd >> 1; sx = qd & 1; }
             if (C::MODE == 2) { sy = py; sx = px; }
             const bool vec = a.vecOK && (j0 + 3 < a.Cout);
-            f32x4 bv = {0.f, 0.f, 0.f, 0.f};
-            if (a.bias) {
-                const float* bp = a.bias + ((C::MODE == 1) ? ch : a.coBase + j0);
-                if (vec) bv = *reinterpret_cast<const f32x4*>(bp);
-                else
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) if (j0 + k < a.Cout) bv[k] = bp[k];
-            }
+            const f32x4 bv = epi_bias4(a, (C::MODE == 1) ? ch : a.coBase + j0, j0, vec);
 #pragma unroll
             for (int m = 0; m < C::MT; ++m) {
                 const int oy = oy0 + wm * C::MT + m;
@@ -270,38 +263,15 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvKArgs a) {
                 if (C::MODE == 0) op = (long long)(n * OH + oy) * OW + ox;
                 else op = (long long)(n * OH + 2 * oy + sy) * OW + 2 * ox + sx;
                 f32x4 v;
-                if (a.ksplit > 1) {          // raw partial sums (workspace in the OUTPUT's pixel / channel coordinates)
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) v[k] = acc[m][nn][4 * g + k];
+                for (int k = 0; k < 4; ++k) v[k] = acc[m][nn][4 * g + k];
+                if (a.ksplit > 1) {          // raw partial sums (workspace in the OUTPUT's pixel / channel coordinates)
                     *reinterpret_cast<f32x4*>(a.out + kpart * a.wsStride + op * a.ldO + ch) = v;
                     continue;
                 }
-#pragma unroll
-                for (int k = 0; k < 4; ++k) v[k] = lrelu(acc[m][nn][4 * g + k] + bv[k], a.slopePre);
-                if (vec) {
-                    if (a.res) v += *reinterpret_cast<const f32x4*>(a.res + op * a.ldR + ch);
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) v[k] = lrelu(v[k], a.slopePost);
-                    if (a.mask) {
-                        const f32x4 mv = *reinterpret_cast<const f32x4*>(a.mask + op * a.ldM + ch);
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) v[k] *= (mv[k] > 0.f) ? 1.f : a.slopeMask;
-                    }
-                    *reinterpret_cast<f32x4*>(a.out + op * a.ldO + ch) = v;
-                    if (a.out2)
-                        *reinterpret_cast<f32x4*>(a.out2 + op * a.ldO2 + ch) = v + *reinterpret_cast<const f32x4*>(a.add2 + op * a.ldA2 + ch);
-                } else {
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        if (j0 + k >= a.Cout) break;
-                        float t = v[k];
-                        if (a.res) t += a.res[op * a.ldR + ch + k];
-                        t = lrelu(t, a.slopePost);
-                        if (a.mask) t *= (a.mask[op * a.ldM + ch + k] > 0.f) ? 1.f : a.slopeMask;
-                        a.out[op * a.ldO + ch + k] = t;
-                        if (a.out2) a.out2[op * a.ldO2 + ch + k] = t + a.add2[op * a.ldA2 + ch + k];
-                    }
-                }
+                v += bv;
+                epi_pre(a, v);
+                epi_tail(a, v, j0, vec, EpiAtOp{op, ch});
             }
         }
     }
@@ -316,23 +286,16 @@ int igemm_ksplit(const ConvKArgs& a, int ncls, int split_mode, bool bf) {
     if (!split_mode || !(C::MODE == 0 || C::MODE == 2) || !a.vecOK || a.Cout % 4) return 1;
     const int tiles1 = cdiv(a.Wo, C::TW) * cdiv(a.Ho, C::TH);                  // per sample
     const int nwg = tiles1 * (split_mode == 2 ? a.N : 8) * cdiv(a.Cout, C::BN) * ncls;
-    const int nchunks = cdiv(a.Ctot, C::KC * (bf ? 2 : 1));
-    int ks = 1;
-    if (nwg <= 128 && nchunks >= 8) {          // (one workgroup per CU already: splitting then only adds the finishing pass)
-        ks = 512 / nwg;
-        if (ks > nchunks / 4) ks = nchunks / 4;
-        if (ks > 8) ks = 8;
-        if (ks < 1) ks = 1;
-    }
-    return ks;
+    // (above 128 workgroups there is one per CU already: splitting then only adds the finishing pass)
+    return refid_splitk_count(nwg, cdiv(a.Ctot, C::KC * (bf ? 2 : 1)), 128, 8, 4);
 }
 
 template <class C>
+long long igemm_opix(const ConvKArgs& a) { return (long long)a.N * a.Ho * a.Wo * (C::MODE == 2 ? 4 : 1); }
+
+template <class C>
 size_t igemm_ws_bytes(const ConvKArgs& a, int ncls, int split_mode, bool bf) {
-    const int ks = igemm_ksplit<C>(a, ncls, split_mode, bf);
-    if (ks == 1) return 0;
-    const long long opix = (long long)a.N * a.Ho * a.Wo * (C::MODE == 2 ? 4 : 1);
-    return (size_t)ks * opix * round_up(a.Cout, 4) * sizeof(float);
+    return refid_splitk_bytes(igemm_ksplit<C>(a, ncls, split_mode, bf), igemm_opix<C>(a), a.Cout);
 }
 
 template <class C, bool BF>
@@ -344,27 +307,16 @@ int launch_t(const ConvKArgs& ka, int ncls, const SplitArgs& sp, hipStream_t st)
     a.tilesY = cdiv(a.Ho, C::TH);
     a.nchunks = cdiv(a.Ctot, C::KC * (BF ? 2 : 1));
     const int ks = sp.ws ? igemm_ksplit<C>(a, ncls, sp.mode, BF) : 1;
-    dim3 grid(a.tilesX * a.tilesY * a.N * ks, cdiv(a.Cout, C::BN), ncls);
-    if (ks == 1) {
-        hipLaunchKernelGGL((conv_igemm_kernel<C, BF>), grid, dim3(256), C::LDS_BYTES, st, a);
-        REFID_LAUNCH_CHECK("conv_igemm");
+    const dim3 grid(a.tilesX * a.tilesY * a.N * ks, cdiv(a.Cout, C::BN), ncls);
+    auto run = [&](const ConvKArgs& k, const char* what) {
+        hipLaunchKernelGGL((conv_igemm_kernel<C, BF>), grid, dim3(256), C::LDS_BYTES, st, k);
+        REFID_LAUNCH_CHECK(what);
         return 0;
-    }
-    const long long opix = (long long)a.N * a.Ho * a.Wo * (C::MODE == 2 ? 4 : 1);
-    const int ldW = round_up(a.Cout, 4);
-    const size_t need = (size_t)ks * opix * ldW * sizeof(float);
-    if (need > sp.ws_bytes || (reinterpret_cast<uintptr_t>(sp.ws) & 15)) {
-        refid_set_error("conv_igemm: split-K workspace too small or misaligned (%zu bytes given, %zu needed: "
-                        "refid_conv_workspace_bytes)", sp.ws_bytes, need);
-        return 1;
-    }
-    ConvKArgs p = a;                       // partial pass: raw sums into the workspace (output coordinates)
-    p.ksplit = ks; p.wsStride = opix * ldW; p.out = sp.ws; p.ldO = ldW;
-    hipLaunchKernelGGL((conv_igemm_kernel<C, BF>), grid, dim3(256), C::LDS_BYTES, st, p);
-    REFID_LAUNCH_CHECK("conv_igemm/splitk");
-    ConvKArgs f = a;
-    f.ksplit = ks; f.wsStride = opix * ldW;
-    return refid_launch_splitk_finish(f, sp.ws, ldW, opix, st);
+    };
+    if (ks == 1) return run(a, "conv_igemm");
+    // (the partial outputs lie in the OUTPUT's pixel / channel coordinates)
+    return refid_launch_splitk("conv_igemm", a, ks, igemm_opix<C>(a), sp.ws, sp.ws_bytes,
+                               [&](const ConvKArgs& p) { return run(p, "conv_igemm/splitk"); }, st);
 }
 
 template <class C>
@@ -574,7 +526,7 @@ extern "C" int refid_conv2d(const refid_conv_desc* d, void* stream) {
         REFID_CHECK((long long)d->n * d->h * d->w * d->ld_a * 4 < lim &&
                         (d->c_b == 0 || (long long)d->n * d->h * d->w * d->ld_b * 4 < lim),
                     "conv2d: tensor too large for the Winograd tile's 32-bit offsets (use algo 0)");
-        return refid_launch_wino3x3(a, d->ws, d->ws_bytes, d->split_k, d->wino_tile, st);
+        return refid_launch_wino3x3(a, d->ws, d->ws_bytes, d->split_k, st);
     }
     switch (f) {
         case F_3x3:

@@ -24,42 +24,17 @@
 // engine keeps the fp32 form (this one is reached through the C ABI only).
 #include "common.h"
 #include "conv_args.h"
+#include "conv_epilogue.h"
+#include "conv_planes.h"
 #include <cstdlib>
 
 namespace {
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 constexpr int KC = 8;
 // the six products kept, largest first: (weight plane, activation plane)
 __device__ constexpr int PW_TA[6] = {0, 1, 0, 2, 0, 1};
 __device__ constexpr int PW_TB[6] = {0, 0, 1, 0, 2, 1};
-
-// v = h + m + l exactly (h = rne(v), m = rne(v - h), l = v - h - m), eight values -> three bf16x8 planes
-__device__ __forceinline__ void pw_split8(const f32x4& v0, const f32x4& v1, f32x4 (&pl)[3]) {
-    bf16x8 p0, p1, p2;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const float v = k < 4 ? v0[k] : v1[k - 4];
-        const __bf16 h = (__bf16)v;
-        p0[k] = h;
-        const float r = v - (float)h;
-        const __bf16 m = (__bf16)r;
-        p1[k] = m;
-        p2[k] = (__bf16)(r - (float)m);
-    }
-    pl[0] = __builtin_bit_cast(f32x4, p0);
-    pl[1] = __builtin_bit_cast(f32x4, p1);
-    pl[2] = __builtin_bit_cast(f32x4, p2);
-}
-constexpr int OOB = -1;
-
-__device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752440f)); }
-__device__ __forceinline__ float gelu_erf_d(float x) {      // d/dx GELU_erf = Phi(x) + x phi(x)   (as egaca.hip::gelu_d)
-    const float cdf = 0.5f * (1.f + erff(x * 0.70710678118654752440f));
-    const float pdf = 0.39894228040143267794f * __expf(-0.5f * x * x);
-    return cdf + x * pdf;
-}
 
 // NT: 32-channel column tiles per wave (Cout tile = 32*NT); XD: activation prefetch depth; EX: the EGACA fusions of
 // PwExtra are compiled in (fusion_modules.py:290-333):
@@ -137,7 +112,7 @@ __global__ __launch_bounds__(256, (SIX || NT > 2) ? 3 : 4) void conv_pw_kernel(c
     };
     auto mfma6 = [&](const f32x4& x0, const f32x4& x1, const f32x4 (&w6)[3][NT]) {
         f32x4 pl[3];
-        pw_split8(x0, x1, pl);
+        split8<3>(x0, x1, pl);
 #pragma unroll
         for (int t = 0; t < 6; ++t)
 #pragma unroll
@@ -313,38 +288,22 @@ __global__ __launch_bounds__(256, (SIX || NT > 2) ? 3 : 4) void conv_pw_kernel(c
                     const unsigned qd = (unsigned)j0 / (unsigned)Co1, ch = (unsigned)j0 - qd * Co1;
                     const unsigned up = (unsigned)pp, row = up / (unsigned)a.W, x = up - row * a.W;   // row = n H + y
                     const long long op = (long long)(2 * row + (qd >> 1)) * (2 * a.W) + 2 * x + (qd & 1);
-                    if (a.bias) v += *reinterpret_cast<const f32x4*>(a.bias + ch);
-                    lrelu4(v, a.slopePre, a.slopePre != 1.f);
-                    if (a.res) v += *reinterpret_cast<const f32x4*>(a.res + op * a.ldR + ch);
-                    lrelu4(v, a.slopePost, a.slopePost != 1.f);
-                    *reinterpret_cast<f32x4*>(a.out + op * a.ldO + ch) = v;
+                    // (the host admits no mask / second output here: bias per real channel, pre, + res, post, store)
+                    conv_epilogue(a, v, ch, j0, true, EpiAtOp{op, (int)ch}, false);
                     continue;
                 }
-                if (a.bias) v += *reinterpret_cast<const f32x4*>(a.bias + a.coBase + j0);
-                lrelu4(v, a.slopePre, a.slopePre != 1.f);
-                if (a.res) v += *reinterpret_cast<const f32x4*>(a.res + pp * a.ldR + j0);
+                // maskMode 1: the GELU backward fused into conv5's input gradient; the skip sum out2 leaves with the tile; EGACA's
+                // second residual (y = ev + img + beta conv3(.)) joins before `post`.  No zero bias quad on this 16-byte path.
+                const float* res2 = nullptr;
                 if constexpr (EX) {
-                    if (e.res2) v += *reinterpret_cast<const f32x4*>(e.res2 + pp * e.ldR2 + j0);
+                    if (e.res2) res2 = e.res2 + pp * e.ldR2 + j0;
                 }
-                lrelu4(v, a.slopePost, a.slopePost != 1.f);
-                if (a.mask) {
-                    const f32x4 mv = *reinterpret_cast<const f32x4*>(a.mask + pp * a.ldM + j0);
-                    if (a.maskMode == 1) {                  // (workgroup-uniform) GELU backward fused into conv5's input gradient
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) v[k] *= gelu_erf_d(mv[k]);
-                    } else {
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) v[k] *= (mv[k] > 0.f) ? 1.f : a.slopeMask;
-                    }
-                }
-                *reinterpret_cast<f32x4*>(a.out + pp * a.ldO + j0) = v;
-                if (a.out2)                                  // (workgroup-uniform) the skip sum leaves with the tile
-                    *reinterpret_cast<f32x4*>(a.out2 + pp * a.ldO2 + j0) = v + *reinterpret_cast<const f32x4*>(a.add2 + pp * a.ldA2 + j0);
+                conv_epilogue<true>(a, v, a.coBase + j0, j0, true, EpiAtOp{pp, j0}, false, res2);
                 if constexpr (EX) {
                     if (e.out2) {
                         f32x4 gl;
 #pragma unroll
-                        for (int k = 0; k < 4; ++k) gl[k] = gelu_erf(v[k]);
+                        for (int k = 0; k < 4; ++k) gl[k] = gelu_f(v[k]);
                         *reinterpret_cast<f32x4*>(e.out2 + pp * e.ldO2 + j0) = gl;
                     }
                 }
@@ -359,16 +318,10 @@ __global__ __launch_bounds__(256, (SIX || NT > 2) ? 3 : 4) void conv_pw_kernel(c
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             const int j0 = n0 + nt * 32 + 8 * g + 4 * kh;
+            f32x4 v;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (j0 + k >= a.Cout) break;
-                float tv = acc[nt][4 * g + k] + (a.bias ? a.bias[a.coBase + j0 + k] : 0.f);
-                tv = lrelu(tv, a.slopePre);
-                if (a.res) tv += a.res[p * a.ldR + j0 + k];
-                tv = lrelu(tv, a.slopePost);
-                if (a.mask) tv *= a.maskMode == 1 ? gelu_erf_d(a.mask[p * a.ldM + j0 + k]) : ((a.mask[p * a.ldM + j0 + k] > 0.f) ? 1.f : a.slopeMask);
-                a.out[p * a.ldO + j0 + k] = tv;
-            }
+            for (int k = 0; k < 4; ++k) v[k] = acc[nt][4 * g + k];
+            conv_epilogue<true>(a, v, a.coBase + j0, j0, false, EpiAtOp{p, j0});
         }
     }
 }

@@ -52,6 +52,8 @@
 //     bias / residual / mask load and the store is a contiguous 1 KB per wave instruction.
 #include "common.h"
 #include "conv_args.h"
+#include "conv_epilogue.h"
+#include "conv_planes.h"
 
 // tools/probes/split_ablate.py builds this file with -DREFID_SPLIT_ABLATE=n (one piece of the kernel removed, results wrong) to
 // price the pieces: 1 = no MFMAs, 2 = no operand split (raw registers stored as planes), 3 = global loads of chunk 0 in every
@@ -63,18 +65,13 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-constexpr int F16_TGT = 8;              // a freshly scaled stage's largest |x| lands in [2^8, 2^9)
+constexpr int F16_TGT = 8;             // a freshly scaled stage's largest |x| lands in [2^8, 2^9)
 constexpr int F16_SLACK = 6;            // binades a later stage may exceed the reference before the accumulators are rescaled
 constexpr int F16_E0 = F16_TGT + 1;     // initial (biased) reference exponent: any real data is larger
 constexpr int F16_HEADER = 64;          // bytes in front of the fp16 planes: int eW (runtime.hip)
 constexpr int TW = 32;                  // output pixels per tile row
 constexpr int KC = 8;                   // input channels per chunk (x 2 taps = K of one bf16 MFMA)
 constexpr int NTH = 256;
-constexpr int OOB = -1;                 // voffset 0xFFFFFFFF: buffer loads return 0 (hardware range check)
 __device__ __forceinline__ int cdiv_dev(int a, int b) { return (a + b - 1) / b; }
 
 // tools/probes/split_trace.py builds this file with -DREFID_SPLIT_TRACE: every workgroup stamps the 100 MHz wall clock
@@ -125,43 +122,6 @@ struct SCfg {
     static constexpr int LDS_EPI = 4 * 32 * XS * 16;
     static constexpr int LDS_BYTES = LDS_LOOP > LDS_EPI ? LDS_LOOP : LDS_EPI;
 };
-
-// v (8 fp32 channels) -> PL bf16 planes; the planes sum to v exactly for PL = 3 and to 2^-17 |v| for PL = 2
-template <int PL>
-__device__ __forceinline__ void split8(const f32x4& v0, const f32x4& v1, f32x4 (&pl)[PL]) {
-    bf16x8 p0, p1, p2;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const float v = k < 4 ? v0[k] : v1[k - 4];
-        const __bf16 h = (__bf16)v;
-        p0[k] = h;
-        if (PL >= 2) {
-            const float r = v - (float)h;
-            const __bf16 m = (__bf16)r;
-            p1[k] = m;
-            if (PL == 3) p2[k] = (__bf16)(r - (float)m);
-        }
-    }
-    pl[0] = __builtin_bit_cast(f32x4, p0);
-    if constexpr (PL >= 2) pl[1] = __builtin_bit_cast(f32x4, p1);
-    if constexpr (PL == 3) pl[2] = __builtin_bit_cast(f32x4, p2);
-}
-
-// v (8 fp32 channels, scaled into fp16's range) -> two fp16 planes, h + l = v to 22 bits
-__device__ __forceinline__ void split8h(const f32x4& v0, const f32x4& v1, f32x4 (&pl)[2]) {
-    f16x8 h, l;
-#pragma unroll
-    for (int k = 0; k < 8; k += 2) {
-        const f32x2 ab = {k < 4 ? v0[k] : v1[k - 4], k < 4 ? v0[k + 1] : v1[k - 3]};
-        const f16x2 hh = __builtin_convertvector(ab, f16x2);
-        const f32x2 r = ab - __builtin_convertvector(hh, f32x2);
-        const f16x2 ll = __builtin_convertvector(r, f16x2);
-        h[k] = hh[0]; h[k + 1] = hh[1];
-        l[k] = ll[0]; l[k + 1] = ll[1];
-    }
-    pl[0] = __builtin_bit_cast(f32x4, h);
-    pl[1] = __builtin_bit_cast(f32x4, l);
-}
 
 template <int MT, int NT, int PL, int KS, int MODE, bool F16 = false>
 __global__ __launch_bounds__(NTH, 2) void conv_split_kernel(const ConvKArgs a) {
@@ -490,41 +450,13 @@ __global__ __launch_bounds__(NTH, 2) void conv_split_kernel(const ConvKArgs a) {
             if (oy >= a.Ho || ox >= a.Wo || j0 >= a.Cout) continue;
             const long long op = opix(oy, ox);
             const bool vec = a.vecOK && (j0 + 3 < a.Cout);
-            f32x4 bv = {0.f, 0.f, 0.f, 0.f};
-            if (a.bias) {
-                const float* bp = a.bias + a.coBase + j0;
-                if (vec) bv = *reinterpret_cast<const f32x4*>(bp);
-                else
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) if (j0 + k < a.Cout) bv[k] = bp[k];
-            }
-            v += bv;
-            lrelu4(v, a.slopePre, a.slopePre != 1.f);
+            v += epi_bias4(a, a.coBase + j0, j0, vec);
+            epi_pre(a, v);
             if (REFID_SPLIT_ABLATE == 6 || REFID_SPLIT_ABLATE == 7) {
                 if (v[0] == 12345.678f) a.out[op * a.ldO + j0] = v[1];
                 continue;
             }
-            if (vec) {
-                if (a.res) v += pres[it];
-                lrelu4(v, a.slopePost, a.slopePost != 1.f);
-                if (a.mask) {
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) v[k] *= (pmask[it][k] > 0.f) ? 1.f : a.slopeMask;
-                }
-                *reinterpret_cast<f32x4*>(a.out + op * a.ldO + j0) = v;
-                if (a.out2) *reinterpret_cast<f32x4*>(a.out2 + op * a.ldO2 + j0) = v + *reinterpret_cast<const f32x4*>(a.add2 + op * a.ldA2 + j0);
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    if (j0 + k >= a.Cout) break;
-                    float tv = v[k];
-                    if (a.res) tv += a.res[op * a.ldR + j0 + k];
-                    tv = lrelu(tv, a.slopePost);
-                    if (a.mask) tv *= (a.mask[op * a.ldM + j0 + k] > 0.f) ? 1.f : a.slopeMask;
-                    a.out[op * a.ldO + j0 + k] = tv;
-                    if (a.out2) a.out2[op * a.ldO2 + j0 + k] = tv + a.add2[op * a.ldA2 + j0 + k];
-                }
-            }
+            epi_tail(a, v, j0, vec, EpiAtOp{op, j0}, true, pres[it], pmask[it]);     // (vec: the quad's residual / mask are in pres / pmask)
         }
     }
     SPLIT_STAMP(3);

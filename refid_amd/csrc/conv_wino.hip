@@ -33,7 +33,8 @@
 //     tile with the fused 16-byte epilogue.
 #include "common.h"
 #include "conv_args.h"
-#include <cstdlib>
+#include "conv_epilogue.h"
+#include "conv_planes.h"
 
 namespace {
 
@@ -41,8 +42,6 @@ constexpr int TW = 32;                  // output pixels per workgroup row
 constexpr int KC = 8;                   // input channels per chunk
 constexpr int HWD = TW + 2;
 constexpr int LDS_BYTES = 64 * 66 * 16;   // 2 raw buffers (13-22 KB) in the K loop; 66 KB row exchange afterwards
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-constexpr int OOB = -1;                 // voffset 0xFFFFFFFF: buffer loads return 0 (hardware range check)
 
 // tools/probes/wino_trace.py builds this file with -DREFID_WINO_TRACE: every workgroup records wall-clock stamps
 // (100 MHz) at its phase boundaries + the CU it ran on, to see where a tile's time goes.  Never in the product build.
@@ -322,38 +321,9 @@ __global__ __launch_bounds__(256, 2) void conv_wino_kernel(const ConvKArgs a) {
             continue;
         }
         const bool vec = a.vecOK && (j0 + 3 < a.Cout);
-        f32x4 bv = {0.f, 0.f, 0.f, 0.f};
-        if (a.bias) {
-            const float* bp = a.bias + a.coBase + j0;
-            if (vec) bv = *reinterpret_cast<const f32x4*>(bp);
-            else
-#pragma unroll
-                for (int k = 0; k < 4; ++k) if (j0 + k < a.Cout) bv[k] = bp[k];
-        }
-        v += bv;
-        lrelu4(v, a.slopePre, a.slopePre != 1.f);
-        if (vec) {
-            if (a.res) v += pre ? pres[it] : *reinterpret_cast<const f32x4*>(a.res + op * a.ldR + j0);
-            lrelu4(v, a.slopePost, a.slopePost != 1.f);
-            if (a.mask) {
-                const f32x4 mv = pre ? pmask[it] : *reinterpret_cast<const f32x4*>(a.mask + op * a.ldM + j0);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) v[k] *= (mv[k] > 0.f) ? 1.f : a.slopeMask;
-            }
-            *reinterpret_cast<f32x4*>(a.out + op * a.ldO + j0) = v;
-            if (a.out2) *reinterpret_cast<f32x4*>(a.out2 + op * a.ldO2 + j0) = v + *reinterpret_cast<const f32x4*>(a.add2 + op * a.ldA2 + j0);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (j0 + k >= a.Cout) break;
-                float tv = v[k];
-                if (a.res) tv += a.res[op * a.ldR + j0 + k];
-                tv = lrelu(tv, a.slopePost);
-                if (a.mask) tv *= (a.mask[op * a.ldM + j0 + k] > 0.f) ? 1.f : a.slopeMask;
-                a.out[op * a.ldO + j0 + k] = tv;
-                if (a.out2) a.out2[op * a.ldO2 + j0 + k] = tv + a.add2[op * a.ldA2 + j0 + k];
-            }
-        }
+        v += epi_bias4(a, a.coBase + j0, j0, vec);
+        epi_pre(a, v);
+        epi_tail(a, v, j0, vec, EpiAtOp{op, j0}, pre, pres[it], pmask[it]);
     }
     WINO_STAMP(4);
 }
@@ -367,37 +337,11 @@ __global__ __launch_bounds__(256) void wino_splitk_finish_kernel(const ConvKArgs
         const int j0 = (int)(e % C4) * 4;
         f32x4 v = *reinterpret_cast<const f32x4*>(ws + op * ldW + j0);
         for (int s = 1; s < a.ksplit; ++s) v += *reinterpret_cast<const f32x4*>(ws + s * a.wsStride + op * ldW + j0);
-        if (a.vecOK && j0 + 3 < a.Cout) {
-            if (a.bias) v += *reinterpret_cast<const f32x4*>(a.bias + a.coBase + j0);
-            lrelu4(v, a.slopePre, a.slopePre != 1.f);
-            if (a.res) v += *reinterpret_cast<const f32x4*>(a.res + op * a.ldR + j0);
-            lrelu4(v, a.slopePost, a.slopePost != 1.f);
-            if (a.mask) {
-                const f32x4 mv = *reinterpret_cast<const f32x4*>(a.mask + op * a.ldM + j0);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) v[k] *= (mv[k] > 0.f) ? 1.f : a.slopeMask;
-            }
-            *reinterpret_cast<f32x4*>(a.out + op * a.ldO + j0) = v;
-            if (a.out2) *reinterpret_cast<f32x4*>(a.out2 + op * a.ldO2 + j0) = v + *reinterpret_cast<const f32x4*>(a.add2 + op * a.ldA2 + j0);
-            continue;
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (j0 + k >= a.Cout) break;
-            float t = v[k] + (a.bias ? a.bias[a.coBase + j0 + k] : 0.f);
-            t = lrelu(t, a.slopePre);
-            if (a.res) t += a.res[op * a.ldR + j0 + k];
-            t = lrelu(t, a.slopePost);
-            if (a.mask) t *= (a.mask[op * a.ldM + j0 + k] > 0.f) ? 1.f : a.slopeMask;
-            a.out[op * a.ldO + j0 + k] = t;
-            if (a.out2) a.out2[op * a.ldO2 + j0 + k] = t + a.add2[op * a.ldA2 + j0 + k];
-        }
+        // (this kernel's 16-byte path has never added a zero bias quad; kept: x + 0 and x differ for x = -0)
+        conv_epilogue(a, v, a.coBase + j0, j0, a.vecOK && j0 + 3 < a.Cout, EpiAtOp{op, j0}, false);
     }
 }
 
-}  // namespace
-
-namespace {
 // Small problems (deep levels, small batches) leave most of the 256 CUs idle with one long K loop per workgroup:
 // split K over grid.y into a partial-sum workspace and finish with a streaming epilogue kernel.
 //   split_mode 1 ("sample"): the split depends on the per-sample geometry only, so a sample's result is bit-identical
@@ -416,14 +360,7 @@ WinoPlan wino_plan(ConvKArgs& a, int split_mode) {
     a.ncot = cdiv(a.Cout, p.bn);
     p.grid = dim3(round_up(a.tilesX * a.tilesY * a.N, 8) * a.ncot);
     const int nwg = (split_mode == 2) ? (int)p.grid.x : a.tilesX * a.tilesY * a.ncot * 8;   // "sample": as if N = 8
-    int ks = 1;
-    if (split_mode && nwg <= 256 && a.nchunks >= 16) {
-        ks = 512 / nwg;
-        if (ks > a.nchunks / 8) ks = a.nchunks / 8;
-        if (ks > 8) ks = 8;
-        if (ks < 1) ks = 1;
-    }
-    p.ks = ks;
+    p.ks = split_mode ? refid_splitk_count(nwg, a.nchunks, 256, 16, 8) : 1;
     return p;
 }
 }  // namespace
@@ -438,16 +375,35 @@ extern "C" int refid_wino_ktrace_set(unsigned long long* buf, int wg) {
 }
 #endif
 
-size_t refid_wino3x3_workspace_bytes(const ConvKArgs& ka, int split_mode) {
-    ConvKArgs a = ka;
-    const WinoPlan p = wino_plan(a, split_mode);
-    if (p.ks == 1) return 0;
-    return (size_t)p.ks * a.N * a.Ho * a.Wo * round_up(a.Cout, 4) * sizeof(float);
+// ---- split-K of a small grid: the one host sequence of the fp32 Winograd, Winograd six-product and direct tiles ------------
+int refid_splitk_count(int nwg, int nchunks, int wgLimit, int minChunks, int div) {
+    if (nwg > wgLimit || nchunks < minChunks) return 1;
+    int ks = 512 / nwg;
+    if (ks > nchunks / div) ks = nchunks / div;
+    if (ks > 8) ks = 8;
+    return ks < 1 ? 1 : ks;
 }
 
-// Generic finishing pass of a split-K launch (also used by the direct tile): out = epilogue(sum_s ws[s]) over an
-// output of npix pixels x a.Cout channels (a.out / ldO / res / mask / bias describe the final tensor).
-int refid_launch_splitk_finish(const ConvKArgs& f, const float* ws, int ldW, long long npix, hipStream_t st) {
+size_t refid_splitk_bytes(int ks, long long npix, int cout) {
+    return ks == 1 ? 0 : (size_t)ks * npix * round_up(cout, 4) * sizeof(float);
+}
+
+int refid_launch_splitk(const char* tile, const ConvKArgs& a, int ks, long long npix, float* ws, size_t ws_bytes,
+                        const std::function<int(const ConvKArgs&)>& partial, hipStream_t st) {
+    const int ldW = round_up(a.Cout, 4);
+    const size_t need = refid_splitk_bytes(ks, npix, a.Cout);
+    if (need > ws_bytes || (reinterpret_cast<uintptr_t>(ws) & 15)) {
+        refid_set_error("%s: split-K workspace too small or misaligned (%zu bytes given, %zu needed: "
+                        "refid_conv_workspace_bytes)", tile, ws_bytes, need);
+        return 1;
+    }
+    ConvKArgs p = a;                       // partial pass: raw sums into the workspace (the finishing pass writes out / out2)
+    p.ksplit = ks; p.wsStride = npix * ldW; p.out = ws; p.ldO = ldW; p.out2 = nullptr;
+    if (int rc = partial(p)) return rc;
+    // finishing pass: out = epilogue(sum_s ws[s]) over npix pixels x a.Cout channels (a.out / ldO / res / mask / bias describe
+    // the final tensor)
+    ConvKArgs f = a;
+    f.ksplit = ks; f.wsStride = npix * ldW;
     const long long tot4 = npix * (ldW / 4);
     int nb = (int)((tot4 + 255) / 256);
     if (nb > 2048) nb = 2048;
@@ -456,55 +412,30 @@ int refid_launch_splitk_finish(const ConvKArgs& f, const float* ws, int ldW, lon
     return 0;
 }
 
-namespace {
-// CU count per device (persistent-tile grid size); 0 = query failed -> the persistent tile is not used
-int device_cus() {
-    static std::atomic<int> cus[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 63) return 0;
-    int c = cus[dev].load(std::memory_order_relaxed);
-    if (c == 0) {
-        if (hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) c = -1;
-        cus[dev].store(c, std::memory_order_relaxed);
-    }
-    return c > 0 ? c : 0;
-}
-}  // namespace
-
-int refid_launch_wino3x3(const ConvKArgs& ka, float* ws, size_t ws_bytes, int split_mode, int tile_hint, hipStream_t st) {
+size_t refid_wino3x3_workspace_bytes(const ConvKArgs& ka, int split_mode) {
     ConvKArgs a = ka;
-    // (tile_hint 2 once selected a persistent one-wave-per-SIMD tile: measured 10-30 % slower at every config-2 shape -- a
-    //  lone wave per SIMD pays ~130 cycles per buffer-load issue and every LDS / barrier stall itself; two co-resident
+    const WinoPlan p = wino_plan(a, split_mode);
+    return refid_splitk_bytes(p.ks, (long long)a.N * a.Ho * a.Wo, a.Cout);
+}
+
+int refid_launch_wino3x3(const ConvKArgs& ka, float* ws, size_t ws_bytes, int split_mode, hipStream_t st) {
+    ConvKArgs a = ka;
+    // (refid_conv_desc.wino_tile 2 once selected a persistent one-wave-per-SIMD tile: measured 10-30 % slower at every config-2
+    //  shape -- a lone wave per SIMD pays ~130 cycles per buffer-load issue and every LDS / barrier stall itself; two co-resident
     //  workgroups hide exactly that, DESIGN.md section 7, profiles/r02_wino_* -- and was removed in round 6)
     // no workspace from the caller = no split (still correct, one K loop per workgroup)
     const WinoPlan pl = wino_plan(a, ws ? split_mode : 0);
-    const bool narrow = a.Cout <= 32;
-    dim3 grid = pl.grid;
     static std::atomic<unsigned long long> done12{0}, done21{0};
     if (int rc = refid_lds_attr_once(done12, &conv_wino_kernel<1, 2>, LDS_BYTES, "conv_wino")) return rc;
     if (int rc = refid_lds_attr_once(done21, &conv_wino_kernel<2, 1>, LDS_BYTES, "conv_wino")) return rc;
-    const int ks = pl.ks;
-    if (ks == 1) {
-        if (narrow) hipLaunchKernelGGL((conv_wino_kernel<1, 2>), grid, dim3(256), LDS_BYTES, st, a);
-        else hipLaunchKernelGGL((conv_wino_kernel<2, 1>), grid, dim3(256), LDS_BYTES, st, a);
-        REFID_LAUNCH_CHECK("conv_wino");
+    auto launch = [&](const ConvKArgs& k, const char* what) {
+        const dim3 grid(pl.grid.x, k.ksplit);
+        if (a.Cout <= 32) hipLaunchKernelGGL((conv_wino_kernel<1, 2>), grid, dim3(256), LDS_BYTES, st, k);
+        else hipLaunchKernelGGL((conv_wino_kernel<2, 1>), grid, dim3(256), LDS_BYTES, st, k);
+        REFID_LAUNCH_CHECK(what);
         return 0;
-    }
-    const long long npix = (long long)a.N * a.Ho * a.Wo;
-    const int ldW = round_up(a.Cout, 4);
-    const size_t need = (size_t)ks * npix * ldW * sizeof(float);
-    if (need > ws_bytes || (reinterpret_cast<uintptr_t>(ws) & 15)) {
-        refid_set_error("conv_wino: split-K workspace too small or misaligned (%zu bytes given, %zu needed: "
-                        "refid_conv_workspace_bytes)", ws_bytes, need);
-        return 1;
-    }
-    ConvKArgs p = a;                       // partial pass: raw sums into the workspace
-    p.ksplit = ks; p.wsStride = npix * ldW; p.out = ws; p.ldO = ldW;
-    grid.y = ks;
-    if (narrow) hipLaunchKernelGGL((conv_wino_kernel<1, 2>), grid, dim3(256), LDS_BYTES, st, p);
-    else hipLaunchKernelGGL((conv_wino_kernel<2, 1>), grid, dim3(256), LDS_BYTES, st, p);
-    REFID_LAUNCH_CHECK("conv_wino/splitk");
-    ConvKArgs f = a;
-    f.ksplit = ks; f.wsStride = npix * ldW;
-    return refid_launch_splitk_finish(f, ws, ldW, npix, st);
+    };
+    if (pl.ks == 1) return launch(a, "conv_wino");
+    return refid_launch_splitk("conv_wino", a, pl.ks, (long long)a.N * a.Ho * a.Wo, ws, ws_bytes,
+                               [&](const ConvKArgs& p) { return launch(p, "conv_wino/splitk"); }, st);
 }

@@ -51,6 +51,8 @@
 //   * the raw halo of chunk c+2 is requested at the top of chunk c (global -> VGPR -> LDS, double buffered).
 #include "common.h"
 #include "conv_args.h"
+#include "conv_epilogue.h"
+#include "conv_planes.h"
 #include <algorithm>
 #include <cstdlib>
 
@@ -71,61 +73,10 @@ constexpr int HP = (TH + 2) * HWD;      // 204 halo pixels
 constexpr int R_ITEMS = (4 * HP + 255) / 256;
 // 2 raw buffers (31 KB) in the K loop; afterwards the row exchange: 66 KB for 64 output channels, 33 KB for 32
 constexpr int lds_bytes(int nt) { return nt == 2 ? 64 * 66 * 16 : (32 * 66 * 16 > 2 * R_F4 * 16 ? 32 * 66 * 16 : 2 * R_F4 * 16); }
-constexpr int OOB = -1;                 // voffset 0xFFFFFFFF: buffer loads return 0 (hardware range check)
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 constexpr int W3H_HEADER = 64;          // bytes in front of the fp16 planes: int eU (runtime.hip)
 constexpr int F16_TGT = 7;              // a freshly scaled chunk's largest |B^T d| lands in [2^7, 2^8)
 constexpr int F16_SLACK = 6;            // binades the largest value may grow over the reference before the accumulators are rescaled
 constexpr int F16_E0 = F16_TGT + 1;     // initial (biased) reference exponent: any real data is larger
-
-// v (8 fp32 channels) -> three bf16 planes that sum to v exactly
-__device__ __forceinline__ void split8(const f32x4& v0, const f32x4& v1, f32x4 (&pl)[3]) {
-    bf16x8 p0, p1, p2;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const float v = k < 4 ? v0[k] : v1[k - 4];
-        const __bf16 h = (__bf16)v;
-        p0[k] = h;
-        const float r = v - (float)h;
-        const __bf16 m = (__bf16)r;
-        p1[k] = m;
-        p2[k] = (__bf16)(r - (float)m);
-    }
-    pl[0] = __builtin_bit_cast(f32x4, p0);
-    pl[1] = __builtin_bit_cast(f32x4, p1);
-    pl[2] = __builtin_bit_cast(f32x4, p2);
-}
-
-// v (8 fp32 channels, already scaled into fp16's range) -> two fp16 planes, h + l = v to 22 bits (20 VALU)
-__device__ __forceinline__ void split8h(const f32x4& v0, const f32x4& v1, f32x4 (&pl)[3]) {
-    f16x8 h, l;
-#pragma unroll
-    for (int k = 0; k < 8; k += 2) {
-        const f32x2 ab = {k < 4 ? v0[k] : v1[k - 4], k < 4 ? v0[k + 1] : v1[k - 3]};
-        const f16x2 hh = __builtin_convertvector(ab, f16x2);                  // v_cvt_pk_f16_f32 (RNE)
-        const f32x2 r = ab - __builtin_convertvector(hh, f32x2);              // exact
-        const f16x2 ll = __builtin_convertvector(r, f16x2);
-        h[k] = hh[0]; h[k + 1] = hh[1];
-        l[k] = ll[0]; l[k + 1] = ll[1];
-    }
-    pl[0] = __builtin_bit_cast(f32x4, h);
-    pl[1] = __builtin_bit_cast(f32x4, l);
-}
-
-// v (8 fp32 channels, already scaled into fp16's range) -> ONE fp16 plane, rounded to nearest even (4 VALU)
-__device__ __forceinline__ void round8h(const f32x4& v0, const f32x4& v1, f32x4 (&pl)[3]) {
-    f16x8 h;
-#pragma unroll
-    for (int k = 0; k < 8; k += 2) {
-        const f32x2 ab = {k < 4 ? v0[k] : v1[k - 4], k < 4 ? v0[k + 1] : v1[k - 3]};
-        const f16x2 hh = __builtin_convertvector(ab, f16x2);                  // v_cvt_pk_f16_f32 (RNE)
-        h[k] = hh[0]; h[k + 1] = hh[1];
-    }
-    pl[0] = __builtin_bit_cast(f32x4, h);
-}
 
 // NT = 2: 64 output channels per workgroup (8 accumulators per wave, two workgroups per CU).
 // NT = 1: the 32-output-channel layers (decoder 2's trunk, the input gradient of level 0's first conv; round 4 -- they ran
@@ -336,7 +287,7 @@ __global__ __launch_bounds__(256, NT == 2 ? 2 : 3) void conv_wino6_kernel(const 
             else if (F16 && REFID_WINO6_ABLATE == 18) { pl[0] = v[0]; pl[1] = v[1]; }
             else if constexpr (ONE) round8h(v[0], v[1], pl);
             else if constexpr (F16) split8h(v[0], v[1], pl);
-            else split8(v[0], v[1], pl);
+            else split8<3>(v[0], v[1], pl);
 #pragma unroll
             for (int e = 0; e < NPR; ++e)
 #pragma unroll
@@ -422,15 +373,9 @@ __global__ __launch_bounds__(256, NT == 2 ? 2 : 3) void conv_wino6_kernel(const 
     bool cok[CPR];
 #pragma unroll
     for (int q2 = 0; q2 < CPR; ++q2) cok[q2] = ox0 + q2 * PPT + p0 < a.Wo;
-    float* const outB = a.out + (a.ksplit > 1 ? blockIdx.y * a.wsStride : 0) + opb * a.ldO + j0;
-    const float* const resB = a.res ? a.res + opb * a.ldR + j0 : nullptr;
-    const float* const mskB = a.mask ? a.mask + opb * a.ldM + j0 : nullptr;
-    const int stepO[2] = {a.Wo * a.ldO, PPT * a.ldO}, stepR[2] = {a.Wo * a.ldR, PPT * a.ldR}, stepM[2] = {a.Wo * a.ldM, PPT * a.ldM};
-    // second output out2 = out + add2 (a skip sum leaves with the tile): same item addressing as the other epilogue tensors
-    const bool two = a.out2 != nullptr && a.ksplit == 1;
-    float* const out2B = two ? a.out2 + opb * a.ldO2 + j0 : nullptr;
-    const float* const add2B = two ? a.add2 + opb * a.ldA2 + j0 : nullptr;
-    const int stepO2[2] = {a.Wo * a.ldO2, PPT * a.ldO2}, stepA2[2] = {a.Wo * a.ldA2, PPT * a.ldA2};
+    // out (or this K range's partial output), residual, mask and the second output out2 = out + add2 (a skip sum leaves with the
+    // tile; the finishing pass writes it under split-K): the same item addressing for all of them
+    const EpiSteps epi(a, a.out + (a.ksplit > 1 ? blockIdx.y * a.wsStride : 0), opb, j0, a.Wo, PPT, a.ksplit == 1);
     const bool pre = REFID_WINO6_ABLATE != 4 && REFID_WINO6_ABLATE != 10 && vec && a.ksplit == 1 && (a.res != nullptr || a.mask != nullptr);
     f32x4 pres[NIT], pmask[NIT];
     if (pre) {
@@ -439,18 +384,12 @@ __global__ __launch_bounds__(256, NT == 2 ? 2 : 3) void conv_wino6_kernel(const 
             const bool ok = (oy0 + it / CPR < a.Ho) && cok[it % CPR];
             pres[it] = f32x4{0.f, 0.f, 0.f, 0.f};
             pmask[it] = f32x4{1.f, 1.f, 1.f, 1.f};
-            if (ok && a.res) pres[it] = *reinterpret_cast<const f32x4*>(resB + (it / CPR) * stepR[0] + (it % CPR) * stepR[1]);
-            if (ok && a.mask) pmask[it] = *reinterpret_cast<const f32x4*>(mskB + (it / CPR) * stepM[0] + (it % CPR) * stepM[1]);
+            if (ok && a.res) pres[it] = epi_load4(epi.at(EPI_RES, it / CPR, it % CPR));
+            if (ok && a.mask) pmask[it] = epi_load4(epi.at(EPI_MASK, it / CPR, it % CPR));
         }
     }
     f32x4 bv = {0.f, 0.f, 0.f, 0.f};                        // the same four output channels for all of a thread's items
-    if (a.bias && a.ksplit == 1 && jok) {
-        const float* bp = a.bias + a.coBase + j0;
-        if (vec) bv = *reinterpret_cast<const f32x4*>(bp);
-        else
-#pragma unroll
-            for (int k = 0; k < 4; ++k) if (j0 + k < a.Cout) bv[k] = bp[k];
-    }
+    if (a.ksplit == 1 && jok) bv = epi_bias4(a, a.coBase + j0, j0, vec);
     __syncthreads();
 
 #pragma unroll
@@ -462,41 +401,17 @@ __global__ __launch_bounds__(256, NT == 2 ? 2 : 3) void conv_wino6_kernel(const 
         const f32x4* xp = xch + (((oa * 2 + ob) * NT + nt) * 4 + rq) * XL + ckh * 33 + tile;   // row i0 = oa
         const float sg = oa ? -1.f : 1.f;                   // a=0: R0+R1+R2 ; a=1: R1-R2-R3
         f32x4 v = xp[0] + (xp[TI_STRIDE] + xp[2 * TI_STRIDE]) * sg;
-        float* const outp = outB + row * stepO[0] + colb * stepO[1];
         if (a.ksplit > 1) {                                 // raw partial sums; the finishing pass applies the epilogue
-            *reinterpret_cast<f32x4*>(outp) = v;
+            *reinterpret_cast<f32x4*>(epi.at(EPI_OUT, row, colb)) = v;
             continue;
         }
         v += bv;
-        lrelu4(v, a.slopePre, a.slopePre != 1.f);
+        epi_pre(a, v);
         if (REFID_WINO6_ABLATE == 4 || REFID_WINO6_ABLATE == 10) {
-            if (v[0] == 12345.678f) outp[0] = v[1];
+            if (v[0] == 12345.678f) epi.at(EPI_OUT, row, colb)[0] = v[1];
             continue;
         }
-        if (vec) {
-            if (a.res) v += pre ? pres[it] : *reinterpret_cast<const f32x4*>(resB + row * stepR[0] + colb * stepR[1]);
-            lrelu4(v, a.slopePost, a.slopePost != 1.f);
-            if (a.mask) {
-                const f32x4 mv = pre ? pmask[it] : *reinterpret_cast<const f32x4*>(mskB + row * stepM[0] + colb * stepM[1]);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) v[k] *= (mv[k] > 0.f) ? 1.f : a.slopeMask;
-            }
-            *reinterpret_cast<f32x4*>(outp) = v;
-            if (two)
-                *reinterpret_cast<f32x4*>(out2B + row * stepO2[0] + colb * stepO2[1]) =
-                    v + *reinterpret_cast<const f32x4*>(add2B + row * stepA2[0] + colb * stepA2[1]);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (j0 + k >= a.Cout) break;
-                float tv = v[k];
-                if (a.res) tv += resB[row * stepR[0] + colb * stepR[1] + k];
-                tv = lrelu(tv, a.slopePost);
-                if (a.mask) tv *= (mskB[row * stepM[0] + colb * stepM[1] + k] > 0.f) ? 1.f : a.slopeMask;
-                outp[k] = tv;
-                if (two) out2B[row * stepO2[0] + colb * stepO2[1] + k] = tv + add2B[row * stepA2[0] + colb * stepA2[1] + k];
-            }
-        }
+        epi_tail(a, v, j0, vec, EpiAtSteps{epi, row, colb}, pre, pres[it], pmask[it]);
     }
 }
 
@@ -528,14 +443,7 @@ Wino6Plan wino6_plan(ConvKArgs& a, int split_mode, int tile_hint = 0) {
     a.ncot = cdiv(a.Cout, bn);
     p.grid = dim3(round_up(a.tilesX * a.tilesY * a.N, 8) * a.ncot);
     const int nwg = (split_mode == 2) ? (int)p.grid.x : a.tilesX * a.tilesY * a.ncot * 8;   // "sample": as if N = 8
-    int ks = 1;
-    if (split_mode && nwg <= 256 && a.nchunks >= 8) {
-        ks = 512 / nwg;
-        if (ks > a.nchunks / 4) ks = a.nchunks / 4;
-        if (ks > 8) ks = 8;
-        if (ks < 1) ks = 1;
-    }
-    p.ks = ks;
+    p.ks = split_mode ? refid_splitk_count(nwg, a.nchunks, 256, 8, 4) : 1;
     return p;
 }
 
@@ -570,7 +478,7 @@ size_t refid_wino6_workspace_bytes(const ConvKArgs& ka, int split_mode) {
     for (int hint : {0, 1, 4}) {                           // any tile form may be asked for (wino_tile): the largest need
         ConvKArgs a = ka;
         const Wino6Plan p = wino6_plan(a, split_mode, hint);
-        if (p.ks > 1) need = std::max(need, (size_t)p.ks * a.N * a.Ho * a.Wo * round_up(a.Cout, 4) * sizeof(float));
+        need = std::max(need, refid_splitk_bytes(p.ks, (long long)a.N * a.Ho * a.Wo, a.Cout));
     }
     return need;
 }
@@ -588,23 +496,9 @@ int refid_launch_wino6(const ConvKArgs& ka, float* ws, size_t ws_bytes, int spli
     // (a wide tile -- 8x32 pixels, 8 waves, weight fragments shared through an LDS ring, same bits -- measured 0-10 % slower
     //  and was removed in round 6: DESIGN.md section 7)
     const Wino6Plan pl = wino6_plan(a, ws ? split_mode : 0, tile_hint);
-    dim3 grid = pl.grid;
-    const int ks = pl.ks;
-    if (ks == 1) return pl.nt == 2 ? launch_wino6<2>(a, terms, grid, st, "conv_wino6") : launch_wino6<1>(a, terms, grid, st, "conv_wino6/32");
-    const long long npix = (long long)a.N * a.Ho * a.Wo;
-    const int ldW = round_up(a.Cout, 4);
-    const size_t need = (size_t)ks * npix * ldW * sizeof(float);
-    if (need > ws_bytes || (reinterpret_cast<uintptr_t>(ws) & 15)) {
-        refid_set_error("conv_wino6: split-K workspace too small or misaligned (%zu bytes given, %zu needed: "
-                        "refid_conv_workspace_bytes)", ws_bytes, need);
-        return 1;
-    }
-    ConvKArgs p = a;                       // partial pass: raw sums into the workspace (the finishing pass writes out / out2)
-    p.ksplit = ks; p.wsStride = npix * ldW; p.out = ws; p.ldO = ldW; p.out2 = nullptr;
-    grid.y = ks;
-    if (int rc = pl.nt == 2 ? launch_wino6<2>(p, terms, grid, st, "conv_wino6/splitk") : launch_wino6<1>(p, terms, grid, st, "conv_wino6/32/splitk"))
-        return rc;
-    ConvKArgs f = a;
-    f.ksplit = ks; f.wsStride = npix * ldW;
-    return refid_launch_splitk_finish(f, ws, ldW, npix, st);
+    if (pl.ks == 1) return pl.nt == 2 ? launch_wino6<2>(a, terms, pl.grid, st, "conv_wino6") : launch_wino6<1>(a, terms, pl.grid, st, "conv_wino6/32");
+    const dim3 grid(pl.grid.x, pl.ks);
+    return refid_launch_splitk("conv_wino6", a, pl.ks, (long long)a.N * a.Ho * a.Wo, ws, ws_bytes, [&](const ConvKArgs& p) {
+        return pl.nt == 2 ? launch_wino6<2>(p, terms, grid, st, "conv_wino6/splitk") : launch_wino6<1>(p, terms, grid, st, "conv_wino6/32/splitk");
+    }, st);
 }

@@ -19,13 +19,6 @@
 
 namespace {
 
-__device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752440f)); }
-__device__ __forceinline__ float gelu_d(float x) {
-    const float cdf = 0.5f * (1.f + erff(x * 0.70710678118654752440f));
-    const float pdf = 0.39894228040143267794f * __expf(-0.5f * x * x);
-    return cdf + x * pdf;
-}
-
 // sum over the LPP lanes that share a pixel (LPP power of two <= 64, lanes contiguous)
 template <int LPP>
 __device__ __forceinline__ float group_sum(float v) {

@@ -18,11 +18,11 @@
 // its reduction kernel unchanged.  This kernel is bandwidth / staging bound (the bf16 matrix rate is 16x the fp32
 // one): its cost is the two fp32 tensors it streams, ~2.2x less than the fp32 Winograd weight gradient it replaces.
 #include "common.h"
+#include "conv_planes.h"
 #include "wgrad_args.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 constexpr int TH = 2, TW = 32;                 // output pixels per K tile
 constexpr int COT = 64, CIT = 64;

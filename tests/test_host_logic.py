@@ -644,6 +644,81 @@ def test_weight_gradient_workspace_sizes_are_pinned():
         assert got == want, ((k, s, p, co, ca, cb, n, ho, wo, algo, phase, ib, it), got, want)
 
 
+# (kh = kw, stride, mode, algo, n, h, w, c_a, c_b, cout, split_k, bytes); pad 1 (1x1: 0), cout_pad = cout rounded up to 64
+CONV_WORKSPACE_TABLE = [
+    (4, 2, 0, 0, 1, 64, 64, 256, 0, 256, 2, 8388608),
+    (4, 2, 0, 0, 1, 64, 64, 256, 0, 256, 1, 4194304),
+    (4, 2, 0, 0, 1, 64, 66, 256, 0, 256, 1, 0),
+    (4, 2, 0, 0, 2, 64, 64, 256, 0, 256, 2, 16777216),
+    (4, 2, 0, 0, 8, 64, 64, 256, 0, 256, 2, 33554432),
+    (4, 2, 0, 0, 8, 64, 72, 256, 0, 256, 2, 0),
+    (4, 2, 0, 0, 1, 16, 16, 64, 0, 64, 1, 32768),
+    (4, 2, 0, 0, 1, 16, 16, 56, 0, 64, 1, 0),
+    (4, 2, 0, 0, 1, 16, 16, 64, 0, 64, 0, 0),
+    (4, 2, 0, 2, 1, 16, 16, 64, 0, 64, 2, 0),
+    (4, 2, 0, 2, 1, 16, 16, 128, 0, 64, 2, 32768),
+    (4, 2, 0, 0, 1, 32, 32, 128, 0, 6, 2, 0),
+    (4, 2, 2, 0, 1, 8, 8, 256, 0, 64, 2, 262144),
+    (4, 2, 2, 0, 1, 8, 8, 256, 0, 256, 2, 1048576),
+    (4, 2, 2, 0, 1, 32, 32, 256, 0, 256, 1, 0),
+    (4, 2, 2, 0, 2, 16, 32, 128, 0, 128, 2, 4194304),
+    (4, 2, 2, 0, 1, 8, 8, 112, 0, 64, 2, 0),
+    (4, 2, 2, 2, 1, 8, 8, 256, 0, 64, 2, 131072),
+    (4, 2, 2, 0, 8, 8, 8, 256, 0, 256, 2, 8388608),
+    (3, 1, 0, 1, 1, 8, 8, 256, 0, 64, 2, 65536),
+    (3, 1, 0, 1, 1, 8, 8, 256, 0, 6, 2, 8192),
+    (3, 1, 0, 1, 1, 8, 8, 256, 0, 32, 1, 32768),
+    (3, 1, 0, 1, 1, 8, 8, 128, 0, 64, 2, 32768),
+    (3, 1, 0, 1, 1, 8, 8, 120, 0, 64, 2, 0),
+    (3, 1, 0, 1, 1, 8, 8, 128, 128, 128, 2, 131072),
+    (3, 1, 0, 1, 1, 32, 128, 256, 0, 512, 2, 16777216),
+    (3, 1, 0, 1, 1, 32, 128, 256, 0, 576, 2, 0),
+    (3, 1, 0, 1, 2, 16, 32, 256, 0, 256, 2, 4194304),
+    (3, 1, 0, 1, 8, 16, 32, 256, 0, 256, 2, 16777216),
+    (3, 1, 0, 1, 1, 16, 32, 256, 0, 256, 1, 2097152),
+    (3, 1, 0, 1, 1, 9, 33, 512, 0, 64, 2, 608256),
+    (3, 1, 0, 5, 1, 8, 8, 256, 0, 64, 2, 65536),
+    (3, 1, 0, 5, 1, 8, 8, 256, 0, 6, 2, 8192),
+    (3, 1, 0, 5, 1, 8, 8, 128, 0, 64, 2, 32768),
+    (3, 1, 0, 5, 1, 8, 8, 144, 0, 64, 2, 32768),
+    (3, 1, 0, 5, 1, 8, 8, 112, 0, 64, 2, 0),
+    (3, 1, 0, 5, 1, 32, 32, 128, 0, 128, 2, 1048576),
+    (3, 1, 0, 5, 1, 32, 32, 128, 0, 128, 1, 1048576),
+    (3, 1, 0, 5, 2, 32, 32, 256, 0, 256, 2, 8388608),
+    (3, 1, 0, 5, 8, 32, 32, 256, 0, 256, 2, 16777216),
+    (3, 1, 0, 5, 1, 32, 128, 256, 0, 512, 2, 16777216),
+    (3, 1, 0, 5, 1, 32, 128, 256, 0, 576, 2, 0),
+    (3, 1, 0, 5, 1, 16, 32, 64, 64, 64, 2, 262144),
+    (3, 1, 0, 5, 8, 8, 8, 512, 0, 64, 1, 1048576),
+    (3, 1, 0, 5, 1, 8, 8, 256, 0, 64, 0, 0),
+    (3, 1, 0, 0, 1, 8, 8, 256, 0, 64, 2, 0),
+    (3, 1, 0, 4, 1, 8, 8, 256, 0, 64, 2, 0),
+    (1, 1, 0, 3, 1, 8, 8, 256, 0, 64, 2, 0),
+]
+
+
+def test_conv_workspace_sizes_are_pinned():
+    """refid_conv_workspace_bytes = split count x output pixels x channels rounded up to 4, so it moves with every part of the
+    three split-K policies (direct tile: at most 128 workgroups, at least 8 chunks, a quarter of the chunks; fp32 Winograd: 256 /
+    16 / an eighth; Winograd six-product: 256 / 8 / a quarter, over its three tile forms) and with the tile each policy counts
+    workgroups for.  Held to a recorded table: algo 0 / 2 on 4x4 stride 2 and on mode 2 with both channel-tile widths, algo 1
+    narrow and wide, algo 5 where the 64 -> 32 small-grid switch flips and where it does not, split_k 0 / 1 / 2, batch 1 / 2 / 8,
+    shapes just either side of each policy's workgroup and chunk limits, and tiles that never split.  Host arithmetic: no GPU,
+    and the pointers are never dereferenced."""
+    import ctypes as C
+    from refid_amd import _lib
+    L = _lib.lib()
+    assert len(CONV_WORKSPACE_TABLE) >= 20
+    for (k, s, mode, algo, n, h, w, ca, cb, cout, split, want) in CONV_WORKSPACE_TABLE:
+        d = _lib.ConvDesc()
+        d.in_a, d.w_packed, d.out, d.ws = 4096, 8192, 12288, 16384
+        d.n, d.h, d.w = n, h, w
+        d.ho, d.wo = (h // s, w // s) if mode == 0 else (h, w)
+        d.c_a, d.c_b, d.cout, d.cout_pad = ca, cb, cout, -(-cout // 64) * 64
+        d.kh, d.kw, d.stride, d.pad, d.mode, d.algo, d.split_k = k, k, s, 1 if k > 1 else 0, mode, algo, split
+        got = L.refid_conv_workspace_bytes(C.byref(d))
+        assert got == want, ((k, s, mode, algo, n, h, w, ca, cb, cout, split), got, want)
+
 
 def test_cached_conv_descriptors_equal_the_validating_path_byte_for_byte(monkeypatch):
     """ops.DESC_CACHE (REFID_DESC_CACHE=1): after the first call with a signature, conv2d copies a recorded descriptor and
