@@ -281,6 +281,11 @@ int refid_wgrad_finish_flush(void* stream);
  *   role DGRAD : rows = I, k = O, taps flipped (stride-1 convs), or 2x2/s2 (convT input
  *                gradient), or the four parity classes of conv4x4/s2 (mode 2)
  *   role CONVT : ConvTranspose2d forward (mode 1): rows = (dy,dx,Co), k = Ci
+ * Every entry point below -- the size functions, the one-by-one calls, refid_pack_entry_fill --
+ * builds the same record with the same conditions (csrc/pack.hip): o, i, kc, bn positive; the
+ * convT roles take a 2x2 kernel, DOWN_DGRAD a 4x4, the Winograd roles a 3x3 (kc = 8 in the fp32
+ * tile layout, no bf16 form); a scale only with the FWD / DGRAD / Winograd roles; the Winograd
+ * plane forms below 2^31 plane entries.  A size function answers 0 where a call would refuse.
  * ---------------------------------------------------------------------------------- */
 enum { REFID_ROLE_FWD = 0, REFID_ROLE_DGRAD = 1, REFID_ROLE_CONVT = 2, REFID_ROLE_CONVT_DGRAD = 3,
        REFID_ROLE_DOWN_DGRAD = 4,
@@ -299,7 +304,8 @@ int refid_pack_conv_weights(const float* w, float* packed, int role, int o, int 
  * and the residual add run in the conv tile's epilogue. */
 int refid_pack_conv_weights_scaled(const float* w, const float* oscale, float* packed, int role, int o,
                                    int i, int kh, int kw, int kc, int bn, void* stream);
-/* bf16 copy of the same packed layout (RNE), kc = 2 * refid_conv_kc(...); oscale may be NULL. */
+/* bf16 copy of the same packed layout (RNE), kc = 2 * refid_conv_kc(...); oscale may be NULL (and must be, but for the FWD / DGRAD
+ * roles).  No Winograd roles. */
 int refid_pack_conv_weights_bf16(const float* w, const float* oscale, void* packed_bf16, int role, int o, int i,
                                  int kh, int kw, int kc, int bn, void* stream);
 /* Split-bf16 packing for refid_conv2d algo 4: every weight (times oscale[row] when given) is written as `planes` bf16
@@ -348,7 +354,7 @@ int refid_pack_conv_weights_wino1h(const float* w, const float* oscale, void* pa
  * device memory once, and calls
  * refid_pack_batch whenever the weights have changed -- after refid_pack_batch_prepass on the same stream when the table holds
  * kind-5 / kind-6 records (their scale exponents: one workgroup per record, a no-op for the other kinds).  `blk0` = the sum of the values returned for the records before this one (each call returns its record's
- * workgroup count >= 1, -1 on error -- the same argument checks as the one-by-one entry points); nblocks = the sum over
+ * workgroup count >= 1, -1 on error -- the one-by-one entry points build their record the same way); nblocks = the sum over
  * all records.  refid_pack_table_check walks a finished HOST table (every record filled, first blocks consecutive from 0:
  * the kernel finds a workgroup's record by binary search over them) and returns that sum, -1 on error.  Same bits as the
  * one-by-one calls. */

@@ -125,6 +125,18 @@ VAL_TAIL_BGR = 1         # == REFID_VAL_TAIL_BGR in include/refid_hip.h
 ABI_VERSION = 9          # == REFID_ABI_VERSION in include/refid_hip.h
 _lib = None
 
+# The weight-packing family: (size function, its one-by-one entry points, the geometry arguments both take, in the C order)
+_PACK_FAMILY = (
+    ("refid_packed_weight_floats", ("refid_pack_conv_weights", "refid_pack_conv_weights_scaled", "refid_pack_conv_weights_bf16"),
+     "role o i kh kw kc bn"),
+    ("refid_packed_weight_split_bytes", ("refid_pack_conv_weights_split",), "role o i kh kw bn planes"),
+    ("refid_packed_weight_split_f16_bytes", ("refid_pack_conv_weights_split_f16",), "role o i kh kw bn"),
+    ("refid_packed_weight_wino6_bytes", ("refid_pack_conv_weights_wino6",), "role o i bn"),
+    ("refid_packed_weight_wino3h_bytes", ("refid_pack_conv_weights_wino3h",), "role o i bn"),
+    ("refid_packed_weight_wino1h_bytes", ("refid_pack_conv_weights_wino1h",), "role o i bn"),
+)
+PACK_GEO = {}            # C symbol -> names of its geometry arguments (filled when the library is bound)
+
 
 def lib():
     """The loaded library; raises RefidHipError when it is not built."""
@@ -152,12 +164,6 @@ def lib():
     L.refid_wgrad_finish_flush.argtypes = [C.c_void_p]
     L.refid_rows_sum_defer.argtypes = [C.c_int]
     L.refid_rows_sum_flush.argtypes = [C.c_void_p]
-    L.refid_packed_weight_floats.argtypes = [C.c_int] * 7
-    L.refid_packed_weight_floats.restype = C.c_size_t
-    L.refid_packed_weight_split_bytes.restype = C.c_size_t
-    L.refid_packed_weight_split_bytes.argtypes = [C.c_int] * 7
-    L.refid_pack_conv_weights_split.argtypes = [C.c_void_p] * 3 + [C.c_int] * 7 + [C.c_void_p]
-    L.refid_pack_conv_weights.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p]
     L.refid_nchw_to_nhwc.argtypes = [C.c_void_p, C.c_longlong, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]
     L.refid_nchw_tsum_to_nhwc.argtypes = [C.c_void_p, C.c_longlong, C.c_longlong, C.c_int, C.c_void_p] + [C.c_int] * 5 + \
         [C.c_void_p]
@@ -177,21 +183,13 @@ def lib():
 def _bind_extra(L):
     """EGACA / train-step entry points (a stale .so without them fails loudly here)."""
     vp, i, f, ll = C.c_void_p, C.c_int, C.c_float, C.c_longlong
-    L.refid_pack_conv_weights_scaled.argtypes = [vp, vp, vp] + [i] * 7 + [vp]
-    L.refid_pack_conv_weights_bf16.argtypes = [vp, vp, vp] + [i] * 7 + [vp]
-    L.refid_packed_weight_wino6_bytes.argtypes = [i] * 4
-    L.refid_packed_weight_wino6_bytes.restype = C.c_size_t
-    L.refid_pack_conv_weights_wino6.argtypes = [vp, vp, vp] + [i] * 4 + [vp]
-    L.refid_packed_weight_wino3h_bytes.argtypes = [i] * 4
-    L.refid_packed_weight_wino3h_bytes.restype = C.c_size_t
-    L.refid_pack_conv_weights_wino3h.argtypes = [vp, vp, vp] + [i] * 4 + [vp]
-    L.refid_packed_weight_wino1h_bytes.argtypes = [i] * 4
-    L.refid_packed_weight_wino1h_bytes.restype = C.c_size_t
-    L.refid_pack_conv_weights_wino1h.argtypes = [vp, vp, vp] + [i] * 4 + [vp]
+    for size, entries, geo in _PACK_FAMILY:
+        PACK_GEO[size] = geo = tuple(geo.split())
+        getattr(L, size).argtypes, getattr(L, size).restype = [i] * len(geo), C.c_size_t
+        for e in entries:                                   # (w, [oscale,] packed, geometry..., stream)
+            PACK_GEO[e] = geo
+            getattr(L, e).argtypes = [vp] * (2 if e == "refid_pack_conv_weights" else 3) + [i] * len(geo) + [vp]
     L.refid_pack_batch_prepass.argtypes = [vp, i, vp]
-    L.refid_packed_weight_split_f16_bytes.argtypes = [i] * 6
-    L.refid_packed_weight_split_f16_bytes.restype = C.c_size_t
-    L.refid_pack_conv_weights_split_f16.argtypes = [vp, vp, vp] + [i] * 6 + [vp]
     L.refid_mul_vec.argtypes = [vp, vp, vp, i, vp]
     L.refid_pack_entry_bytes.restype = C.c_size_t
     L.refid_pack_entry_bytes.argtypes = []

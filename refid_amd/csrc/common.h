@@ -64,6 +64,11 @@ int refid_launch_sum_rows_f64(const double* part, int rows, int n, double* out, 
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline int round_up(int a, int b) { return cdiv(a, b) * b; }
+// workgroups of 256 for a grid-stride loop over n items
+static inline int grid_for(long long n) {
+    long long b = (n + 255) / 256;
+    return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
+}
 
 // One-time per-DEVICE set-up of a kernel's dynamic-LDS limit (the attribute belongs to the device's copy of the
 // code object).  hipFuncSetAttribute is idempotent, so a benign race between host threads costs one extra call.

@@ -9,6 +9,8 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 constexpr int OOB = -1;                 // voffset 0xFFFFFFFF: buffer loads return 0 (hardware range check)
+// bytes in front of the fp16 planes of a weight packing: int scale exponent at byte 0, zeros (written by pack.hip's prepass)
+constexpr int PACK_HEADER_BYTES = 64;
 
 // v (8 fp32 channels) -> PL bf16 planes (h = rne(v), m = rne(v - h), l = v - h - m); the planes sum to v exactly for PL = 3
 // (44 VALU) and to 2^-17 |v| for PL = 2

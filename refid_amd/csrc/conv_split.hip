@@ -68,7 +68,6 @@ namespace {
 constexpr int F16_TGT = 8;             // a freshly scaled stage's largest |x| lands in [2^8, 2^9)
 constexpr int F16_SLACK = 6;            // binades a later stage may exceed the reference before the accumulators are rescaled
 constexpr int F16_E0 = F16_TGT + 1;     // initial (biased) reference exponent: any real data is larger
-constexpr int F16_HEADER = 64;          // bytes in front of the fp16 planes: int eW (runtime.hip)
 constexpr int TW = 32;                  // output pixels per tile row
 constexpr int KC = 8;                   // input channels per chunk (x 2 taps = K of one bf16 MFMA)
 constexpr int NTH = 256;
@@ -166,7 +165,7 @@ __global__ __launch_bounds__(NTH, 2) void conv_split_kernel(const ConvKArgs a) {
     const int cls = (MODE == 2) ? blockIdx.y : 0;            // MODE 2: output parity class (py, px)
     const int py = cls >> 1, px = cls & 1;
     const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc(
-        reinterpret_cast<char*>(const_cast<float*>(a.w)) + (F16 ? F16_HEADER : 0) + (long long)cls * nsub * wChunk, 0,
+        reinterpret_cast<char*>(const_cast<float*>(a.w)) + (F16 ? PACK_HEADER_BYTES : 0) + (long long)cls * nsub * wChunk, 0,
         (int)min((long long)nsub * wChunk, 0x7fffffffLL), 0x00020000);
     const int eW = F16 ? *reinterpret_cast<const int*>(a.w) : 0;       // the weights travel as w 2^eW
     int eRef = F16_E0;                                       // F16: the workgroup's reference exponent (biased)

@@ -73,7 +73,6 @@ constexpr int HP = (TH + 2) * HWD;      // 204 halo pixels
 constexpr int R_ITEMS = (4 * HP + 255) / 256;
 // 2 raw buffers (31 KB) in the K loop; afterwards the row exchange: 66 KB for 64 output channels, 33 KB for 32
 constexpr int lds_bytes(int nt) { return nt == 2 ? 64 * 66 * 16 : (32 * 66 * 16 > 2 * R_F4 * 16 ? 32 * 66 * 16 : 2 * R_F4 * 16); }
-constexpr int W3H_HEADER = 64;          // bytes in front of the fp16 planes: int eU (runtime.hip)
 constexpr int F16_TGT = 7;              // a freshly scaled chunk's largest |B^T d| lands in [2^7, 2^8)
 constexpr int F16_SLACK = 6;            // binades the largest value may grow over the reference before the accumulators are rescaled
 constexpr int F16_E0 = F16_TGT + 1;     // initial (biased) reference exponent: any real data is larger
@@ -127,7 +126,7 @@ __global__ __launch_bounds__(256, NT == 2 ? 2 : 3) void conv_wino6_kernel(const 
     const int uXi = NPL * uPlane;                          // bytes between xi and xi+1
     const int uChunk = 16 * uXi;                           // bytes per K chunk
     const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(a.w) + (F16 ? W3H_HEADER / 4 : 0), 0, (int)min((long long)a.nchunks * uChunk, 0x7fffffffLL), 0x00020000);
+        const_cast<float*>(a.w) + (F16 ? PACK_HEADER_BYTES / 4 : 0), 0, (int)min((long long)a.nchunks * uChunk, 0x7fffffffLL), 0x00020000);
     const int eU = F16 ? *reinterpret_cast<const int*>(a.w) : 0;      // U travels as U 2^eU (wave-uniform scalar load)
     int eRef = F16_E0;                                      // this lane's reference exponent (biased), F16 only
     // raw halo: thread -> (pixel, channel quad); four lanes read one pixel's 64 contiguous bytes

@@ -310,44 +310,26 @@ def _sub_batches(n, *tensors):
 
 class _Packing:
     """One packed copy of a conv's weights: the ConvOp attribute that holds the buffer (by name: _Egaca re-binds conv5.wp and
-    side.wp to halves of one buffer), the packer ("pack": the fp32 / bf16 tile layouts, "split": bf16 / fp16 planes of the
-    direct tile, "wino6": planes of U = G g G^T) and that packer's arguments after the weight; `flag` is bf16 for "pack",
-    f16 for "split", the product terms (0 = six bf16, 3 = three fp16, 1 = one fp16) for "wino6".  lazy: a fallback layout the batched repack leaves out (ConvOp._packed writes it on demand)."""
-    __slots__ = ("attr", "form", "args", "flag", "lazy", "epoch")
+    side.wp to halves of one buffer), its form (a key of ops.py's table of packings) and geometry (ops.pack_geo).  lazy: a
+    fallback layout the batched repack leaves out (ConvOp._packed writes it on demand)."""
+    __slots__ = ("attr", "form", "geo", "lazy", "epoch")
 
-    def __init__(self, attr, form, args, flag=False):
-        self.attr, self.form, self.args, self.flag, self.lazy, self.epoch = attr, form, args, flag, False, -1
+    def __init__(self, attr, form, geo):
+        self.attr, self.form, self.geo, self.lazy, self.epoch = attr, form, geo, False, -1
 
     def alloc(self, device):
-        if self.form == "pack":
-            return torch.empty(ops.packed_weight_floats(*self.args), dtype=torch.bfloat16 if self.flag else torch.float32, device=device)
-        one_plane = self.form == "wino6" and self.flag == 1    # (ops.conv2d tells the one-plane Winograd packing by its type)
-        return torch.empty(self.nbytes() // 2, dtype=torch.float16 if one_plane else torch.bfloat16, device=device)
+        return ops.pack_alloc(self.form, self.geo, device)
 
     def nbytes(self):
-        """Size of a plane-form packing (also what its 2 GiB guard looks at)."""
-        if self.form == "split":
-            return ops.packed_weight_split_bytes(*self.args, self.flag)
-        return ops.packed_weight_wino6_bytes(*self.args, terms=self.flag)
+        """Size of the packing (what the plane forms' 2 GiB guard looks at)."""
+        return ops.pack_bytes(self.form, self.geo)
 
     def pack(self, op):
-        out = getattr(op, self.attr)
-        if self.form == "pack":
-            (ops.pack_conv_weights_bf16 if self.flag else ops.pack_conv_weights)(op.w, *self.args, out=out, oscale=op.scale)
-        elif self.form == "split":
-            ops.pack_conv_weights_split(op.w, *self.args[:-1], planes=self.args[-1], out=out, oscale=op.scale, f16=self.flag)
-        else:
-            ops.pack_conv_weights_wino6(op.w, *self.args, out=out, oscale=op.scale, terms=self.flag)
+        ops.pack_form(self.form, op.w, self.geo, out=getattr(op, self.attr), oscale=op.scale)
         self.epoch = op.arena.pack_epoch
 
     def plan(self, op, plan):
-        out = getattr(op, self.attr)
-        if self.form == "pack":
-            plan.add_pack(op.w, *self.args, out, oscale=op.scale, bf16=self.flag)
-        elif self.form == "split":
-            plan.add_split(op.w, *self.args, out, oscale=op.scale, f16=self.flag)
-        else:
-            plan.add_wino6(op.w, *self.args, out, oscale=op.scale, terms=self.flag)
+        plan.add_form(self.form, op.w, self.geo, getattr(op, self.attr), oscale=op.scale)
 
 
 class ConvOp:
@@ -421,7 +403,8 @@ class ConvOp:
             self.f_kc, self.f_bn = 8, 32
         self.f_pad = -(-self.f_rows // self.f_bn) * self.f_bn
         # The packed copies of the weights, in the order repack() / plan_repack() write them (the batched launch's entry order)
-        wp = _Packing("wp", "pack", (f_role, self.f_bn, self.f_kc, k, k, co, ci), bf16)
+        tile_form = "bf16" if bf16 else "f32"
+        wp = _Packing("wp", tile_form, ops.pack_geo(f_role, co, ci, k, k, self.f_kc, self.f_bn))
         wd = wp6 = wd6 = wps = wds = None
         if need_dgrad:
             self.d_kc = ops.conv_kc(*d_geo)
@@ -440,7 +423,7 @@ class ConvOp:
             if bf16:
                 self.d_kc *= 2
             self.d_pad = -(-self.d_rows // self.d_bn) * self.d_bn
-            wd = _Packing("wd", "pack", (self.d_role, self.d_bn, self.d_kc, k, k, co, ci), bf16)
+            wd = _Packing("wd", tile_form, ops.pack_geo(self.d_role, co, ci, k, k, self.d_kc, self.d_bn))
         # Winograd x six bf16 products (algo 5): third packing -- three bf16 planes of U = G g G^T.  From 32 output channels
         # on (round 4: the tile's 32-channel form; REFID_WINO6_MIN_CO=33 restores round 3's choice for an A/B)
         # ... and thin outputs (pred, 32 -> 3): the direct fp32 tile pads them to 32 GEMM columns and is bound by the fp32
@@ -451,10 +434,11 @@ class ConvOp:
         f_wino, d_wino = self.f_algo == 1, self.d_algo == 1
         if fp16 and bf16 and USE_WINOGRAD and kind == "conv" and k == 3:
             f_wino, d_wino = co >= 16, True
+        f_terms, d_terms = (1, 1) if fp16 else (3 if WINO_F16_FWD else 0, 3 if WINO_F16_DGRAD else 0)
         if WINO6 and (fp16 or not bf16) and ((f_wino and co >= WINO6_MIN_CO) or thin6) and ci % 4 == 0:
-            wp6 = _Packing("wp6", "wino6", (ops.ROLE_WINO_FWD, co, ci), 1 if fp16 else (3 if WINO_F16_FWD else 0))
+            wp6 = _Packing("wp6", ops.wino6_form(terms=f_terms), ops.pack_geo(ops.ROLE_WINO_FWD, co, ci))
         if WINO6 and (fp16 or not bf16) and need_dgrad and d_wino and ci >= WINO6_MIN_CO and co % 4 == 0:
-            wd6 = _Packing("wd6", "wino6", (ops.ROLE_WINO_DGRAD, co, ci), 1 if fp16 else (3 if WINO_F16_DGRAD else 0))
+            wd6 = _Packing("wd6", ops.wino6_form(terms=d_terms), ops.pack_geo(ops.ROLE_WINO_DGRAD, co, ci))
         if wp6 is not None and wp6.nbytes() >= 2 ** 31 - 1:
             wp6 = None
         if wd6 is not None and wd6.nbytes() >= 2 ** 31 - 1:
@@ -472,13 +456,13 @@ class ConvOp:
             # "fp16": a conv on the one-plane Winograd packing never reads the split planes -- but for the input-gradient halves
             # of a ci == 2 co conv below the Winograd tile's 32 rows, which stay on the split tile as in the bf16 mode
             if not (fp16 and wp6 is not None):
-                wps = _Packing("wps", "split", (ops.ROLE_FWD, sf_bn, 3, 3, co, ci, planes))
+                wps = _Packing("wps", "split", ops.pack_geo(ops.ROLE_FWD, co, ci, 3, 3, 8, sf_bn, planes))
             if need_dgrad and co % 8 == 0 and (not (fp16 and wd6 is not None) or (ci == 2 * co and co < WINO6_MIN_CO)):
                 sd_bn = self.d_bn if self.d_algo != 1 else ops.conv_bn(3, 3, 1, 0, min(ci, 128))
                 if ci == 2 * co:
                     sd_bn = ops.conv_bn(3, 3, 1, 0, co)
                 sd_pad = -(-ci // sd_bn) * sd_bn
-                wds = _Packing("wds", "split", (ops.ROLE_DGRAD, sd_bn, 3, 3, co, ci, planes))
+                wds = _Packing("wds", "split", ops.pack_geo(ops.ROLE_DGRAD, co, ci, 3, 3, 8, sd_bn, planes))
         if kind == "down" and ci % 8 == 0 and co % 8 == 0 and (terms or DOWN_SPLIT):
             self.split = terms = terms or DOWN_SPLIT
             planes = {1: 1, 3: 2, 6: 3, ops.TERMS_F16X3: 2}[terms]
@@ -486,11 +470,11 @@ class ConvOp:
             if not bf16:                      # (plain bf16 operands: the LDS-staged tile is as fast on the forward conv)
                 sf_bn = ops.conv_bn(4, 4, 2, 0, co)
                 sf_pad = -(-co // sf_bn) * sf_bn
-                wps = _Packing("wps", "split", (ops.ROLE_FWD, sf_bn, 4, 4, co, ci, planes), f16)
+                wps = _Packing("wps", ops.split_form(4, 4, f16), ops.pack_geo(ops.ROLE_FWD, co, ci, 4, 4, 8, sf_bn, planes))
             if need_dgrad:
                 sd_bn = ops.conv_bn(4, 4, 2, 2, ci)
                 sd_pad = -(-ci // sd_bn) * sd_bn
-                wds = _Packing("wds", "split", (ops.ROLE_DOWN_DGRAD, sd_bn, 4, 4, co, ci, planes), f16)
+                wds = _Packing("wds", ops.split_form(4, 4, f16), ops.pack_geo(ops.ROLE_DOWN_DGRAD, co, ci, 4, 4, 8, sd_bn, planes))
         # A conv with Winograd x six planes runs on them wherever its shapes allow (_fwd_route / _dgrad_route): its fp32 Winograd
         # packing (wp / wd, algo 1) is a FALLBACK layout (two sources whose first is not a multiple of 16 channels, input-
         # gradient row ranges below 32 rows) -- 159 MB of the model's 463 MB of packed weights that the batched repack of
@@ -518,7 +502,7 @@ class ConvOp:
             self._f_split = ("wps", dict(kh=kh, kw=kw, stride=st, pad=1, mode=0, cout_pad=sf_pad, algo=4, terms=self.split), True, False)
         if wp6 is not None and (self.split == 0 or fp16):
             self._f_wino6 = ("wp6", dict(kh=3, kw=3, stride=1, pad=1, mode=0, cout_pad=-(-self.f_rows // 64) * 64, algo=5,
-                                     terms=wp6.flag), True, False)
+                                     terms=f_terms), True, False)
         # (the pointwise tile has no second output)
         self._f_plain = ("wp", dict(kh=kh, kw=kw, stride=st, pad=self.pad, mode=md, cout_pad=self.f_pad, algo=self.f_algo),
                          self.f_algo != 3, True)
@@ -529,7 +513,7 @@ class ConvOp:
             if wd6 is not None and (self.split == 0 or fp16):
                 # (the planes' rows are padded to 64 = the fp32 Winograd tile's d_bn; "fp16" keeps the bf16 tile's d_bn in d_pad)
                 self._d_wino6 = ("wd6", dict(kh=3, kw=3, stride=1, pad=1, mode=0, cout_pad=-(-self.d_rows // 64) * 64, algo=5,
-                                         terms=wd6.flag), True, False)
+                                         terms=d_terms), True, False)
             # the pointwise tile: the patch GEMM of ConvTranspose2d writes the second output, the 1x1 layers keep their separate
             # skip-sum launch.  GELU' rides only in the fp32 pointwise tile of a 1x1 conv (refid_conv_desc.mask_mode = 1)
             self._d_plain = ("wd", dict(kh=kh, kw=kw, stride=st, pad=d_padding, mode=md, cout_pad=self.d_pad, algo=self.d_algo),

@@ -4,6 +4,7 @@ Tensors are NHWC fp32 on the GPU: shape (N, H, W, C) with stride(-1) == 1; the p
 pitch may exceed C (channel-slice views of wider buffers).  torch is used here only
 for device memory and streams; all arithmetic happens in librefid_hip.so.
 """
+import collections
 import ctypes as C
 import os
 
@@ -61,84 +62,34 @@ def conv_bn(kh, kw, stride, mode, cout):
     return lib().refid_conv_bn(kh, kw, stride, mode, cout)
 
 
-def packed_weight_floats(role, bn, kc, kh, kw, o, i):
-    return lib().refid_packed_weight_floats(role, o, i, kh, kw, kc, bn)
+# Every weight packing: the public spelling (pack fp32 / bf16; split with planes or f16; wino6 with terms 0 / 6 / 3 / 1) -> the
+# record kind and `planes` of refid_pack_entry_fill (None: the caller's), the element type of the packing's tensor (the one-plane
+# Winograd packing is tagged by it: conv2d), the C size function and one-by-one entry point.  The geometry arguments of each C
+# symbol, in its order: _lib.PACK_GEO.
+_Form = collections.namedtuple("_Form", "kind planes dtype size entry")
+_FORMS = {
+    "f32": _Form(0, 0, torch.float32, "refid_packed_weight_floats", "refid_pack_conv_weights"),       # (+ "_scaled" with a scale)
+    "bf16": _Form(0, 1, torch.bfloat16, "refid_packed_weight_floats", "refid_pack_conv_weights_bf16"),
+    "split": _Form(1, None, torch.bfloat16, "refid_packed_weight_split_bytes", "refid_pack_conv_weights_split"),
+    "split1x1": _Form(2, None, torch.bfloat16, "refid_packed_weight_split_bytes", "refid_pack_conv_weights_split"),
+    "split_f16": _Form(6, 2, torch.bfloat16, "refid_packed_weight_split_f16_bytes", "refid_pack_conv_weights_split_f16"),
+    "wino6": _Form(3, 3, torch.bfloat16, "refid_packed_weight_wino6_bytes", "refid_pack_conv_weights_wino6"),
+    "wino3h": _Form(5, 2, torch.bfloat16, "refid_packed_weight_wino3h_bytes", "refid_pack_conv_weights_wino3h"),
+    "wino1h": _Form(5, 1, torch.float16, "refid_packed_weight_wino1h_bytes", "refid_pack_conv_weights_wino1h"),
+}
 
 
-def pack_conv_weights(w, role, bn, kc, kh, kw, o, i, out=None, oscale=None):
-    """Pack a reference-layout weight (OIHW, or IOHW for ConvTranspose2d) for the conv tile.
-
-    oscale: optional per-output-channel factor folded into the packed copy (FWD/DGRAD)."""
-    L = lib()
-    nfl = L.refid_packed_weight_floats(role, o, i, kh, kw, kc, bn)
-    if nfl == 0:
-        raise _lib.RefidHipError("pack_conv_weights: bad geometry")
-    if not w.is_contiguous():
-        raise _lib.RefidHipError("pack_conv_weights: weight must be contiguous")
-    if out is None:
-        out = torch.empty(nfl, dtype=torch.float32, device=w.device)
-    elif out.numel() != nfl:
-        raise _lib.RefidHipError("pack_conv_weights: out has the wrong size")
-    if oscale is None:
-        check(L.refid_pack_conv_weights(w.data_ptr(), out.data_ptr(), role, o, i, kh, kw, kc, bn, _stream()),
-              "refid_pack_conv_weights")
-    else:
-        check(L.refid_pack_conv_weights_scaled(w.data_ptr(), oscale.data_ptr(), out.data_ptr(), role, o, i, kh, kw,
-                                               kc, bn, _stream()), "refid_pack_conv_weights_scaled")
-    return out
+def pack_geo(role, o, i, kh=3, kw=3, kc=16, bn=64, planes=0):
+    """The geometry of a packing (defaults: the Winograd plane forms')."""
+    return dict(role=role, o=o, i=i, kh=kh, kw=kw, kc=kc, bn=bn, planes=planes)
 
 
-def pack_conv_weights_bf16(w, role, bn, kc, kh, kw, o, i, out=None, oscale=None):
-    """bf16 packed weights for conv2d(algo=2); kc = 2 * conv_kc(...)."""
-    L = lib()
-    n = L.refid_packed_weight_floats(role, o, i, kh, kw, kc, bn)
-    if n == 0:
-        raise _lib.RefidHipError("pack_conv_weights_bf16: bad geometry")
-    if out is None:
-        out = torch.empty(n, dtype=torch.bfloat16, device=w.device)
-    check(L.refid_pack_conv_weights_bf16(w.data_ptr(), oscale.data_ptr() if oscale is not None else None,
-                                         out.data_ptr(), role, o, i, kh, kw, kc, bn, _stream()),
-          "refid_pack_conv_weights_bf16")
-    return out
+def split_form(kh, kw, f16=False):
+    return "split_f16" if f16 else ("split1x1" if kh == 1 and kw == 1 else "split")
 
 
-TERMS_F16X3 = 19          # refid_conv_desc.mfma_terms of the split tile's three-fp16-product form (16 + 3)
-
-
-def packed_weight_split_bytes(role, bn, kh, kw, o, i, planes, f16=False):
-    """f16: two fp16 planes behind a 64-byte header (conv2d algo 4 with terms = TERMS_F16X3); `planes` is then ignored."""
-    if f16:
-        return lib().refid_packed_weight_split_f16_bytes(role, o, i, kh, kw, bn)
-    return lib().refid_packed_weight_split_bytes(role, o, i, kh, kw, bn, planes)
-
-
-def pack_conv_weights_split(w, role, bn, kh, kw, o, i, planes=3, out=None, oscale=None, f16=False):
-    """Split-bf16 packed weights for conv2d(algo=4): `planes` bf16 numbers per weight (3 = exact, 2 = 2^-17); f16: two fp16
-    planes of w 2^eW (22 bits), the scale exponent found by a reduction over the tensor and kept in the packing's header."""
-    L = lib()
-    nb = packed_weight_split_bytes(role, bn, kh, kw, o, i, planes, f16)
-    if nb == 0:
-        raise _lib.RefidHipError("pack_conv_weights_split: bad geometry")
-    if not w.is_contiguous():
-        raise _lib.RefidHipError("pack_conv_weights_split: weight must be contiguous")
-    if out is None:
-        out = torch.empty(nb // 2, dtype=torch.bfloat16, device=w.device)
-    elif out.numel() * out.element_size() != nb:
-        raise _lib.RefidHipError("pack_conv_weights_split: out has the wrong size")
-    if f16:
-        check(L.refid_pack_conv_weights_split_f16(w.data_ptr(), oscale.data_ptr() if oscale is not None else None,
-                                                  out.data_ptr(), role, o, i, kh, kw, bn, _stream()),
-              "refid_pack_conv_weights_split_f16")
-        return out
-    check(L.refid_pack_conv_weights_split(w.data_ptr(), oscale.data_ptr() if oscale is not None else None,
-                                          out.data_ptr(), role, o, i, kh, kw, bn, planes, _stream()),
-          "refid_pack_conv_weights_split")
-    return out
-
-
-def _wino6_form(f16, terms):
-    """The packing a conv2d(algo=5, terms=...) call reads: suffix of the C entry points.  `terms` wins over the older `f16`
-    flag (f16=True = terms 3)."""
+def wino6_form(f16=False, terms=None):
+    """The packing a conv2d(algo=5, terms=...) call reads.  `terms` wins over the older `f16` flag (f16=True = terms 3)."""
     if terms is None:
         terms = 3 if f16 else 0
     if terms not in (0, 6, 3, 1):
@@ -147,32 +98,83 @@ def _wino6_form(f16, terms):
     return {0: "wino6", 6: "wino6", 3: "wino3h", 1: "wino1h"}[terms]
 
 
+def pack_elems(form, geo):
+    """Elements of the packing's tensor (0: bad geometry)."""
+    f = _FORMS[form]
+    n = getattr(lib(), f.size)(*(geo[k] for k in _lib.PACK_GEO[f.size]))
+    return n if f.size.endswith("floats") else n // 2           # (every size in bytes is of two-byte elements)
+
+
+def pack_bytes(form, geo):
+    return pack_elems(form, geo) * _FORMS[form].dtype.itemsize
+
+
+def pack_alloc(form, geo, device):
+    return torch.empty(pack_elems(form, geo), dtype=_FORMS[form].dtype, device=device)
+
+
+def pack_form(form, w, geo, out=None, oscale=None, what="pack_form"):
+    """Pack `w` (contiguous, reference layout) as `form`: size, contiguity, allocate or check `out`, the one-by-one call."""
+    f = _FORMS[form]
+    n = pack_elems(form, geo)
+    if n == 0:
+        raise _lib.RefidHipError(f"{what}: bad geometry")
+    if not w.is_contiguous():
+        raise _lib.RefidHipError(f"{what}: weight must be contiguous")
+    if out is None:
+        out = torch.empty(n, dtype=f.dtype, device=w.device)
+    elif out.numel() * out.element_size() != n * f.dtype.itemsize:
+        raise _lib.RefidHipError(f"{what}: out has the wrong size")
+    elif not out.is_contiguous():
+        raise _lib.RefidHipError(f"{what}: out must be contiguous")
+    name, ptrs = f.entry, [w.data_ptr(), None if oscale is None else oscale.data_ptr(), out.data_ptr()]
+    if form == "f32":                                   # two C entry points: with a scale and without the argument
+        name, ptrs = (name, ptrs[::2]) if oscale is None else (name + "_scaled", ptrs)
+    check(getattr(lib(), name)(*ptrs, *(geo[k] for k in _lib.PACK_GEO[name]), _stream()), name)
+    return out
+
+
+def packed_weight_floats(role, bn, kc, kh, kw, o, i):
+    return pack_elems("f32", pack_geo(role, o, i, kh, kw, kc, bn))
+
+
+def pack_conv_weights(w, role, bn, kc, kh, kw, o, i, out=None, oscale=None):
+    """Pack a reference-layout weight (OIHW, or IOHW for ConvTranspose2d) for the conv tile.
+
+    oscale: optional per-output-channel factor folded into the packed copy (FWD/DGRAD)."""
+    return pack_form("f32", w, pack_geo(role, o, i, kh, kw, kc, bn), out, oscale, "pack_conv_weights")
+
+
+def pack_conv_weights_bf16(w, role, bn, kc, kh, kw, o, i, out=None, oscale=None):
+    """bf16 packed weights for conv2d(algo=2); kc = 2 * conv_kc(...)."""
+    return pack_form("bf16", w, pack_geo(role, o, i, kh, kw, kc, bn), out, oscale, "pack_conv_weights_bf16")
+
+
+TERMS_F16X3 = 19          # refid_conv_desc.mfma_terms of the split tile's three-fp16-product form (16 + 3)
+
+
+def packed_weight_split_bytes(role, bn, kh, kw, o, i, planes, f16=False):
+    """f16: two fp16 planes behind a 64-byte header (conv2d algo 4 with terms = TERMS_F16X3); `planes` is then ignored."""
+    return pack_bytes(split_form(kh, kw, f16), pack_geo(role, o, i, kh, kw, 8, bn, planes))
+
+
+def pack_conv_weights_split(w, role, bn, kh, kw, o, i, planes=3, out=None, oscale=None, f16=False):
+    """Split-bf16 packed weights for conv2d(algo=4): `planes` bf16 numbers per weight (3 = exact, 2 = 2^-17); f16: two fp16
+    planes of w 2^eW (22 bits), the scale exponent found by a reduction over the tensor and kept in the packing's header."""
+    return pack_form(split_form(kh, kw, f16), w, pack_geo(role, o, i, kh, kw, 8, bn, planes), out, oscale, "pack_conv_weights_split")
+
+
 def packed_weight_wino6_bytes(role, o, i, f16=False, terms=None):
     """Bytes of the Winograd-domain packing for conv2d(algo=5): three bf16 planes (terms 0 / 6), a 64-byte header + two fp16
     planes (terms 3, or f16=True), or the header + one fp16 plane (terms 1)."""
-    return getattr(lib(), "refid_packed_weight_%s_bytes" % _wino6_form(f16, terms))(role, o, i, 64)
+    return pack_bytes(wino6_form(f16, terms), pack_geo(role, o, i))
 
 
 def pack_conv_weights_wino6(w, role, o, i, out=None, oscale=None, f16=False, terms=None):
     """Winograd-domain weights as three bf16 planes for conv2d(algo=5); role = ROLE_WINO_FWD / ROLE_WINO_DGRAD.
     terms=3 (or f16=True): the two-fp16-plane packing of conv2d(algo=5, terms=3) (scaled by a per-tensor power of two kept in
     its header); terms=1: its high plane alone, for the one-product form conv2d(algo=5, terms=1)."""
-    L = lib()
-    form = _wino6_form(f16, terms)
-    nb = packed_weight_wino6_bytes(role, o, i, f16, terms)
-    if nb == 0:
-        raise _lib.RefidHipError("pack_conv_weights_wino6: bad geometry")
-    if not w.is_contiguous():
-        raise _lib.RefidHipError("pack_conv_weights_wino6: weight must be contiguous")
-    if out is None:
-        # (the one-plane form is tagged by its tensor type: conv2d(algo=5, terms=1) takes nothing else)
-        out = torch.empty(nb // 2, dtype=torch.float16 if form == "wino1h" else torch.bfloat16, device=w.device)
-    elif out.numel() * out.element_size() != nb:
-        raise _lib.RefidHipError("pack_conv_weights_wino6: out has the wrong size")
-    fn = getattr(L, "refid_pack_conv_weights_" + form)
-    check(fn(w.data_ptr(), oscale.data_ptr() if oscale is not None else None, out.data_ptr(), role, o, i, 64, _stream()),
-          "refid_pack_conv_weights_" + form)
-    return out
+    return pack_form(wino6_form(f16, terms), w, pack_geo(role, o, i), out, oscale, "pack_conv_weights_wino6")
 
 
 def _pw_extras(pw, out):
@@ -781,19 +783,18 @@ class PackPlan:
         self.items.append((kind, w, oscale, dst, role, o, i, kh, kw, kc, bn, planes))
         self.keep += [w, oscale, dst]
 
+    def add_form(self, form, w, geo, out, oscale=None):
+        f = _FORMS[form]
+        self._add(f.kind, w, oscale, out, **dict(geo, planes=geo["planes"] if f.planes is None else f.planes))
+
     def add_pack(self, w, role, bn, kc, kh, kw, o, i, out, oscale=None, bf16=False):
-        self._add(0, w, oscale, out, role, o, i, kh, kw, kc, bn, 1 if bf16 else 0)
+        self.add_form("bf16" if bf16 else "f32", w, pack_geo(role, o, i, kh, kw, kc, bn), out, oscale)
 
     def add_split(self, w, role, bn, kh, kw, o, i, planes, out, oscale=None, f16=False):
-        if f16:
-            self._add(6, w, oscale, out, role, o, i, kh, kw, 8, bn, 2)
-        else:
-            self._add(2 if kh == 1 and kw == 1 else 1, w, oscale, out, role, o, i, kh, kw, 8, bn, planes)
+        self.add_form(split_form(kh, kw, f16), w, pack_geo(role, o, i, kh, kw, 8, bn, planes), out, oscale)
 
     def add_wino6(self, w, role, o, i, out, oscale=None, f16=False, terms=None):
-        form = _wino6_form(f16, terms)
-        kind, planes = {"wino6": (3, 3), "wino3h": (5, 2), "wino1h": (5, 1)}[form]
-        self._add(kind, w, oscale, out, role, o, i, 3, 3, 16, 64, planes)
+        self.add_form(wino6_form(f16, terms), w, pack_geo(role, o, i), out, oscale)
 
     def add_mul_vec(self, a, b, out):
         self._add(4, a, b, out, o=a.numel())

@@ -378,7 +378,7 @@ def test_parameter_hooks_fire_and_grads_do_not_alias_the_arena(golden_dir):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("dtype", ["fp32", "bf16", "bf16x3"])
+@pytest.mark.parametrize("dtype", ["fp32", "bf16", "bf16x3", "fp16"])
 def test_batched_weight_packing_equals_the_one_by_one_calls(dtype):
     """Engine.repack(): every packed copy of the weights (direct / Winograd / Winograd x six / split planes / folded biases) written
     by ONE launch (refid_pack_batch) is bit-identical to the per-packing calls."""

@@ -446,7 +446,7 @@ def test_convop_gelu_mask_and_skip_sum_follow_the_tile_route(monkeypatch):
     calls = []
     monkeypatch.setattr(ops, "conv2d", lambda a, w, out, **kw: calls.append(("conv2d", kw)))
     monkeypatch.setattr(ops, "add", lambda a, b, out=None: calls.append(("add", out)) or out)
-    for nm in ("pack_conv_weights", "pack_conv_weights_bf16", "pack_conv_weights_split", "pack_conv_weights_wino6", "mul_vec"):
+    for nm in ("pack_form", "pack_conv_weights", "pack_conv_weights_bf16", "pack_conv_weights_split", "pack_conv_weights_wino6", "mul_vec"):
         monkeypatch.setattr(ops, nm, lambda *a, **kw: None)
     eng = engine.Engine(26, device="cpu")
     answers = set()
@@ -802,3 +802,66 @@ def test_cached_conv_descriptors_equal_the_validating_path_byte_for_byte(monkeyp
     a, w, o = t(1, 8, 32, 64), t(1 << 16), t(1, 8, 32, 68)[..., 2:66]
     with pytest.raises(_lib.RefidHipError):
         ops.conv2d(t(1, 8, 32, 64), w, o, kh=3, kw=3, pad=1, cout=64, cout_pad=64, algo=5, bias=t(64), slope_pre=0.1)
+
+
+def test_weight_packing_sizes_records_and_table_check_stay_as_they_were():
+    """The host side of weight packing, pinned to what the library answered before the record builder was written once
+    (pack.hip): the byte / float counts of the layouts tests/test_hip_pack_layouts.py walks, the record size, the workgroup
+    counts refid_pack_entry_fill returns, its refusals (-1 with a message) and refid_pack_table_check's."""
+    import ctypes as C
+    from refid_amd import _lib, ops
+    L = _lib.lib()
+    F, D, CT, CTD, DD, WF, WD, CTP = range(8)
+    assert (F, D, CT, CTD, DD, WF, WD, CTP) == (ops.ROLE_FWD, ops.ROLE_DGRAD, ops.ROLE_CONVT, ops.ROLE_CONVT_DGRAD, ops.ROLE_DOWN_DGRAD,
+                                                ops.ROLE_WINO_FWD, ops.ROLE_WINO_DGRAD, ops.ROLE_CONVT_DGRAD_PW)
+    fl = lambda role, o, i, k, kc, bn: ops.packed_weight_floats(role, bn, kc, k, k, o, i)        # noqa: E731
+    sp = lambda role, o, i, k, planes, f16=False: ops.packed_weight_split_bytes(role, 32, k, k, o, i, planes, f16)   # noqa: E731
+    assert [fl(F, 20, 12, 3, 8, 32), fl(D, 20, 12, 3, 8, 32)] == [4608, 6912]
+    assert [fl(F, 20, 12, 3, 16, 32), fl(D, 20, 12, 3, 16, 32), fl(DD, 24, 20, 4, 16, 32)] == [4608, 9216, 16384]
+    assert [sp(F, 20, 12, 3, pl) for pl in (1, 2, 3)] == [10240, 20480, 30720]
+    assert [sp(D, 20, 12, 3, pl) for pl in (1, 2, 3)] == [15360, 30720, 46080]
+    assert [sp(F, 20, 12, 3, 2, True), sp(D, 20, 12, 3, 2, True)] == [20544, 30784]
+    assert [sp(r, 24, 20, 4, pl) for r in (F, DD) for pl in (1, 2, 3)] == [24576, 49152, 73728] * 2
+    assert [sp(F, 24, 20, 4, 2, True), sp(DD, 24, 20, 4, 2, True)] == [49216, 49216]
+    assert fl(DD, 24, 20, 4, 8, 32) == 12288
+    assert [sp(r, 20, 24, 1, pl) for r in (F, D) for pl in (1, 2, 3)] == [2048, 4096, 6144] * 2
+    assert [fl(WF, 40, 24, 3, 8, 64), fl(WD, 40, 24, 3, 8, 64)] == [24576, 40960]
+    assert [ops.packed_weight_wino6_bytes(r, 40, 24, terms=t) for t in (0, 3, 1) for r in (WF, WD)] == \
+        [196608, 294912, 131136, 196672, 65600, 98368]
+    assert [fl(r, 12, 24, 2, 8, 32) for r in (CT, CTD, CTP)] == [1536, 2048, 1536]
+    # a bad geometry has no size
+    assert sp(F, 20, 12, 5, 3) == 0 and sp(F, 20, 12, 1, 2, True) == 0 and sp(F, 20, 12, 3, 4) == 0
+    assert ops.packed_weight_wino6_bytes(F, 40, 24) == 0 and fl(8, 20, 12, 3, 8, 32) == 0
+    with pytest.raises(_lib.RefidHipError):
+        ops.packed_weight_wino6_bytes(WF, 40, 24, terms=2)
+
+    esz = L.refid_pack_entry_bytes()
+    assert esz == 112
+
+    def fill(kind, role, o, i, k, kc, bn, planes, blk0=0, scale=False, buf=None, at=0):
+        buf = buf if buf is not None else (C.c_char * esz)()
+        # (the pointers are only stored: 16-byte aligned placeholders)
+        return L.refid_pack_entry_fill(C.addressof(buf) + at * esz, kind, 4096, 8192 if scale else None, 16384, role, o, i, k, k,
+                                       kc, bn, planes, blk0)
+
+    records = [(0, F, 20, 12, 3, 8, 32, 0, 18), (0, WF, 40, 24, 3, 8, 64, 0, 96), (1, F, 20, 12, 3, 8, 32, 3, 60),
+               (2, F, 20, 24, 1, 8, 32, 3, 12), (3, WF, 40, 24, 3, 16, 64, 3, 8), (5, WF, 40, 24, 3, 16, 64, 2, 8),
+               (5, WD, 40, 24, 3, 16, 64, 1, 12), (6, DD, 24, 20, 4, 8, 32, 2, 96)]
+    for kind, role, o, i, k, kc, bn, planes, want in records:
+        assert fill(kind, role, o, i, k, kc, bn, planes) == want, (kind, role)
+    assert fill(4, 0, 37, 0, 1, 8, 32, 0, scale=True) == 1
+    for bad in ((7, F, 20, 12, 3, 8, 32, 0), (5, WF, 40, 24, 3, 16, 64, 3)):
+        assert fill(*bad) == -1 and L.refid_last_error()
+    assert fill(0, CT, 12, 24, 2, 8, 32, 0, scale=True) == -1 and b"scale" in L.refid_last_error()
+
+    # a table: consecutive first blocks pass, an unfilled record and a gap are refused
+    table = (C.c_char * (3 * esz))()
+    blk = 0
+    for n, (kind, role, o, i, k, kc, bn, planes, want) in enumerate(records[:3]):
+        assert fill(kind, role, o, i, k, kc, bn, planes, blk0=blk, buf=table, at=n) == want
+        blk += want
+    assert L.refid_pack_table_check(C.addressof(table), 3) == blk == 18 + 96 + 60
+    C.memset(C.addressof(table) + esz, 0, esz)
+    assert L.refid_pack_table_check(C.addressof(table), 3) == -1 and b"never filled" in L.refid_last_error()
+    assert fill(*records[1][:8], blk0=18 + 1, buf=table, at=1) == 96
+    assert L.refid_pack_table_check(C.addressof(table), 3) == -1 and b"starts at block" in L.refid_last_error()
