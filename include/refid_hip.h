@@ -610,6 +610,57 @@ int refid_assemble_bins(int m, int n, int layout);
 int refid_assemble_batch(const refid_assemble_desc* d, int stages, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * voxel_norm (data/event_util.py:141-160) on the device, and the single-image event deblurring dataset's __getitem__
+ * (data/Single_image_npy_dataset.py:136-201), the one place where the reference KEEPS voxel_norm's result (:187, after
+ * crop and augmentation).  Per sample, with v the fp32 voxel element:
+ *   S0 = #{v != 0}, S1 = sum v, S2 = sum v^2, mean64 = S1/S0, var64 = S2/S0 - mean64^2 (float64),
+ *   mean_f = (float)mean64, std_f = (float)sqrt(var64),
+ *   out = v != 0 ? (v - mean_f) / std_f : 0     -- one fp32 subtraction and one IEEE fp32 division, no contraction: the
+ *                                                   reference's order, mask * (voxel - mean) / stddev.
+ * Bit-reproducible, no floating-point atomics: a statistics launch writes one partial {S0, S1, S2} (three 8-byte words)
+ * per (sample, chunk of 4096 elements) into `parts`, which the caller owns (refid_voxel_norm_parts words); the
+ * normalising launch adds a sample's partials in index order.  S0 is an integer count.  S2 is float64 in a fixed tree
+ * order (every v*v is exact in float64; within a chunk: 16 elements per thread at stride 256 in sequence, the 64 lanes of
+ * a wave by the xor tree 1,2,..,32, the 4 waves in order).  S1 is float64 in that same order on the stand-alone route and
+ * an exact int64 sum of v*2^32 on the fused route, where v = (float)a * 2^-32 of the int64 scratch is a multiple of
+ * 2^-32.  The order depends on an element's index inside its sample only: the result does not depend on the run, the
+ * batch size, the sample's position in the batch, or the other samples.  Inputs must be finite.
+ * Degenerate samples:
+ *   S0 == 0: the output is all zeros (the reference leaves the voxel untouched: the same thing).
+ *   var64 <= 0 or std_f == 0 (one non-zero element, or all non-zero elements equal): the output is all zeros.  The
+ *   reference divides 0 by 0 there and returns an all-NaN voxel; that is NOT reproduced, a deliberate departure like
+ *   the dropped events above.
+ * ---------------------------------------------------------------------------------- */
+/* 8-byte words of `parts` for `batch` samples of `per_sample` elements */
+long long refid_voxel_norm_parts(int batch, long long per_sample);
+/* Stand-alone form on an fp32 (batch, per_sample) tensor, e.g. a voxel that arrives already assembled; out == in is
+ * allowed.  Two launches on `stream`. */
+int refid_voxel_norm(const float* in, float* out, int batch, long long per_sample, void* parts, void* stream);
+
+#define REFID_ASSEMBLE_STATS 16
+typedef struct refid_single_desc {
+    const refid_sample_desc* samples_host;      /* as refid_assemble_desc; frames: 2 per sample, blur then sharp   */
+    const refid_sample_desc* samples_dev;
+    int batch;
+    int bins;                                   /* >= 1 and != 3 (img2tensor would swap bins 0 and 2)             */
+    int crop_h, crop_w;                         /* crop BEFORE the transpose; rot90 needs crop_h == crop_w        */
+    int norm;                                   /* 0: voxel = the plain bins; 1: voxel_norm per sample            */
+    long long* scratch;                         /* int64 [batch][bins][crop_h*crop_w]                             */
+    void* parts;                                /* refid_voxel_norm_parts(batch, bins*crop_h*crop_w) words; norm  */
+    float* lq;                                  /* (batch, 3, h, w): frame 0, BGR -> RGB, /255                    */
+    float* voxel;                               /* (batch, bins, h, w): plain bins, not sliding pairs             */
+    float* gt;                                  /* (batch, 3, h, w): frame 1                                      */
+} refid_single_desc;
+/* `bins`, or -1 (with the error text set) when the single layout does not support it. */
+int refid_single_bins(int bins);
+/* Runs the chosen stages (REFID_ASSEMBLE_* and REFID_ASSEMBLE_STATS) in the order zero, scatter, stats, finish, frames
+ * on `stream`: one launch each for the whole batch.  Scatter and frames are the kernels of refid_assemble_batch; stats
+ * is skipped when norm == 0.  With norm == 1 the fused result equals refid_voxel_norm applied to the norm == 0 voxel of
+ * the same call, bit for bit (float64 adds multiples of 2^-32 exactly while the partial sums stay below 2^21).  Fewer
+ * than 2^30 events per sample with norm (S1 stays inside int64). */
+int refid_assemble_single(const refid_single_desc* d, int stages, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Test-time assembly of network inputs for frame pairs of ONE resident sequence (csrc/sequence.hip): the key frames and
  * the whole event stream are uploaded once, and every pair (two key-frame indices + a row window of the stream) becomes
  * one sample of `lq` / `voxel` in the layouts of refid_assemble_batch.  No crop, no flips, no ground truth.  The event

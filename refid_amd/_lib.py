@@ -96,6 +96,20 @@ class AssembleDesc(C.Structure):
     ]
 
 
+class SingleDesc(C.Structure):
+    """refid_single_desc: the single-image layout (lq, plain-bin voxel with voxel_norm, gt)."""
+    _fields_ = [
+        ("samples_host", C.c_void_p), ("samples_dev", C.c_void_p),
+        ("batch", C.c_int),
+        ("bins", C.c_int),
+        ("crop_h", C.c_int), ("crop_w", C.c_int),
+        ("norm", C.c_int),
+        ("scratch", C.c_void_p),
+        ("parts", C.c_void_p),
+        ("lq", C.c_void_p), ("voxel", C.c_void_p), ("gt", C.c_void_p),
+    ]
+
+
 class SeqPair(C.Structure):
     """refid_seq_pair: one frame pair of a resident sequence (refid_amd.sequence.SequenceAssembler fills the table)."""
     _fields_ = [
@@ -120,6 +134,7 @@ class SeqDesc(C.Structure):
 
 LAYOUT_BLUR, LAYOUT_SHARP = 0, 1                 # == REFID_LAYOUT_* in include/refid_hip.h
 ASSEMBLE_ZERO, ASSEMBLE_SCATTER, ASSEMBLE_FINISH, ASSEMBLE_FRAMES, ASSEMBLE_ALL = 1, 2, 4, 8, 15
+ASSEMBLE_STATS = 16                              # refid_assemble_single only: voxel_norm's statistics, between scatter and finish
 
 VAL_TAIL_BGR = 1         # == REFID_VAL_TAIL_BGR in include/refid_hip.h
 ABI_VERSION = 9          # == REFID_ABI_VERSION in include/refid_hip.h
@@ -240,6 +255,11 @@ def _bind_extra(L):
     L.refid_assemble_bins.argtypes = [i, i, i]
     L.refid_assemble_batch.argtypes = [C.POINTER(AssembleDesc), i, vp]
     L.refid_seq_assemble.argtypes = [C.POINTER(SeqDesc), i, vp]
+    L.refid_voxel_norm_parts.argtypes = [i, ll]
+    L.refid_voxel_norm_parts.restype = ll
+    L.refid_voxel_norm.argtypes = [vp, vp, i, ll, vp, vp]
+    L.refid_single_bins.argtypes = [i]
+    L.refid_assemble_single.argtypes = [C.POINTER(SingleDesc), i, vp]
 
 
 def check(rc, what):

@@ -17,6 +17,18 @@
 // NOT reproduced from the reference: its flat index xs + ys*W + tis*W*H (event_util.py:54-59) lets an event outside the
 // frame, or with a negative normalised time, wrap or spill into another pixel / bin.  Such events are dropped here, as
 // are events outside the crop window.  Polarity: > 0 counts as +1, everything else (0 or -1) as -1.
+// NOT reproduced either: voxel_norm (event_util.py:141-160) of a sample whose non-zero elements have no spread (one
+// element, or all equal) divides 0 by 0 and returns an all-NaN voxel; here such a sample's voxel is all zeros.
+//
+// The single-image layout (data/Single_image_npy_dataset.py:136-201): lq (B,3,h,w) from frame 0, gt (B,3,h,w) from frame 1,
+// voxel (B,bins,h,w) = the plain bins after voxel_norm, the one data-dependent step: a reduction over the sample between
+// the scatter and the finish.  voxel_stats_kernel writes one partial {S0, S1, S2} per (sample, chunk of 4096 elements),
+// voxel_apply_kernel sums a sample's partials in index order and normalises.  S0 (the count of non-zero elements) is an
+// integer; on the fused route S1 is an exact int64 sum of v * 2^32 (v = fixed_to_float(a) is a multiple of 2^-32: an
+// integer rounded to 24 bits is an integer); S2 = sum v^2 is FLOAT64 IN A FIXED TREE ORDER: every product is exact in
+// float64, a thread adds its 16 elements e = chunk*4096 + k*256 + t in the order k = 0..15, the 64 lanes of a wave are
+// added by the xor tree 1, 2, 4, .., 32 (adjacent pairs first), the four waves and then the chunks in index order.  The
+// order depends on the element's index inside the sample only: not on the batch, the sample's place in it, or the run.
 #include <cstdint>
 
 #include "common.h"
@@ -30,6 +42,7 @@ struct BatchGeom {
     int oh, ow;          // output plane
     int lq_chn;          // blur layout: channels of lq
 };
+constexpr int LAYOUT_SINGLE = 2;   // refid_assemble_single only: frame 0 -> lq (B,3,h,w), frame 1 -> gt (B,3,h,w)
 
 // (cy, cx) in the crop -> flat index in the output plane: hflip, vflip, then transpose (transforms.py:116-128)
 __device__ __forceinline__ int out_index(const refid_sample_desc& s, const BatchGeom& g, int cy, int cx) {
@@ -106,11 +119,157 @@ __global__ __launch_bounds__(256) void sample_frames_kernel(const refid_sample_d
         c[2][k] = (float)px[0] / 255.f;
     }
     float* dst;
-    if (f >= 2) dst = gt + ((long long)b * (g.bins - 1) + (f - 2)) * 3 * plane;
+    if (g.layout == LAYOUT_SINGLE) dst = (f == 0 ? lq : gt) + (long long)b * 3 * plane;
+    else if (f >= 2) dst = gt + ((long long)b * (g.bins - 1) + (f - 2)) * 3 * plane;
     else if (g.layout == REFID_LAYOUT_BLUR) dst = lq + ((long long)b * g.lq_chn + (f == 0 ? 0 : 3 + (g.m - 1))) * plane;
     else dst = lq + ((long long)b * 2 + f) * 3 * plane;
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) store_v<V>(dst + ch * plane + e, c[ch]);
+}
+
+// ---- voxel_norm: statistics over the non-zero elements of a sample, then (v - mean) / std on them -------------------------
+constexpr int VN_CHUNK = 4096;                 // elements per workgroup of the statistics pass: 256 threads x 16
+constexpr double VN_TWO_M32 = 1.0 / 4294967296.0;
+
+// In = float: the element itself, S1 in float64 (same tree as S2).  In = long long: the scatter's fixed-point sum,
+// v = fixed_to_float(a), S1 as the exact integer sum of v * 2^32.
+template <class In> struct VoxelIn;
+template <> struct VoxelIn<float> {
+    typedef double S1;
+    static __device__ __forceinline__ float value(float a) { return a; }
+    static __device__ __forceinline__ double term(float v) { return (double)v; }
+    static __device__ __forceinline__ double sum(double s1) { return s1; }
+};
+template <> struct VoxelIn<long long> {
+    typedef long long S1;
+    static __device__ __forceinline__ float value(long long a) { return fixed_to_float(a); }
+    static __device__ __forceinline__ long long term(float v) { return (long long)(v * REFID_TWO32); }   // exact
+    static __device__ __forceinline__ double sum(long long s1) { return (double)s1 * VN_TWO_M32; }
+};
+
+// fixed xor tree over the 64 lanes (adjacent pairs first), then the four waves in index order; the total is in thread 0
+template <class T>
+__device__ __forceinline__ T vn_block_sum(T v, T* sh) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o, 64);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    v = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+    __syncthreads();
+    return v;
+}
+
+// grid = (chunks of the sample, batch); parts[(b * chunks + c) * 3 + {0, 1, 2}] = S0, S1, S2 of chunk c of sample b
+template <class In>
+__global__ __launch_bounds__(256) void voxel_stats_kernel(const In* __restrict__ in, long long per_sample,
+                                                         unsigned long long* __restrict__ parts) {
+#pragma clang fp contract(off)
+    typedef typename VoxelIn<In>::S1 S1;
+    __shared__ unsigned long long sh[4];
+    const In* src = in + (long long)blockIdx.y * per_sample;
+    const long long base = (long long)blockIdx.x * VN_CHUNK + threadIdx.x;
+    long long s0 = 0;
+    S1 s1 = 0;
+    double s2 = 0.0;
+#pragma unroll 4
+    for (int k = 0; k < VN_CHUNK / 256; ++k) {
+        const long long e = base + k * 256;
+        if (e >= per_sample) break;
+        const float v = VoxelIn<In>::value(src[e]);
+        s0 += v != 0.f;
+        s1 += VoxelIn<In>::term(v);
+        s2 += (double)v * (double)v;
+    }
+    s0 = vn_block_sum(s0, reinterpret_cast<long long*>(sh));
+    s1 = vn_block_sum(s1, reinterpret_cast<S1*>(sh));
+    s2 = vn_block_sum(s2, reinterpret_cast<double*>(sh));
+    if (threadIdx.x == 0) {
+        unsigned long long* p = parts + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * 3;
+        p[0] = (unsigned long long)s0;
+        __builtin_memcpy(p + 1, &s1, 8);
+        __builtin_memcpy(p + 2, &s2, 8);
+    }
+}
+
+// grid = (chunks of the sample, batch); one thread = V consecutive elements.  parts == nullptr: conversion only.
+// Every workgroup sums the sample's partials itself, in index order: mean64 = S1/S0, var64 = S2/S0 - mean64^2,
+// out = v != 0 ? (v - (float)mean64) / (float)sqrt(var64) : 0; all zeros when S0 == 0, var64 <= 0 or the fp32 std is 0.
+template <class In, int V>
+__global__ __launch_bounds__(256) void voxel_apply_kernel(const In* in, float* out,                   // (out may be in)
+                                                         long long per_sample, const unsigned long long* __restrict__ parts,
+                                                         int chunks) {
+#pragma clang fp contract(off)
+    typedef typename VoxelIn<In>::S1 S1;
+    __shared__ float sh_ms[2];
+    __shared__ int sh_ok;
+    const int b = blockIdx.y;
+    if (parts && threadIdx.x == 0) {
+        const unsigned long long* p = parts + (long long)b * chunks * 3;
+        long long s0 = 0;
+        S1 s1 = 0;
+        double s2 = 0.0;
+        for (int c = 0; c < chunks; ++c) {
+            S1 t1;
+            double t2;
+            __builtin_memcpy(&t1, p + c * 3ll + 1, 8);
+            __builtin_memcpy(&t2, p + c * 3ll + 2, 8);
+            s0 += (long long)p[c * 3ll];
+            s1 += t1;
+            s2 += t2;
+        }
+        const double n = (double)s0;
+        const double mean = VoxelIn<In>::sum(s1) / n;
+        const double var = s2 / n - mean * mean;
+        const float std_f = (float)sqrt(var);
+        sh_ms[0] = (float)mean;
+        sh_ms[1] = std_f;
+        sh_ok = s0 > 0 && var > 0.0 && std_f != 0.f;
+    }
+    __syncthreads();
+    const long long e = (blockIdx.x * 256ll + threadIdx.x) * V;
+    if (e >= per_sample) return;
+    const In* src = in + (long long)b * per_sample + e;
+    float v[V];
+    if constexpr (V == 4 && sizeof(In) == 8) {
+        const longlong2 a0 = *reinterpret_cast<const longlong2*>(src), a1 = *reinterpret_cast<const longlong2*>(src + 2);
+        v[0] = VoxelIn<In>::value(a0.x); v[1] = VoxelIn<In>::value(a0.y);
+        v[2] = VoxelIn<In>::value(a1.x); v[3] = VoxelIn<In>::value(a1.y);
+    } else if constexpr (V == 4) {
+        const float4 a = *reinterpret_cast<const float4*>(src);
+        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
+    } else {
+        v[0] = VoxelIn<In>::value(src[0]);
+    }
+    if (parts) {
+        const bool ok = sh_ok != 0;
+        const float mean_f = sh_ms[0], std_f = sh_ms[1];
+#pragma unroll
+        for (int k = 0; k < V; ++k) v[k] = (ok && v[k] != 0.f) ? (v[k] - mean_f) / std_f : 0.f;
+    }
+    store_v<V>(out + (long long)b * per_sample + e, v);
+}
+
+static inline long long vn_chunks(long long per_sample) { return (per_sample + VN_CHUNK - 1) / VN_CHUNK; }
+
+// statistics (stats) and / or normalisation (apply; parts == nullptr: conversion only) of `batch` samples, one launch each
+template <class In>
+int voxel_norm_launch(const In* in, float* out, int batch, long long per_sample, void* parts, bool stats, bool apply,
+                      hipStream_t st, const char* what) {
+    const long long chunks = vn_chunks(per_sample);
+    unsigned long long* p = static_cast<unsigned long long*>(parts);
+    if (stats) {
+        hipLaunchKernelGGL(voxel_stats_kernel<In>, dim3((unsigned)chunks, batch), dim3(256), 0, st, in, per_sample, p);
+        REFID_LAUNCH_CHECK(what);
+    }
+    if (apply) {
+        const bool vec = (per_sample & 3) == 0 && (((uintptr_t)in | (uintptr_t)out) & 15) == 0;
+        const unsigned nb = (unsigned)(((vec ? per_sample / 4 : per_sample) + 255) / 256);
+        if (vec) hipLaunchKernelGGL((voxel_apply_kernel<In, 4>), dim3(nb, batch), dim3(256), 0, st, in, out, per_sample, p, (int)chunks);
+        else hipLaunchKernelGGL((voxel_apply_kernel<In, 1>), dim3(nb, batch), dim3(256), 0, st, in, out, per_sample, p, (int)chunks);
+        REFID_LAUNCH_CHECK(what);
+    }
+    return 0;
 }
 
 }  // namespace
@@ -135,32 +294,68 @@ extern "C" int refid_assemble_bins(int m, int n, int layout) {
     return bins;
 }
 
+// The per-sample checks both assemblers make on the host table; max_events: the longest event list of the batch
+static int check_samples(const refid_sample_desc* tab, int batch, int crop_h, int crop_w, long long* max_events) {
+    REFID_CHECK((long long)crop_h * crop_w <= (1ll << 30), "assemble: crop %dx%d too large", crop_h, crop_w);
+    bool any_rot = false;
+    *max_events = 0;
+    for (int b = 0; b < batch; ++b) {
+        const refid_sample_desc& s = tab[b];
+        REFID_CHECK(s.n_events >= 0 && (s.n_events == 0 || s.events) && ((uintptr_t)s.events & 15) == 0,
+                    "assemble: sample %d: events must be %lld 16-byte aligned float32 rows", b, s.n_events);
+        REFID_CHECK(s.frames && s.height > 0 && s.width > 0, "assemble: sample %d: no frames", b);
+        REFID_CHECK(s.top >= 0 && s.left >= 0 && s.top + crop_h <= s.height && s.left + crop_w <= s.width,
+                    "assemble: sample %d: crop %dx%d at (%d,%d) does not fit inside the %dx%d frame", b, crop_h, crop_w,
+                    s.top, s.left, s.height, s.width);
+        const long long wy = (long long)s.top - s.y0, wx = (long long)s.left - s.x0;
+        REFID_CHECK(s.y0 >= 0 && s.x0 >= 0 && wy >= 0 && wx >= 0 && s.row_pitch > 0 && (wx + crop_w) * 3 <= s.row_pitch &&
+                    (wy + crop_h) * s.row_pitch <= s.frame_stride,
+                    "assemble: sample %d: crop %dx%d at (%d,%d) does not fit inside the uploaded window (origin (%d,%d), row "
+                    "pitch %d, frame stride %lld)", b, crop_h, crop_w, s.top, s.left, s.y0, s.x0, s.row_pitch, s.frame_stride);
+        any_rot = any_rot || s.rot90;
+        if (s.n_events > *max_events) *max_events = s.n_events;
+    }
+    REFID_CHECK(!any_rot || crop_h == crop_w, "assemble: rot90 (a transpose) needs a square crop, got %dx%d", crop_h, crop_w);
+    return 0;
+}
+
+// stages zero and scatter of both assemblers
+static int launch_zero_scatter(const refid_sample_desc* tab_dev, int batch, const BatchGeom& g, long long max_events,
+                               long long* scratch, int stages, hipStream_t st) {
+    const long long plane = (long long)g.oh * g.ow;
+    if (stages & REFID_ASSEMBLE_ZERO) {
+        hipError_t e = hipMemsetAsync(scratch, 0, sizeof(long long) * (size_t)batch * g.bins * plane, st);
+        REFID_CHECK(e == hipSuccess, "assemble: memset failed: %s", hipGetErrorString(e));
+    }
+    if ((stages & REFID_ASSEMBLE_SCATTER) && max_events > 0) {
+        long long nbx = (max_events + 255) / 256;
+        if (nbx > 2048) nbx = 2048;
+        hipLaunchKernelGGL(sample_scatter_kernel, dim3((unsigned)nbx, batch), dim3(256), 0, st, tab_dev, g,
+                           reinterpret_cast<unsigned long long*>(scratch));
+        REFID_LAUNCH_CHECK("assemble: scatter");
+    }
+    return 0;
+}
+
+// stage frames of both assemblers: n_frames u8 frames per sample
+static int launch_frames(const refid_sample_desc* tab_dev, int batch, const BatchGeom& g, int n_frames, float* lq, float* gt,
+                         hipStream_t st) {
+    const long long plane = (long long)g.oh * g.ow;
+    const bool vec = (plane & 3) == 0;                                         // planes stay 16-byte aligned
+    const unsigned chunks = (unsigned)(((vec ? plane / 4 : plane) + 255) / 256);
+    if (vec) hipLaunchKernelGGL(sample_frames_kernel<4>, dim3(chunks, n_frames, batch), dim3(256), 0, st, tab_dev, g, lq, gt);
+    else hipLaunchKernelGGL(sample_frames_kernel<1>, dim3(chunks, n_frames, batch), dim3(256), 0, st, tab_dev, g, lq, gt);
+    REFID_LAUNCH_CHECK("assemble: frames");
+    return 0;
+}
+
 extern "C" int refid_assemble_batch(const refid_assemble_desc* d, int stages, void* stream) {
     REFID_CHECK(d && d->samples_host && d->samples_dev && d->batch > 0 && d->batch <= 65535 && d->crop_h > 0 && d->crop_w > 0 &&
                 d->scratch && d->lq && d->voxel && d->gt, "assemble: bad arguments");
     const int bins = refid_assemble_bins(d->m, d->n, d->layout);
     if (bins < 0) return 1;
-    REFID_CHECK((long long)d->crop_h * d->crop_w <= (1ll << 30), "assemble: crop %dx%d too large", d->crop_h, d->crop_w);
     long long max_events = 0;
-    bool any_rot = false;
-    for (int b = 0; b < d->batch; ++b) {
-        const refid_sample_desc& s = d->samples_host[b];
-        REFID_CHECK(s.n_events >= 0 && (s.n_events == 0 || s.events) && ((uintptr_t)s.events & 15) == 0,
-                    "assemble: sample %d: events must be %lld 16-byte aligned float32 rows", b, s.n_events);
-        REFID_CHECK(s.frames && s.height > 0 && s.width > 0, "assemble: sample %d: no frames", b);
-        REFID_CHECK(s.top >= 0 && s.left >= 0 && s.top + d->crop_h <= s.height && s.left + d->crop_w <= s.width,
-                    "assemble: sample %d: crop %dx%d at (%d,%d) does not fit inside the %dx%d frame", b, d->crop_h, d->crop_w,
-                    s.top, s.left, s.height, s.width);
-        const long long wy = (long long)s.top - s.y0, wx = (long long)s.left - s.x0;
-        REFID_CHECK(s.y0 >= 0 && s.x0 >= 0 && wy >= 0 && wx >= 0 && s.row_pitch > 0 && (wx + d->crop_w) * 3 <= s.row_pitch &&
-                    (wy + d->crop_h) * s.row_pitch <= s.frame_stride,
-                    "assemble: sample %d: crop %dx%d at (%d,%d) does not fit inside the uploaded window (origin (%d,%d), row "
-                    "pitch %d, frame stride %lld)", b, d->crop_h, d->crop_w, s.top, s.left, s.y0, s.x0, s.row_pitch, s.frame_stride);
-        any_rot = any_rot || s.rot90;
-        if (s.n_events > max_events) max_events = s.n_events;
-    }
-    REFID_CHECK(!any_rot || d->crop_h == d->crop_w, "assemble: rot90 (a transpose) needs a square crop, got %dx%d", d->crop_h,
-                d->crop_w);
+    if (int rc = check_samples(d->samples_host, d->batch, d->crop_h, d->crop_w, &max_events)) return rc;
     BatchGeom g;
     g.bins = bins; g.m = d->m; g.n = d->n; g.layout = d->layout;
     g.ch = d->crop_h; g.cw = d->crop_w;
@@ -168,28 +363,60 @@ extern "C" int refid_assemble_batch(const refid_assemble_desc* d, int stages, vo
     g.lq_chn = 6 + 2 * (d->m - 1);
     const long long plane = (long long)g.oh * g.ow;
     hipStream_t st = (hipStream_t)stream;
-    if (stages & REFID_ASSEMBLE_ZERO) {
-        hipError_t e = hipMemsetAsync(d->scratch, 0, sizeof(long long) * (size_t)d->batch * bins * plane, st);
-        REFID_CHECK(e == hipSuccess, "assemble: memset failed: %s", hipGetErrorString(e));
-    }
-    if ((stages & REFID_ASSEMBLE_SCATTER) && max_events > 0) {
-        long long nbx = (max_events + 255) / 256;
-        if (nbx > 2048) nbx = 2048;
-        hipLaunchKernelGGL(sample_scatter_kernel, dim3((unsigned)nbx, d->batch), dim3(256), 0, st, d->samples_dev, g,
-                           reinterpret_cast<unsigned long long*>(d->scratch));
-        REFID_LAUNCH_CHECK("assemble: scatter");
-    }
-    const bool vec = (plane & 3) == 0;                                         // planes stay 16-byte aligned
-    const unsigned chunks = (unsigned)(((vec ? plane / 4 : plane) + 255) / 256);
+    if (int rc = launch_zero_scatter(d->samples_dev, d->batch, g, max_events, d->scratch, stages, st)) return rc;
     if (stages & REFID_ASSEMBLE_FINISH) {
+        const bool vec = (plane & 3) == 0;                                     // planes stay 16-byte aligned
+        const unsigned chunks = (unsigned)(((vec ? plane / 4 : plane) + 255) / 256);
         if (vec) hipLaunchKernelGGL(sample_finish_kernel<4>, dim3(chunks, bins, d->batch), dim3(256), 0, st, g, d->scratch, d->lq, d->voxel);
         else hipLaunchKernelGGL(sample_finish_kernel<1>, dim3(chunks, bins, d->batch), dim3(256), 0, st, g, d->scratch, d->lq, d->voxel);
         REFID_LAUNCH_CHECK("assemble: finish");
     }
-    if (stages & REFID_ASSEMBLE_FRAMES) {
-        if (vec) hipLaunchKernelGGL(sample_frames_kernel<4>, dim3(chunks, bins + 1, d->batch), dim3(256), 0, st, d->samples_dev, g, d->lq, d->gt);
-        else hipLaunchKernelGGL(sample_frames_kernel<1>, dim3(chunks, bins + 1, d->batch), dim3(256), 0, st, d->samples_dev, g, d->lq, d->gt);
-        REFID_LAUNCH_CHECK("assemble: frames");
+    if (stages & REFID_ASSEMBLE_FRAMES) return launch_frames(d->samples_dev, d->batch, g, bins + 1, d->lq, d->gt, st);
+    return 0;
+}
+
+extern "C" long long refid_voxel_norm_parts(int batch, long long per_sample) {
+    return (batch > 0 && per_sample > 0) ? 3 * (long long)batch * vn_chunks(per_sample) : 0;
+}
+
+extern "C" int refid_voxel_norm(const float* in, float* out, int batch, long long per_sample, void* parts, void* stream) {
+    REFID_CHECK(in && out && parts && batch > 0 && batch <= 65535 && per_sample > 0 && per_sample <= (1ll << 36) &&
+                ((uintptr_t)parts & 7) == 0, "voxel_norm: bad arguments (batch=%d, per_sample=%lld)", batch, per_sample);
+    return voxel_norm_launch<float>(in, out, batch, per_sample, parts, true, true, (hipStream_t)stream, "voxel_norm");
+}
+
+extern "C" int refid_single_bins(int bins) {
+    if (bins < 1) { refid_set_error("assemble: single layout needs num_bins >= 1 (num_bins=%d)", bins); return -1; }
+    if (bins == 3) {
+        refid_set_error("assemble: num_bins == 3 is not supported: the reference's img2tensor (img_util.py:23-24) takes a 3-bin "
+                        "voxel for a BGR image and swaps bins 0 and 2");
+        return -1;
     }
+    return bins;
+}
+
+extern "C" int refid_assemble_single(const refid_single_desc* d, int stages, void* stream) {
+    REFID_CHECK(d && d->samples_host && d->samples_dev && d->batch > 0 && d->batch <= 65535 && d->crop_h > 0 && d->crop_w > 0 &&
+                d->scratch && d->lq && d->voxel && d->gt && (!d->norm || d->parts) && ((uintptr_t)d->parts & 7) == 0,
+                "assemble: bad arguments");
+    if (refid_single_bins(d->bins) < 0) return 1;
+    long long max_events = 0;
+    if (int rc = check_samples(d->samples_host, d->batch, d->crop_h, d->crop_w, &max_events)) return rc;
+    // every event adds exactly 2^32 of magnitude to the scratch, so below 2^30 events the int64 sum S1 cannot overflow
+    REFID_CHECK(!d->norm || max_events < (1ll << 30), "assemble: voxel_norm supports fewer than 2^30 events per sample (%lld)",
+                max_events);
+    BatchGeom g;
+    g.bins = d->bins; g.m = 1; g.n = 0; g.layout = LAYOUT_SINGLE;
+    g.ch = d->crop_h; g.cw = d->crop_w;
+    g.oh = d->crop_h; g.ow = d->crop_w;
+    g.lq_chn = 3;
+    const long long per_sample = (long long)d->bins * g.oh * g.ow;             // scratch and voxel: the same flat (B, bins, h, w)
+    REFID_CHECK(per_sample <= (1ll << 36), "assemble: %d bins of %dx%d are too large", d->bins, d->crop_h, d->crop_w);
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = launch_zero_scatter(d->samples_dev, d->batch, g, max_events, d->scratch, stages, st)) return rc;
+    const bool stats = (stages & REFID_ASSEMBLE_STATS) && d->norm, finish = (stages & REFID_ASSEMBLE_FINISH) != 0;
+    if (int rc = voxel_norm_launch<long long>(d->scratch, d->voxel, d->batch, per_sample, d->norm ? d->parts : nullptr, stats,
+                                              finish, st, "assemble: voxel_norm")) return rc;
+    if (stages & REFID_ASSEMBLE_FRAMES) return launch_frames(d->samples_dev, d->batch, g, 2, d->lq, d->gt, st);
     return 0;
 }

@@ -83,6 +83,12 @@ class DeviceBatchAssembler:
     gt (B, bins-1, 3, h, w).  ``gt_size=None`` keeps the whole frame (all samples of a batch then share one frame size, and
     rot90 needs a square frame).
 
+    ``layout='single'`` (GoProSingleImageEventDataset, data/Single_image_npy_dataset.py:136-201; ``m`` and ``n`` are not
+    used): ``num_bins`` bins, frames u8 (2, Hwin, Wwin, 3) = blur, sharp; lq (B, 3, h, w), gt (B, 3, h, w) and voxel
+    (B, num_bins, h, w), the plain bins after ``voxel_norm`` (event_util.py:141-160, kept at :187) unless
+    ``norm_voxel=False``.  A sample whose non-zero voxel elements have no spread comes out all zeros, where the reference
+    returns NaN.
+
     ``__call__(raw_batch)``: a list of per-sample dicts, or a dict of per-sample lists.  Per sample:
       frames       u8 tensor (2 + bins-1, Hwin, Wwin, 3), BGR: blur0, blur1, then the ground-truth frames; host or device
       events       float32 tensor (N, 4) rows [t, x, y, p] as the datasets build them (N may be 0); host or device
@@ -95,14 +101,22 @@ class DeviceBatchAssembler:
     uploaded there (pin them for an asynchronous copy).  The cached scratch is ordered by that stream only: use one
     assembler per stream (``CUDAPrefetcher`` runs its own on its side stream)."""
 
-    def __init__(self, m, n, layout="blur", gt_size=None, use_hflip=False, use_rot=False, device=None):
-        if layout not in ("blur", "sharp"):
-            raise RefidHipError(f"DeviceBatchAssembler: unknown layout {layout!r} ('blur' or 'sharp')")
+    def __init__(self, m=1, n=1, layout="blur", gt_size=None, use_hflip=False, use_rot=False, device=None, num_bins=6,
+                 norm_voxel=True):
+        if layout not in ("blur", "sharp", "single"):
+            raise RefidHipError(f"DeviceBatchAssembler: unknown layout {layout!r} ('blur', 'sharp' or 'single')")
         from . import ops
         self.m, self.n = int(m), int(n)
         self.layout = layout
-        self._layout = _lib.LAYOUT_BLUR if layout == "blur" else _lib.LAYOUT_SHARP
-        self.bins = ops.assemble_bins(self.m, self.n, self._layout)
+        self.norm_voxel = bool(norm_voxel)
+        if layout == "single":
+            self._layout = None
+            self.bins = ops.single_bins(num_bins)
+            self.n_frames = 2
+        else:
+            self._layout = _lib.LAYOUT_BLUR if layout == "blur" else _lib.LAYOUT_SHARP
+            self.bins = ops.assemble_bins(self.m, self.n, self._layout)
+            self.n_frames = self.bins + 1
         self.gt_size = None if gt_size is None else int(gt_size)
         self.use_hflip, self.use_rot = bool(use_hflip), bool(use_rot)
         self.device = torch.device("cuda" if device is None else device)
@@ -119,8 +133,14 @@ class DeviceBatchAssembler:
     def rerun(self, stages):
         """Launches ``stages`` (``_lib.ASSEMBLE_*``) again for the batch of the last call, into its outputs: lets a
         benchmark put device events around a single kernel (tools/bench_assemble.py)."""
+        self._run(self._last[0], stages)
+
+    def _run(self, desc, stages):
         from . import ops
-        ops.assemble_batch(self._last[0], stages)
+        if self.layout == "single":
+            ops.assemble_single(desc, stages)
+        else:
+            ops.assemble_batch(desc, stages & _lib.ASSEMBLE_ALL)
 
     def _geometry(self, batch, h, w):
         key = (batch, h, w)
@@ -131,6 +151,9 @@ class DeviceBatchAssembler:
                  "table_dev": torch.empty(nbytes, dtype=torch.uint8, device=self.device),
                  "table_pin": torch.empty(nbytes, dtype=torch.uint8).pin_memory(),
                  "uploaded": None}
+            if self.layout == "single" and self.norm_voxel:
+                from . import ops
+                c["parts"] = ops.voxel_norm_parts(batch, self.bins * h * w, self.device)
             self._cache[key] = c
         return c
 
@@ -142,8 +165,7 @@ class DeviceBatchAssembler:
             return [{k: raw_batch[k][i] for k in keys} for i in range(count)]
         return list(raw_batch)
 
-    def __call__(self, raw_batch, stages=_lib.ASSEMBLE_ALL):
-        from . import ops
+    def __call__(self, raw_batch, stages=_lib.ASSEMBLE_ALL | _lib.ASSEMBLE_STATS):
         samples = self._samples(raw_batch)
         if not samples:
             raise RefidHipError("DeviceBatchAssembler: empty batch")
@@ -153,9 +175,10 @@ class DeviceBatchAssembler:
         crop = None
         for b, s in enumerate(samples):
             fr, ev = s["frames"], s["events"]
-            if fr.dtype != torch.uint8 or fr.dim() != 4 or fr.shape[3] != 3 or fr.shape[0] != self.bins + 1:
-                raise RefidHipError(f"DeviceBatchAssembler: sample {b}: frames must be uint8 ({self.bins + 1}, H, W, 3) "
-                                    f"(blur0, blur1, {self.bins - 1} ground-truth frames), got {fr.dtype} {tuple(fr.shape)}")
+            if fr.dtype != torch.uint8 or fr.dim() != 4 or fr.shape[3] != 3 or fr.shape[0] != self.n_frames:
+                what = "blur, sharp" if self.layout == "single" else f"blur0, blur1, {self.bins - 1} ground-truth frames"
+                raise RefidHipError(f"DeviceBatchAssembler: sample {b}: frames must be uint8 ({self.n_frames}, H, W, 3) "
+                                    f"({what}), got {fr.dtype} {tuple(fr.shape)}")
             if ev.dtype != torch.float32 or ev.dim() != 2 or ev.shape[1] != 4:
                 raise RefidHipError(f"DeviceBatchAssembler: sample {b}: events must be float32 (N, 4) rows [t, x, y, p], "
                                     f"got {ev.dtype} {tuple(ev.shape)}")
@@ -195,6 +218,8 @@ class DeviceBatchAssembler:
         c["uploaded"] = torch.cuda.Event()
         c["uploaded"].record()
         nb = self.bins
+        if self.layout == "single":
+            return self._finish_single(samples, table, keep, c, B, h, w, stages)
         if self.layout == "blur":
             lq = torch.empty((B, 6 + 2 * (self.m - 1), h, w), dtype=torch.float32, device=self.device)
         else:
@@ -206,7 +231,21 @@ class DeviceBatchAssembler:
         desc.batch, desc.m, desc.n, desc.layout = B, self.m, self.n, self._layout
         desc.crop_h, desc.crop_w = h, w
         desc.scratch, desc.lq, desc.voxel, desc.gt = c["scratch"].data_ptr(), lq.data_ptr(), voxel.data_ptr(), gt.data_ptr()
-        ops.assemble_batch(desc, stages)
+        return self._launch(desc, stages, samples, table, keep, lq, voxel, gt)
+
+    def _finish_single(self, samples, table, keep, c, B, h, w, stages):
+        lq, gt = (torch.empty((B, 3, h, w), dtype=torch.float32, device=self.device) for _ in range(2))
+        voxel = torch.empty((B, self.bins, h, w), dtype=torch.float32, device=self.device)
+        desc = _lib.SingleDesc()
+        desc.samples_host, desc.samples_dev = C.addressof(table), c["table_dev"].data_ptr()
+        desc.batch, desc.bins, desc.crop_h, desc.crop_w, desc.norm = B, self.bins, h, w, int(self.norm_voxel)
+        desc.scratch = c["scratch"].data_ptr()
+        desc.parts = c["parts"].data_ptr() if self.norm_voxel else None
+        desc.lq, desc.voxel, desc.gt = lq.data_ptr(), voxel.data_ptr(), gt.data_ptr()
+        return self._launch(desc, stages, samples, table, keep, lq, voxel, gt)
+
+    def _launch(self, desc, stages, samples, table, keep, lq, voxel, gt):
+        self._run(desc, stages)
         self._last = (desc, table, keep)      # rerun() launches again from these
         cur = torch.cuda.current_stream(self.device)
         for t in keep:                        # (tensors the caller allocated on another stream stay valid until the kernels ran)

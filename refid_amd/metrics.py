@@ -225,3 +225,42 @@ class InterpolationMetrics:
         for k, v in self.interpo.items():
             s += f"\t # {k}: {v:.4f}"
         return [s]
+
+
+class SingleImageMetrics:
+    """The single-image model's bookkeeping (image_event_restoration_model.py:377-382, :457-484) and its one log line
+    (_log_validation_metric_values, :487-496), without any GPU dependency: one ``val.metrics`` dict, one sum per metric
+    name over the items (an item is one frame), ``finish`` divides by the item count and returns the last metric in dict
+    order (0. without metrics).  Same interface as ``ValidationMetrics``."""
+
+    def __init__(self, val_metrics):
+        self.opt_metrics = val_metrics
+        self.with_metrics = val_metrics is not None
+        self.cnt = 0
+        self.results = {k: 0 for k in (val_metrics or {})}
+
+    def metric_types(self):
+        return {o["type"] for o in self.opt_metrics.values()} if self.with_metrics else set()
+
+    def add_item(self, per_frame):
+        """per_frame: {'calculate_psnr': [value], 'calculate_ssim': [value]} of ONE sample (only the types in use)."""
+        self.cnt += 1
+        if not self.with_metrics:
+            return
+        for name, o in self.opt_metrics.items():
+            for v in per_frame[o["type"]]:
+                self.results[name] += v
+
+    def finish(self):
+        current = 0.
+        if self.with_metrics:
+            for k in self.results:
+                self.results[k] /= self.cnt
+                current = self.results[k]
+        return current
+
+    def log_lines(self, dataset_name):
+        s = f"Validation {dataset_name},\t"
+        for k, v in self.results.items():
+            s += f"\t # {k}: {v:.4f}"
+        return [s]

@@ -983,3 +983,40 @@ def assemble_batch(desc, stages=_lib.ASSEMBLE_ALL):
 def seq_assemble(desc, stages=_lib.ASSEMBLE_ALL):
     """Runs the pair-assembly kernels of csrc/sequence.hip for an _lib.SeqDesc on the current stream."""
     check(lib().refid_seq_assemble(C.byref(desc), int(stages), _stream()), "refid_seq_assemble")
+
+
+ASSEMBLE_STATS = _lib.ASSEMBLE_STATS
+
+
+def single_bins(bins):
+    """Checks the bin count of the single-image layout (>= 1, not 3); raises on an unsupported one."""
+    rc = lib().refid_single_bins(int(bins))
+    if rc < 0:
+        raise _lib.RefidHipError("refid_single_bins: " + lib().refid_last_error().decode("utf-8", "replace"))
+    return rc
+
+
+def voxel_norm_parts(batch, per_sample, device):
+    """The scratch of voxel_norm's statistics pass for (batch, per_sample): an int64 tensor of 8-byte words."""
+    return torch.empty(lib().refid_voxel_norm_parts(int(batch), int(per_sample)), dtype=torch.int64, device=device)
+
+
+def voxel_norm(x, out=None):
+    """voxel_norm (event_util.py:141-160) of every sample of a float32 CUDA tensor (B, ...): (x - mean) / std over each
+    sample's non-zero elements, zeros stay zero; a sample without spread becomes all zeros (the reference: NaN).
+    Deterministic (include/refid_hip.h).  ``out`` may be ``x``."""
+    if not x.is_cuda or x.dtype != torch.float32 or x.dim() < 2 or not x.is_contiguous() or x.numel() == 0:
+        raise _lib.RefidHipError("voxel_norm: a non-empty contiguous float32 CUDA tensor (B, ...) is required")
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.shape != x.shape or out.dtype != x.dtype or out.device != x.device or not out.is_contiguous():
+        raise _lib.RefidHipError("voxel_norm: out must match x")
+    batch, per = x.shape[0], x.numel() // x.shape[0]
+    parts = voxel_norm_parts(batch, per, x.device)
+    check(lib().refid_voxel_norm(x.data_ptr(), out.data_ptr(), batch, per, parts.data_ptr(), _stream()), "refid_voxel_norm")
+    return out
+
+
+def assemble_single(desc, stages=_lib.ASSEMBLE_ALL | _lib.ASSEMBLE_STATS):
+    """Runs the single-image assembly of csrc/sample.hip for an _lib.SingleDesc on the current stream."""
+    check(lib().refid_assemble_single(C.byref(desc), int(stages), _stream()), "refid_assemble_single")

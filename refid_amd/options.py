@@ -75,11 +75,20 @@ def assembler_from_dataset_opt(ds, device=None):
     / use_hflip / use_rot (hand it to ``CUDAPrefetcher(..., assemble=...)``; its ``draw(rng, H, W)`` draws a sample's crop and
     flips the way the reference does).  None when the key is absent or false.
     The layout follows the dataset class: the sharp-interpolation datasets (``*Sharp*``, image_sharp_npy_dataset.py) give
-    lq (2,3,h,w), the blur datasets with ``return_deblur_voxel`` the 6+2(m-1)-channel lq."""
+    lq (2,3,h,w), the blur datasets with ``return_deblur_voxel`` the 6+2(m-1)-channel lq.  A ``type`` containing
+    ``SingleImage`` (GoProSingleImageEventDataset, data/Single_image_npy_dataset.py) gives ``layout='single'`` with the
+    block's ``num_bins``: lq (3,h,w), gt (3,h,w), voxel (num_bins,h,w).  There ``norm_voxel`` counts as TRUE whatever the
+    block says: the reference's __getitem__ normalises unconditionally (:187; the switch at :172-173 is commented out)."""
     if not ds.get("device_assemble", False):
         return None
     from ._lib import RefidHipError
     from .data import DeviceBatchAssembler
+    if "singleimage" in str(ds.get("type", "")).lower():
+        if "num_bins" not in ds:
+            raise RefidHipError("device_assemble: the single-image dataset needs num_bins (Single_image_npy_dataset.py:48)")
+        return DeviceBatchAssembler(layout="single", num_bins=int(ds["num_bins"]), norm_voxel=True,
+                                    gt_size=ds.get("gt_size"), use_hflip=ds.get("use_hflip", False),
+                                    use_rot=ds.get("use_rot", False), device=device)
     if not ds.get("one_voxel_flag", True):
         raise RefidHipError("device_assemble: the per-pair voxel mode (one_voxel_flag: false) is not supported")
     sharp = "sharp" in str(ds.get("type", "")).lower()

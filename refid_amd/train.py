@@ -472,6 +472,7 @@ class TwoImageEventRecurrentRestorationModel:
         types = book.metric_types()
         was_training = self.net_g.training
         writer = FrameWriter(self.device) if save_img else None
+        seen = 0                                                # samples before this item (the reference's `cnt`)
         try:
             for val_data in dataloader:
                 self.feed_data(val_data)
@@ -491,12 +492,16 @@ class TwoImageEventRecurrentRestorationModel:
                     for key in ("seq", "origin_index"):
                         if key not in val_data or len(val_data[key]) < b:
                             raise RefidHipError(f"nondist_validation: save_img needs data['{key}'] with one entry per sample")
-                    stem = [os.path.join(self.opt["path"]["visualization"], dataset_name, val_data["seq"][i],
-                                         f"{val_data['origin_index'][i]}_{f:02d}") for i in range(b) for f in range(t)]
-                    batches = [(tail.pred_u8.view(b * t, h, w, 3), [s + ".png" for s in stem])]
+                    stem = self._val_stems(val_data, b, t, dataset_name, current_iter, seen)
+                    pick = [k for k, s in enumerate(stem) if s is not None]
+                    frames = (lambda u8: u8.view(b * t, h, w, 3)) if len(pick) == b * t else \
+                        (lambda u8: u8.view(b * t, h, w, 3)[pick])
+                    batches = [(frames(tail.pred_u8), [stem[k] + ".png" for k in pick])]
                     if save_gt:
-                        batches.append((tail.gt_u8.view(b * t, h, w, 3), [s + "_gt.png" for s in stem]))
-                    writer.dump(batches)
+                        batches.append((frames(tail.gt_u8), [stem[k] + "_gt.png" for k in pick]))
+                    if pick:
+                        writer.dump(batches)
+                seen += b
         finally:
             self.net_g.train(was_training)
             if writer is not None:
@@ -512,6 +517,12 @@ class TwoImageEventRecurrentRestorationModel:
                     for name, value in res.items():
                         tb_logger.add_scalar(f"metrics/{name}", value, current_iter)
         return current_metric
+
+    def _val_stems(self, val_data, b, t, dataset_name, current_iter, seen):
+        """The file names (without '.png' / '_gt.png') of an item's b*t frames, sample-major; None: the frame is not
+        written.  This class: {visualization}/{name}/{seq}/{origin_index}_{frame:02d} (:435-458)."""
+        return [os.path.join(self.opt["path"]["visualization"], dataset_name, val_data["seq"][i],
+                             f"{val_data['origin_index'][i]}_{f:02d}") for i in range(b) for f in range(t)]
 
     def _val_book(self, val, use_image):
         """The bookkeeping of this class's validation loop: deblur / interpolation / total (:362-379, :460-512)."""
@@ -679,6 +690,32 @@ class ImageEventRestorationModel(TwoImageEventRecurrentRestorationModel):
             self.output = torch.cat(outs, dim=0)
         self.net_g.train()
 
+    # ---- validation (image_event_restoration_model.py:372-496): the base class's loop, tail and PNG writer (a 4-D output
+    # is one frame per sample) with this model's book, attributes and file names --------------------------------------
+    # (feed_data stays the base class's: the reference's requires `seq` and `origin_index` (:105-109), but training batches
+    # without them are fed to this class -- tests/test_hip_evhinet.py -- so they are required only where they are used,
+    # by the image dumps of the loop.)
+    def _val_book(self, val, use_image):
+        """One ``val.metrics`` dict, one sum per name, one log line (:377-382, :457-496)."""
+        metrics.check_metric_options(val, use_image, groups=("metrics",))
+        return metrics.SingleImageMetrics(val.get("metrics"))
+
+    def _val_results(self, book):
+        self.metric_results = book.results
+        return (book.results,)
+
+    def _val_stems(self, val_data, b, t, dataset_name, current_iter, seen):
+        """:428-450.  Testing: {visualization}/{name}/{seq}/{origin_index}.  Training (opt['is_train']): only the item
+        with cnt == 1, the second of the loader, as {visualization}/{origin_index}/{origin_index}_{iter}.  NOT reproduced:
+        the reference's NameError at cnt == 0 (its path variables are unset until cnt == 1), and its writing of every later
+        item over the cnt == 1 path, which it never updates; both items are simply not written here."""
+        vis = self.opt["path"]["visualization"]
+        if self.opt.get("is_train"):
+            return [os.path.join(vis, str(val_data["origin_index"][i]), f"{val_data['origin_index'][i]}_{current_iter}")
+                    if seen + i == 1 else None for i in range(b) for _ in range(t)]
+        return [os.path.join(vis, dataset_name, val_data["seq"][i], f"{val_data['origin_index'][i]}")
+                for i in range(b) for _ in range(t)]
+
 
 class TwoSharpImageEventRecurrentRestorationModel(TwoImageEventRecurrentRestorationModel):
     """Sharp key frames (reference twoSharpImage_event_recurrent_model.py): the same network, step and validation loop;
@@ -714,9 +751,16 @@ class Test_TwoSharpImageEventRecurrentRestorationModel(TwoSharpImageEventRecurre
     TEST_ONLY = True
 
 
+class TestImageEventRestorationModel(ImageEventRestorationModel):
+    """Test_image_event_restoration_model.py:16: the single-image model for the test YAMLs; no training settings."""
+    __test__ = False
+    VAL_DATASET = "test"
+    TEST_ONLY = True
+
+
 MODEL_CLASSES = {c.__name__: c for c in (TwoImageEventRecurrentRestorationModel, ImageEventRestorationModel,
                                          TwoSharpImageEventRecurrentRestorationModel,
-                                         TestTwoImageEventRecurrentRestorationModel,
+                                         TestTwoImageEventRecurrentRestorationModel, TestImageEventRestorationModel,
                                          Test_TwoSharpImageEventRecurrentRestorationModel)}
 # the GoPro 7- and 15-skip test YAMLs spell the sharp test class without the underscore; the reference cannot resolve that
 MODEL_CLASSES["TestTwoSharpImageEventRecurrentRestorationModel"] = Test_TwoSharpImageEventRecurrentRestorationModel
