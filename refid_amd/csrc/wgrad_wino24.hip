@@ -36,17 +36,24 @@
 // (coordinates advance by scalar increments).
 // Split-K slabs [split][24][o][i] persist over the T recurrent steps exactly like wgrad_wino.hip's (phase 1 / 2 / 3); the
 // bias gradient is the transform point (1, 1) of Gy dY Gx^T (rows {1,1} x {1,1,1,1}: the tile sum), summed by wave 1.
+//
+// The two 3x3 kernels -- wgrad_wino24_kernel<NS> (four waves, two stages) and wgrad_wino24_pair_kernel (eight waves, three-stage
+// ring) -- are built from ONE set of pieces: the tile walk (wgrad_w24_walk.h), W24Dma (lane roles, the two row movers, the
+// request), W24Bases, w24_tile, w24_two_stage, w24_store_slabs / w24_store_bias.  What a kernel keeps to itself: its LDS layout
+// (where a stage's tiles go), its waves' share of a request (W24Share), and the pair form's ring schedule (step()).
+// wgrad_wino24_down_kernel<NS> (conv_down, algo 7) keeps its own copy of all of it: built from the same pieces it gave the same
+// bits but ran 0.3 - 1.4 % slower (profiles/w24_shared_pieces_ab.txt).  The walk and W24Dma keep its two parameters (rows per
+// K tile, input pixels per tile pixel); tools/probes/w24_walk_host_check.cpp walks both geometries.
 #include "wgrad_args.h"
+#include "wgrad_w24_walk.h"
 #include <cstdlib>
 #include <type_traits>
 
-// Timing experiments only (tools/probes/w24_ablate.py builds the variants; results are wrong for n != 0):
+// Timing experiments only (tools/probes/w24_ablate.py builds the variants; results are wrong for n != 0).  The switches sit in
+// the shared pieces, so both 3x3 kernels carry them (conv_down's kernel has none):
 //   1: no DMA requests (stale tiles: no global traffic, no LDS writes)   2: no MFMAs (operands kept alive)
 //   3: no LDS reads (operands from opaque registers)   4: no barrier   5: 1 + 4   6: 1 + 3 + 4 (transforms + MFMAs alone)
-//   7: every request fetches the workgroup's FIRST tile again (same instructions, same LDS writes, cache hits instead of HBM)
-#ifndef REFID_W24_ABLATE
-#define REFID_W24_ABLATE 0
-#endif
+//   7: every request fetches the workgroup's FIRST tile again (wgrad_w24_walk.h)
 #define W24_NO_DMA (REFID_W24_ABLATE == 1 || REFID_W24_ABLATE == 5 || REFID_W24_ABLATE == 6)
 #define W24_NO_MFMA (REFID_W24_ABLATE == 2)
 #define W24_NO_LDS (REFID_W24_ABLATE == 3 || REFID_W24_ABLATE == 6)
@@ -59,7 +66,8 @@ __device__ __forceinline__ float w24_fake(float seed) { asm volatile("" : "+v"(s
 constexpr int IT = 32;                         // input-channel tile; output-channel tile = 32 NS (NS = 2; 1 for c_o <= 32): the
                                                // gradient tile is staged as NS 32-channel halves
 constexpr int TC = 4;                          // Winograd tile columns per K tile (tile rows: 2 = the MFMA K halves)
-constexpr int GH = 4, GW = 4 * TC;             // output-gradient pixels of a K tile
+constexpr int GH = 4, GW = W24_GW;             // output-gradient pixels of a K tile
+static_assert(GW == 4 * TC, "four-pixel tile columns");
 constexpr int XH = GH + 2, XW = GW + 2;        // input halo
 constexpr int X_BYTES = XH * XW * IT * 4;      // 13,824
 constexpr int GS_BYTES = GH * GW * 32 * 4;     // 8,192 per 32-channel half
@@ -69,6 +77,8 @@ constexpr int NXI = 24;
 typedef __attribute__((address_space(3))) void* lds_ptr24;
 typedef __attribute__((address_space(3))) const float lds_cf24;     // typed LDS pointers: 32-bit, ds_read instructions
 typedef float f32x2 __attribute__((ext_vector_type(2)));
+template <int V>
+using w24_ic = std::integral_constant<int, V>;
 
 // {a.lo or a.hi, b.lo or b.hi} in ONE instruction; the result is opaque to the compiler, which otherwise un-packs every
 // transform instruction downstream of a pair it would have to assemble from two registers
@@ -152,89 +162,87 @@ struct W24Row {
     }
 };
 
-template <int NS>
-__global__ __launch_bounds__(256, NS == 2 ? 2 : 3) void wgrad_wino24_kernel(const W24Args a) {
-    constexpr int OT = 32 * NS, BUF_BYTES = buf_bytes(NS);
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int li = lane & 31, kh = lane >> 5;
-    const int co0 = blockIdx.z * OT, ci0 = blockIdx.y * IT;
-    const int split = blockIdx.x;
-    const int Hin = a.H, Win = a.W;      // (for the address arithmetic; loaded here, their place in the prologue's schedule)
+// ---- The pieces the 3x3 kernels are built from --------------------------------------------------------------------------
 
-    // the input-channel tile lies in one source (host: c_a % 32 == 0 for two sources), so the descriptor is workgroup-uniform;
-    // a tile beyond the sources (first recurrent step: no second source yet) keeps a valid descriptor, all lanes out of range
-    const bool xFromA = ci0 < a.Ca || ci0 >= a.Ctot;
-    const int xld = xFromA ? a.ldA : a.ldB;
-    const long long gpixAll = (long long)a.N * a.Ho * a.Wo, xpixAll = (long long)a.N * Hin * Win;
-    const int limG = (int)min(gpixAll * a.ldG * 4, 0x7fffffffLL), limX = (int)min(xpixAll * xld * 4, 0x7fffffffLL);
-    const int ntAll = a.ntiles * a.groups;
-    const int chunk = (ntAll + a.nsplit - 1) / a.nsplit;
-    const int p0 = min(split * chunk, ntAll), p1 = min(p0 + chunk, ntAll);
+// One halo row (18 pixels at o0: two 16-byte pieces of 8 pixels, a 4-byte piece of 2) and one gradient row of a 32-channel
+// half (two 16-byte pieces) by LDS-DMA; the offsets are final (bytes into the descriptor, out of range = zero fill).
+__device__ __forceinline__ void w24_halo_row(__amdgpu_buffer_rsrc_t rs, char* dst, int o0, int o1, int o2) {
+    if (W24_NO_DMA) return;
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr24)dst, 16, o0, 0, 0, 0);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr24)(dst + 1024), 16, o1, 0, 0, 0);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr24)(dst + 2048), 4, o2, 0, 0, 0);
+}
+__device__ __forceinline__ void w24_grad_row(__amdgpu_buffer_rsrc_t rs, char* dst, int o0, int o1) {
+    if (W24_NO_DMA) return;
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr24)dst, 16, o0, 0, 0, 0);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr24)(dst + 1024), 16, o1, 0, 0, 0);
+}
 
-    // coordinates of the next tile to request (wave-uniform; advanced by increments)
-    int qg, qn, qy, qx;
-    {
-        int t = p0 < ntAll ? p0 : 0;
-        qg = t / a.ntiles; t -= qg * a.ntiles;
-        qx = t % a.tilesX; t /= a.tilesX;
-        qy = t % a.tilesY; qn = t / a.tilesY;
+// A wave's share of a request (wave-uniform): halo rows xr0, xr0 + xstep (at most two) below xrEnd, and gradient (half, row)
+// pieces q = (rows per K tile) half + row = q0 .. q0 + nq - 1, nq <= 3: three DMA instructions per halo row, two per piece.
+struct W24Share { int xr0, xstep, xrEnd, q0, nq; };
+
+// The DMA side of a wave of the 3x3 kernels: the walk, the input-channel tile's source and the lane's role.  (conv_down's kernel
+// has its own copy, with two input pixels per tile pixel.)
+// 16-byte pieces: lane -> (pixel lane>>3 of 8, channel quad lane&7); 4-byte tail piece of a halo row: lane -> (pixel 16 +
+// lane>>5, channel lane&31).  Three per-lane constants (byte offset of the lane inside a piece); a piece's offset is
+// (tile-dependent scalar) + constant.  FAST path (the tile touches neither the left nor the right image border and the
+// channel tiles are full -- every layer of the network away from the borders): no per-lane test at all, an out-of-image ROW
+// is a scalar select of an out-of-range base: one v_add per DMA instruction.  Otherwise out-of-range columns / channels are
+// forced out of range with OR masks.
+struct W24Dma {
+    static constexpr int OOB = 0x7ff00000;     // base of a dead row: + any lane constant (< 1 MB) stays out of range
+    static constexpr int XROW_BYTES = XW * IT * 4, GROW_BYTES = GW * 32 * 4, GHALF_BYTES = GH * GROW_BYTES;      // in LDS
+    W24Walk<GH, 1> w;
+    int xq, xt, gq;                            // the lane's first channel in a 16-byte / 4-byte input piece, a gradient piece
+    int xlc, xlt, glc;                         // ... and its bytes from the piece's first pixel
+    int limG, limX;                            // descriptor sizes
+    int xRowB, gRowB;                          // bytes per tile-pixel row of the input / the gradient
+    bool fullch;                               // workgroup-uniform (pair form: wave-uniform)
+
+    // The input-channel tile lies in one source (host: c_a % 32 == 0 for two sources), so the descriptor is wave-uniform;
+    // a tile beyond the sources (first recurrent step: no second source yet) keeps a valid descriptor, all lanes out of range.
+    __device__ __forceinline__ void init(const W24Args& a, int lane, int split, int ci0, int co0, int cot) {
+        const int Hin = a.H, Win = a.W;
+        const bool xFromA = ci0 < a.Ca || ci0 >= a.Ctot;
+        const int xld = xFromA ? a.ldA : a.ldB;
+        const long long gpixAll = (long long)a.N * a.Ho * a.Wo, xpixAll = (long long)a.N * Hin * Win;
+        limG = (int)min(gpixAll * a.ldG * 4, 0x7fffffffLL);
+        limX = (int)min(xpixAll * xld * 4, 0x7fffffffLL);
+        w.init(a, split, xFromA, xld, Hin, Win, a.pad, a.pad);
+        xq = ci0 + (lane & 7) * 4; xt = ci0 + (lane & 31); gq = co0 + (lane & 7) * 4;
+        xlc = ((lane >> 3) * xld + (xFromA ? xq : xq - a.Ca)) * 4;
+        xlt = ((lane >> 5) * xld + (xFromA ? xt : xt - a.Ca)) * 4;
+        glc = ((lane >> 3) * a.ldG + gq) * 4;
+        fullch = ci0 + IT <= a.Ctot && co0 + cot <= a.Co;
+        xRowB = Win * xld * 4; gRowB = a.Wo * a.ldG * 4;
     }
-    // ---- DMA roles.  16-byte pieces: lane -> (pixel lane>>3 of 8, channel quad lane&7); 4-byte tail piece of a halo row:
-    // lane -> (pixel 16 + lane>>5, channel lane&31).  Three per-lane constants (byte offset of the lane inside a piece); a
-    // piece's offset is (tile-dependent scalar) + constant.  FAST path (the tile touches neither the left nor the right image
-    // border and the channel tiles are full -- every layer of the network away from the borders): no per-lane test at all,
-    // an out-of-image ROW is a scalar select of an out-of-range base: one v_add per DMA instruction.  Otherwise out-of-range
-    // columns / channels are forced out of range with OR masks.
-    const int xq = ci0 + (lane & 7) * 4, xt = ci0 + (lane & 31), gq = co0 + (lane & 7) * 4;
-    const int xlc = ((lane >> 3) * xld + (xFromA ? xq : xq - a.Ca)) * 4;      // bytes from the piece's first pixel
-    const int xlt = ((lane >> 5) * xld + (xFromA ? xt : xt - a.Ca)) * 4;
-    const int glc = ((lane >> 3) * a.ldG + gq) * 4;
-    const bool fullch = ci0 + IT <= a.Ctot && co0 + OT <= a.Co;                     // workgroup-uniform
-    constexpr int OOB = 0x7ff00000;                        // base of a dead row: + any lane constant (< 1 MB) stays out of range
-    // Scalar state of the walk: the current time step's tensors (reloaded from the argument block only when the walk crosses
-    // into the next step -- an s_load per request would put a full scalar-memory latency in front of every tile), the byte
-    // offset of the next tile's first halo / gradient pixel (advanced by one tile width; recomputed at the end of a tile row)
-    const int xRowB = Win * xld * 4, gRowB = a.Wo * a.ldG * 4;      // bytes per image row
-    auto x_origin = [&](int n, int ty, int tx) {           // byte offset of pixel (ty GH - pad, tx GW - pad) of sample n
-        return ((n * Hin + (ty * GH - a.pad)) * Win + (tx * GW - a.pad)) * xld * 4;
-    };
-    const float* gPtr = a.g[qg];
-    const float* xPtr = xFromA ? a.inA[qg] : a.inB[qg];
-    int xTile = x_origin(qn, qy, qx);
-    int gTile = ((qn * a.Ho + qy * GH) * a.Wo + qx * GW) * a.ldG * 4;
-    auto request = [&](int buf) {
-        const int oy0 = qy * GH, ox0 = qx * GW;
-        const int iy0 = oy0 - a.pad, ix0 = ox0 - a.pad;
-        const __amdgpu_buffer_rsrc_t rsG = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(gPtr), 0, limG, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xPtr), 0, limX, 0x00020000);
-        char* xdst = smem + buf * BUF_BYTES;
-        char* gdst = xdst + X_BYTES;
-        const bool fast = fullch && ix0 >= 0 && ix0 + XW <= a.W && ox0 + GW <= a.Wo && xld * 8 * 4 < 0x100000 && a.ldG * 8 * 4 < 0x100000;
-        // gradient (half, row) pairs q = 4 half + row of this wave: NS = 2: wave 0 q = 0, wave 1 q = 1, wave 2 q = 2..4, wave 3
-        // q = 5..7 (with the halo rows: 8 / 8 / 9 / 9 DMA instructions); NS = 1: waves 2 / 3 two rows each (6 / 6 / 7 / 7)
-        const int q0 = NS == 2 ? (wave < 2 ? wave : 3 * wave - 4) : 2 * (wave - 2), nq = NS == 2 ? (wave < 2 ? 1 : 3) : (wave < 2 ? 0 : 2);
+
+    // the wave's share of the cursor's tile into the stage at xdst / gdst (gradient half `sub` at gdst + sub x half), then on.
+    // (The walk's origin offset is a.pad, read from the argument block where it is used: held in the walk it lived in scalar
+    // registers across the K loop.)
+    __device__ __forceinline__ void request(const W24Args& a, const W24Share sh, char* xdst, char* gdst, int lane) {
+        const int oy0 = w.qy * GH, ox0 = w.qx * GW, iy0 = oy0 - a.pad, ix0 = ox0 - a.pad;
+        const __amdgpu_buffer_rsrc_t rsG = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(w.gPtr), 0, limG, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(w.xPtr), 0, limX, 0x00020000);
+        const int xPc = 8 * w.xld * 4, gPc = 8 * a.ldG * 4;              // bytes per 8-pixel piece
+        const bool fast = fullch && ix0 >= 0 && ix0 + XW <= a.W && ox0 + GW <= a.Wo && xPc < 0x100000 && gPc < 0x100000;
         if (fast) {
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
-                const int r = wave + 4 * k;
-                if (r < XH && !W24_NO_DMA) {
-                    const int base = (unsigned)(iy0 + r) < (unsigned)a.H ? xTile + r * xRowB : OOB;
-                    char* dst = xdst + r * (XW * IT * 4);
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_ptr24)dst, 16, base + xlc, 0, 0, 0);
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_ptr24)(dst + 1024), 16, base + 8 * xld * 4 + xlc, 0, 0, 0);
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_ptr24)(dst + 2048), 4, base + 16 * xld * 4 + xlt, 0, 0, 0);
+                const int r = sh.xr0 + k * sh.xstep;
+                if (r < sh.xrEnd) {
+                    const int base = (unsigned)(iy0 + r) < (unsigned)a.H ? w.xTile + r * xRowB : OOB;
+                    w24_halo_row(rsX, xdst + r * XROW_BYTES, base + xlc, base + xPc + xlc, base + 2 * xPc + xlt);
                 }
             }
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
-                if (k < nq && !W24_NO_DMA) {
-                    const int q = q0 + k, r = q & 3, sub = q >> 2;
-                    const int base = oy0 + r < a.Ho ? gTile + r * gRowB + sub * 128 : OOB;
-                    char* dst = gdst + sub * GS_BYTES + r * (GW * 32 * 4);
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsG, (lds_ptr24)dst, 16, base + glc, 0, 0, 0);
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsG, (lds_ptr24)(dst + 1024), 16, base + 8 * a.ldG * 4 + glc, 0, 0, 0);
+                if (k < sh.nq) {
+                    const unsigned q = sh.q0 + k;
+                    const int r = q % GH, sub = q / GH;
+                    const int base = oy0 + r < a.Ho ? w.gTile + r * gRowB + sub * 128 : OOB;
+                    w24_grad_row(rsG, gdst + sub * GHALF_BYTES + r * GROW_BYTES, base + glc, base + gPc + glc);
                 }
             }
         } else {
@@ -245,180 +253,205 @@ __global__ __launch_bounds__(256, NS == 2 ? 2 : 3) void wgrad_wino24_kernel(cons
             const int cx1 = (unsigned)(ix0 + 8 + l8) < (unsigned)a.W ? 0 : -1;
             const int cxt = (unsigned)(ix0 + 16 + l32) < (unsigned)a.W ? 0 : -1;
             const int cg0 = ox0 + l8 < a.Wo ? 0 : -1, cg1 = ox0 + 8 + l8 < a.Wo ? 0 : -1;
-            // halo rows: wave w moves row w, waves 0 / 1 also rows 4 / 5
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
-                const int r = wave + 4 * k;
-                if (r < XH && !W24_NO_DMA) {
+                const int r = sh.xr0 + k * sh.xstep;
+                if (r < sh.xrEnd) {
                     const int rbad = (unsigned)(iy0 + r) < (unsigned)a.H ? 0 : -1;
-                    const int base = xTile + r * xRowB;                                   // bytes, < 2^31 for live lanes (host check)
-                    char* dst = xdst + r * (XW * IT * 4);
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_ptr24)dst, 16, (base + xlc) | xbadq | rbad | cx0, 0, 0, 0);
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_ptr24)(dst + 1024), 16,
-                                                             (base + 8 * xld * 4 + xlc) | xbadq | rbad | cx1, 0, 0, 0);
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_ptr24)(dst + 2048), 4,
-                                                             (base + 16 * xld * 4 + xlt) | xbadt | rbad | cxt, 0, 0, 0);
+                    const int base = w.xTile + r * xRowB;                                 // bytes, < 2^31 for live lanes (host check)
+                    w24_halo_row(rsX, xdst + r * XROW_BYTES, (base + xlc) | xbadq | rbad | cx0,
+                                 (base + xPc + xlc) | xbadq | rbad | cx1, (base + 2 * xPc + xlt) | xbadt | rbad | cxt);
                 }
             }
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
-                if (k < nq && !W24_NO_DMA) {
-                    const int q = q0 + k, r = q & 3, sub = q >> 2;
-                    const int rbad = oy0 + r < a.Ho ? 0 : -1;
-                    const int base = gTile + r * gRowB + sub * 128;
-                    const int gbad = sub ? gbad1 : gbad0;
-                    char* dst = gdst + sub * GS_BYTES + r * (GW * 32 * 4);
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsG, (lds_ptr24)dst, 16, (base + glc) | gbad | rbad | cg0, 0, 0, 0);
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsG, (lds_ptr24)(dst + 1024), 16,
-                                                             (base + 8 * a.ldG * 4 + glc) | gbad | rbad | cg1, 0, 0, 0);
+                if (k < sh.nq) {
+                    const unsigned q = sh.q0 + k;
+                    const int r = q % GH, sub = q / GH;
+                    const int rbad = oy0 + r < a.Ho ? 0 : -1, gbad = sub ? gbad1 : gbad0;
+                    const int base = w.gTile + r * gRowB + sub * 128;
+                    w24_grad_row(rsG, gdst + sub * GHALF_BYTES + r * GROW_BYTES, (base + glc) | gbad | rbad | cg0,
+                                 (base + gPc + glc) | gbad | rbad | cg1);
                 }
             }
         }
-        // advance
-        if (REFID_W24_ABLATE == 7) return;
-        qx += 1;
-        if (qx != a.tilesX) {
-            xTile += GW * xld * 4;
-            gTile += GW * a.ldG * 4;
-        } else {
-            qx = 0;
-            qy += 1;
-            if (qy == a.tilesY) {
-                qy = 0;
-                qn += 1;
-                if (qn == a.N) {
-                    qn = 0;
-                    qg = min(qg + 1, a.groups - 1);
-                    gPtr = a.g[qg];
-                    xPtr = xFromA ? a.inA[qg] : a.inB[qg];
-                }
-            }
-            xTile = x_origin(qn, qy, 0);
-            gTile = (qn * a.Ho + qy * GH) * a.Wo * a.ldG * 4;
-        }
-    };
+        w.advance(a, a.pad, a.pad);
+    }
+};
 
-    f32x16 acc[6][NS];                                     // [j][o half]
+template <int NP, int NS>
+__device__ __forceinline__ void w24_zero(f32x16 (&acc)[NP][NS]) {
 #pragma unroll
-    for (int j = 0; j < 6; ++j)
+    for (int j = 0; j < NP; ++j)
 #pragma unroll
         for (int sm = 0; sm < NS; ++sm)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[j][sm][r] = 0.f;
-    float bs[NS];
-#pragma unroll
-    for (int sm = 0; sm < NS; ++sm) bs[sm] = 0.f;
+}
 
-    // The LDS bases point into buffer 0 and never change: buffer 1 is 118 x 256 bytes further, an immediate of the same
-    // ds_read2st64 (the largest unit offset is 218 of 255), so the K loop is written for a PAIR of tiles (buffer 0, buffer 1)
-    // and carries no address arithmetic at all.
-    static_assert(BUF_BYTES % 256 == 0 && (BUF_BYTES + X_BYTES + (NS - 1) * GS_BYTES + 4 * GW * 32 * 4) / 256 < 256, "ds_read2st64 offset range");
-    lds_cf24* xe = (lds_cf24*)smem + (2 * kh) * (XW * IT) + li;
-    lds_cf24* ge = (lds_cf24*)(smem + X_BYTES) + (2 * kh) * (GW * 32) + li;
-    lds_cf24* xb[4] = {xe, xe + IT, xe + 2 * IT, xe + 3 * IT};
-    lds_cf24* gb[4] = {ge, ge + 32, ge + 2 * 32, ge + 3 * 32};
-    asm volatile("" : "+v"(xb[0]), "+v"(xb[1]), "+v"(xb[2]), "+v"(xb[3]), "+v"(xe));
-    asm volatile("" : "+v"(gb[0]), "+v"(gb[1]), "+v"(gb[2]), "+v"(gb[3]));
-
-    auto kloop = [&](auto TI) {
-        constexpr int I = decltype(TI)::value;
-        using R = W24Row<I>;
-        auto tile = [&](auto BUF) {
-            constexpr int BO = decltype(BUF)::value * (BUF_BYTES / 4);          // floats
-            lds_cf24* xbb[4] = {xb[0] + BO, xb[1] + BO, xb[2] + BO, xb[3] + BO};
-            lds_cf24* gbb[4] = {gb[0] + BO, gb[1] + BO, gb[2] + BO, gb[3] + BO};
-            f32x2 t[6], p4, p5;
+// The LDS bases of a lane (see W24Row) point into stage 0 of the wave's input region (xreg) and of the gradient region (greg)
+// at the lane's tile row (rowbase = 2 kh; conv_down 3 kh) and never change: the other stages are immediates of the same
+// ds_read2st64 (each kernel asserts its range), so the K loop is written for a pair or triple of tiles and carries no address
+// arithmetic at all.
+struct W24Bases {
+    lds_cf24 *xe, *xb[4], *gb[4];
+    __device__ __forceinline__ W24Bases(char* xreg, char* greg, int rowbase, int li) {
+        xe = (lds_cf24*)xreg + rowbase * (XW * IT) + li;
+        lds_cf24* ge = (lds_cf24*)greg + rowbase * (GW * 32) + li;
 #pragma unroll
-            for (int s = 0; s < TC; s += 2) {
-                // window columns 4s+k (low half) and 4s+4+k (high half); columns 0 / 1 of the low half are the previous
-                // pair's columns 4 / 5 of the high half (p4 / p5 carry them; the tile's first two columns are read as a pair)
-                R::x_rows(xbb, s, t);
-                if (s == 0) {
-                    const f32x2 a01 = R::x_rows01(xe + BO);
-                    t[0] = w24_pair<0, 0>(a01, t[4]);
-                    t[1] = w24_pair<1, 0>(a01, t[5]);
-                } else {
-                    t[0] = w24_pair<1, 0>(p4, t[4]);
-                    t[1] = w24_pair<1, 0>(p5, t[5]);
-                }
-                p4 = t[4]; p5 = t[5];
-                f32x2 v[6];
-                R::v_cols(t, v);
-#pragma unroll
-                for (int sm = 0; sm < NS; ++sm) {
-                    f32x2 x[4], z[6];
-                    R::g_rows(gbb, s, sm, x);
-                    R::z_cols(x, z);
-                    if constexpr (I == 1) bs[sm] += z[1][0] + z[1][1];     // point (1, 1) = sum of the 2x4 gradient tile
-#pragma unroll
-                    for (int h = 0; h < 2; ++h)
-#pragma unroll
-                        for (int j = 0; j < 6; ++j) {
-                            if (W24_NO_MFMA) { asm volatile("" :: "v"(v[j][h]), "v"(z[j][h])); continue; }
-                            acc[j][sm] = __builtin_amdgcn_mfma_f32_32x32x2f32(v[j][h], z[j][h], acc[j][sm], 0, 0, 0);
-                        }
-                }
-            }
-        };
-        auto sync = [&] {
-            __builtin_amdgcn_s_waitcnt(0x0F70);            // vmcnt(0): this wave's pieces of the tile have landed
-            if (!W24_NO_BAR) __builtin_amdgcn_s_barrier(); // ... everybody's; and everybody is done with the other buffer
-            __builtin_amdgcn_sched_barrier(0);
-        };
-        // (pairs in the loop, an odd last tile after it: an exit from the middle of the loop body makes the register allocator
-        //  copy all 192 accumulators on one of the two paths)
-        const int npairs = (p1 - p0) >> 1;
-        if (p0 < p1) request(0);
-        for (int i = 0; i < npairs; ++i) {
-            sync();
-            request(1);
-            tile(std::integral_constant<int, 0>{});
-            sync();
-            if (p0 + 2 * i + 2 < p1) request(0);
-            tile(std::integral_constant<int, 1>{});
-        }
-        if ((p1 - p0) & 1) {
-            sync();
-            tile(std::integral_constant<int, 0>{});
-        }
-    };
-    switch (wave) {
-        case 0: kloop(std::integral_constant<int, 0>{}); break;
-        case 1: kloop(std::integral_constant<int, 1>{}); break;
-        case 2: kloop(std::integral_constant<int, 2>{}); break;
-        default: kloop(std::integral_constant<int, 3>{}); break;
+        for (int k = 0; k < 4; ++k) { xb[k] = xe + k * IT; gb[k] = ge + k * 32; }
+        asm volatile("" : "+v"(xb[0]), "+v"(xb[1]), "+v"(xb[2]), "+v"(xb[3]), "+v"(xe));
+        asm volatile("" : "+v"(gb[0]), "+v"(gb[1]), "+v"(gb[2]), "+v"(gb[3]));
     }
+};
 
-    // ---- slab: [split][xi][co][ci]; D[ci][co]: lane li = output channel, register quad = 4 ci ------
+// One K tile of F(3,2) row I from the stage XO / GO floats behind the bases: 6 x NS x 4 MFMAs; row 1 also adds up the gradient
+// tile (bs: the bias gradient).  Plain `inline` on purpose: inlined early as __forceinline__, the same body is scheduled so that
+// the backend splits ~10 % of the packed transform instructions into single ones, and the 64 -> 32 layer ran 1.8 % slower.
+template <int I, int NS, int XO, int GO>
+__device__ inline void w24_tile(const W24Bases& b, f32x16 (&acc)[6][NS], float (&bs)[NS]) {
+    using R = W24Row<I>;
+    lds_cf24* xbb[4] = {b.xb[0] + XO, b.xb[1] + XO, b.xb[2] + XO, b.xb[3] + XO};
+    lds_cf24* gbb[4] = {b.gb[0] + GO, b.gb[1] + GO, b.gb[2] + GO, b.gb[3] + GO};
+    f32x2 t[6], p4, p5;
 #pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        float* sl = a.slabs + ((long long)(split * NXI + wave * 6 + j) * a.CoP) * a.CiP;
+    for (int s = 0; s < TC; s += 2) {
+        // window columns 4s+k (low half) and 4s+4+k (high half); columns 0 / 1 of the low half are the previous
+        // pair's columns 4 / 5 of the high half (p4 / p5 carry them; the tile's first two columns are read as a pair)
+        R::x_rows(xbb, s, t);
+        if (s == 0) {
+            const f32x2 a01 = R::x_rows01(b.xe + XO);
+            t[0] = w24_pair<0, 0>(a01, t[4]);
+            t[1] = w24_pair<1, 0>(a01, t[5]);
+        } else {
+            t[0] = w24_pair<1, 0>(p4, t[4]);
+            t[1] = w24_pair<1, 0>(p5, t[5]);
+        }
+        p4 = t[4]; p5 = t[5];
+        f32x2 v[6];
+        R::v_cols(t, v);
 #pragma unroll
         for (int sm = 0; sm < NS; ++sm) {
-            const int co = co0 + sm * 32 + li;
+            f32x2 x[4], z[6];
+            R::g_rows(gbb, s, sm, x);
+            R::z_cols(x, z);
+            if constexpr (I == 1) bs[sm] += z[1][0] + z[1][1];     // point (1, 1) = sum of the 2x4 gradient tile
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int j = 0; j < 6; ++j) {
+                    if (W24_NO_MFMA) { asm volatile("" :: "v"(v[j][h]), "v"(z[j][h])); continue; }
+                    acc[j][sm] = __builtin_amdgcn_mfma_f32_32x32x2f32(v[j][h], z[j][h], acc[j][sm], 0, 0, 0);
+                }
+        }
+    }
+}
+
+// the wave-uniform switch to one of the four K loops: f(integral_constant<row>)
+template <class F>
+__device__ __forceinline__ void w24_for_row(int row, F&& f) {
+    switch (row) {
+        case 0: f(w24_ic<0>{}); break;
+        case 1: f(w24_ic<1>{}); break;
+        case 2: f(w24_ic<2>{}); break;
+        default: f(w24_ic<3>{}); break;
+    }
+}
+
+// Two stages, n tiles: request(stage) one tile ahead, tile(integral_constant<stage>).  (Pairs in the loop, an odd last tile
+// after it: an exit from the middle of the loop body makes the register allocator copy all the accumulators on one of the
+// two paths.)
+template <class Req, class Tile>
+__device__ __forceinline__ void w24_two_stage(int n, Req&& request, Tile&& tile) {
+    auto sync = [] {
+        __builtin_amdgcn_s_waitcnt(0x0F70);            // vmcnt(0): this wave's pieces of the tile have landed
+        if (!W24_NO_BAR) __builtin_amdgcn_s_barrier(); // ... everybody's; and everybody is done with the other stage
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    if (n > 0) request(0);
+    for (int i = 0; i < (n >> 1); ++i) {
+        sync();
+        request(1);
+        tile(w24_ic<0>{});
+        sync();
+        if (2 * i + 2 < n) request(0);
+        tile(w24_ic<1>{});
+    }
+    if (n & 1) {
+        sync();
+        tile(w24_ic<0>{});
+    }
+}
+
+// acc -> the wave's NP planes [co][ci] of the slab image, from plane `plane0` on; D[ci][co]: lane = output channel co (+ 32
+// per half), register quad = 4 input channels from ci on (ci includes the lane's 4 kh)
+template <int NP, int NS>
+__device__ __forceinline__ void w24_store_slabs(const W24Args& a, int plane0, const f32x16 (&acc)[NP][NS], int co, int ci) {
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+        float* sl = a.slabs + ((long long)(plane0 + j) * a.CoP) * a.CiP;
+#pragma unroll
+        for (int sm = 0; sm < NS; ++sm)
 #pragma unroll
             for (int qd = 0; qd < 4; ++qd) {
-                const int ci = ci0 + 8 * qd + 4 * kh;
                 f32x4 vv;
 #pragma unroll
                 for (int k = 0; k < 4; ++k) vv[k] = acc[j][sm][4 * qd + k];
-                f32x4* dst = reinterpret_cast<f32x4*>(sl + (long long)co * a.CiP + ci);
+                f32x4* dst = reinterpret_cast<f32x4*>(sl + (long long)(co + sm * 32) * a.CiP + ci + 8 * qd);
                 if (a.accum) vv += *dst;
                 *dst = vv;
             }
-        }
     }
-    if (a.bslabs != nullptr && blockIdx.y == 0 && wave == 1) {
-        // wave 1 holds the tile sums of the output channels: the two tile rows (kh) by one shuffle -- fixed order
+}
+// the tile sums of row 1's output channels -> the split's bias slab: the two tile rows (kh) by one shuffle -- fixed order
+template <int NS>
+__device__ __forceinline__ void w24_store_bias(const W24Args& a, int split, const float (&bs)[NS], int co, bool kh0) {
 #pragma unroll
-        for (int sm = 0; sm < NS; ++sm) {
-            const float tot = bs[sm] + __shfl_xor(bs[sm], 32, 64);
-            if (kh == 0) {
-                float* dst = a.bslabs + (long long)split * a.CoP + co0 + sm * 32 + li;
-                *dst = a.accum ? *dst + tot : tot;
-            }
+    for (int sm = 0; sm < NS; ++sm) {
+        const float tot = bs[sm] + __shfl_xor(bs[sm], 32, 64);
+        if (kh0) {
+            float* dst = a.bslabs + (long long)split * a.CoP + co + sm * 32;
+            *dst = a.accum ? *dst + tot : tot;
         }
     }
+}
+
+// ---- algo 5, four waves -----------------------------------------------------------------------------------------------
+
+template <int NS>
+__global__ __launch_bounds__(256, NS == 2 ? 2 : 3) void wgrad_wino24_kernel(const W24Args a) {
+    constexpr int OT = 32 * NS, BUF_BYTES = buf_bytes(NS);
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int li = lane & 31, kh = lane >> 5;
+    const int co0 = blockIdx.z * OT, ci0 = blockIdx.y * IT;
+    const int split = blockIdx.x;
+    W24Dma dma;
+    dma.init(a, lane, split, ci0, co0, OT);
+    // Share: wave w moves halo row w, waves 0 / 1 also rows 4 / 5; gradient pieces NS = 2: wave 0 q = 0, wave 1 q = 1, wave 2
+    // q = 2..4, wave 3 q = 5..7 (8 / 8 / 9 / 9 DMA instructions); NS = 1: waves 2 / 3 two rows each (6 / 6 / 7 / 7)
+    auto request = [&](int buf) {
+        const W24Share sh = {wave, 4, XH, NS == 2 ? (wave < 2 ? wave : 3 * wave - 4) : 2 * (wave - 2),
+                             NS == 2 ? (wave < 2 ? 1 : 3) : (wave < 2 ? 0 : 2)};
+        dma.request(a, sh, smem + buf * BUF_BYTES, smem + buf * BUF_BYTES + X_BYTES, lane);
+    };
+
+    f32x16 acc[6][NS];                                     // [j][o half]
+    w24_zero(acc);
+    float bs[NS] = {};
+    // buffer 1 is 118 x 256 bytes behind buffer 0 (the largest unit offset is 218 of 255)
+    static_assert(BUF_BYTES % 256 == 0 && (BUF_BYTES + X_BYTES + (NS - 1) * GS_BYTES + 4 * GW * 32 * 4) / 256 < 256, "ds_read2st64 offset range");
+    const W24Bases b(smem, smem + X_BYTES, 2 * kh, li);
+    w24_for_row(wave, [&](auto TI) {
+        w24_two_stage(dma.w.p1 - dma.w.p0, request, [&](auto BUF) {
+            constexpr int BO = decltype(BUF)::value * (BUF_BYTES / 4);          // floats
+            w24_tile<decltype(TI)::value, NS, BO, BO>(b, acc, bs);
+        });
+    });
+    // slab: [split][xi][co][ci]; wave 1 holds the tile sums of the output channels
+    w24_store_slabs(a, split * NXI + wave * 6, acc, co0 + li, ci0 + 4 * kh);
+    if (a.bslabs != nullptr && blockIdx.y == 0 && wave == 1) w24_store_bias(a, split, bs, co0 + li, kh == 0);
 }
 
 // PAIR form (NS = 2, an even number of input-channel tiles): ONE workgroup of eight waves computes the two 64(o) x 32(i) tiles
@@ -431,12 +464,22 @@ __global__ __launch_bounds__(256, NS == 2 ? 2 : 3) void wgrad_wino24_kernel(cons
 // lies inside the 8-bit x 256-byte offset range of ds_read2st64 from ONE set of bases: the K loop is written for a TRIPLE of
 // tiles and still carries no address arithmetic.  Tile t + 2 is requested at the top of tile t (two K tiles of lead), ONE
 // barrier per K tile: after it every wave has left tile t - 1, whose stage the request overwrites.  Every wave issues a
-// FIXED number of DMA instructions per request (rows 0 / 1: halo rows 2 row, 2 row + 1 of their half = 6; rows 2 / 3: halo row
-// row + 2 of their half and the gradient pieces (half w >> 2, rows 2 (row - 2), + 1) = 7; dead rows are requested out of
-// range), so "my pieces of tile t have landed" is vmcnt(requests of tile t + 1) and the lead survives the wait.
+// FIXED number of DMA instructions per request (dead rows are requested out of range), so "my pieces of tile t have landed"
+// is vmcnt(requests of tile t + 1) and the lead survives the wait.
 constexpr int PAIR_STAGES = 3;
 constexpr int PAIR_G0 = 2 * PAIR_STAGES * X_BYTES;                             // 82,944: the gradient ring
 constexpr int PAIR_LDS_BYTES = PAIR_G0 + PAIR_STAGES * 2 * GS_BYTES;           // 132,096: one workgroup per CU
+
+// Share of the wave of row `row`, half hf: rows 0 / 1 move halo rows 2 row, 2 row + 1 of their half; rows 2 / 3 halo row
+// row + 2 and the gradient pieces (half hf, rows 2 (row - 2), + 1).  step()'s vmcnt(6) / vmcnt(7) ARE these counts.
+constexpr W24Share pair_share(int row, int hf) {
+    return {row < 2 ? 2 * row : row + 2, 1, row < 2 ? 2 * row + 2 : row + 3, 4 * hf + 2 * (row - 2), row < 2 ? 0 : 2};
+}
+constexpr int pair_dma_count(int row) {
+    return 3 * (pair_share(row, 0).xrEnd - pair_share(row, 0).xr0) + 2 * pair_share(row, 0).nq;
+}
+static_assert(pair_dma_count(0) == 6 && pair_dma_count(1) == 6 && pair_dma_count(2) == 7 && pair_dma_count(3) == 7,
+              "wgrad_wino24_pair_kernel's step() waits for vmcnt(6) in rows 0 / 1 and vmcnt(7) in rows 2 / 3");
 
 // the lane index, opaque to the compiler (not merged with an earlier copy)
 __device__ __forceinline__ int w24_lane_again() {
@@ -454,260 +497,62 @@ __global__ __launch_bounds__(512, 1) void wgrad_wino24_pair_kernel(const W24Args
     const int li = lane & 31, kh = lane >> 5;
     const int co0 = blockIdx.z * OT, ci0 = (2 * blockIdx.y + hf) * IT;
     const int split = blockIdx.x;
-    const int Hin = a.H, Win = a.W;      // (for the address arithmetic; loaded here, their place in the prologue's schedule)
-
-    // one X descriptor per half (wave-uniform): the halves may lie in different sources, or beyond them
-    const bool xFromA = ci0 < a.Ca || ci0 >= a.Ctot;
-    const int xld = xFromA ? a.ldA : a.ldB;
-    const long long gpixAll = (long long)a.N * a.Ho * a.Wo, xpixAll = (long long)a.N * Hin * Win;
-    const int limG = (int)min(gpixAll * a.ldG * 4, 0x7fffffffLL), limX = (int)min(xpixAll * xld * 4, 0x7fffffffLL);
-    const int ntAll = a.ntiles * a.groups;
-    const int chunk = (ntAll + a.nsplit - 1) / a.nsplit;
-    const int p0 = min(split * chunk, ntAll), p1 = min(p0 + chunk, ntAll);
-
-    int qg, qn, qy, qx;
-    {
-        int t = p0 < ntAll ? p0 : 0;
-        qg = t / a.ntiles; t -= qg * a.ntiles;
-        qx = t % a.tilesX; t /= a.tilesX;
-        qy = t % a.tilesY; qn = t / a.tilesY;
-    }
-    // ---- DMA roles: pieces, lane constants and the FAST / masked paths as in the four-wave kernel
-    const int xq = ci0 + (lane & 7) * 4, xt = ci0 + (lane & 31), gq = co0 + (lane & 7) * 4;
-    const int xlc = ((lane >> 3) * xld + (xFromA ? xq : xq - a.Ca)) * 4;
-    const int xlt = ((lane >> 5) * xld + (xFromA ? xt : xt - a.Ca)) * 4;
-    const int glc = ((lane >> 3) * a.ldG + gq) * 4;
-    const bool fullch = ci0 + IT <= a.Ctot && co0 + OT <= a.Co;                     // wave-uniform
-    constexpr int OOB = 0x7ff00000;
-    const int xRowB = Win * xld * 4, gRowB = a.Wo * a.ldG * 4;
-    auto x_origin = [&](int n, int ty, int tx) {
-        return ((n * Hin + (ty * GH - a.pad)) * Win + (tx * GW - a.pad)) * xld * 4;
-    };
-    const float* gPtr = a.g[qg];
-    const float* xPtr = xFromA ? a.inA[qg] : a.inB[qg];
-    int xTile = x_origin(qn, qy, qx);
-    int gTile = ((qn * a.Ho + qy * GH) * a.Wo + qx * GW) * a.ldG * 4;
-    // this wave's share of a request: halo rows xr0 .. xr0 + nxr - 1 of its half; rows 2 / 3 also two gradient rows of half hf
-    const int xr0 = row < 2 ? 2 * row : row + 2, nxr = row < 2 ? 2 : 1;
-    const int gr0 = 2 * (row - 2);
+    // (one input descriptor per half: the halves may lie in different sources, or beyond them)
+    W24Dma dma;
+    dma.init(a, lane, split, ci0, co0, OT);
+    // (the share is worked out at each request: inside a row's K loop the row is a constant)
     auto request = [&](int st) {
-        const int oy0 = qy * GH, ox0 = qx * GW;
-        const int iy0 = oy0 - a.pad, ix0 = ox0 - a.pad;
-        const __amdgpu_buffer_rsrc_t rsG = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(gPtr), 0, limG, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xPtr), 0, limX, 0x00020000);
-        char* xdst = smem + (hf * PAIR_STAGES + st) * X_BYTES;
-        char* gdst = smem + PAIR_G0 + st * (2 * GS_BYTES) + hf * GS_BYTES;
-        const bool fast = fullch && ix0 >= 0 && ix0 + XW <= a.W && ox0 + GW <= a.Wo && xld * 8 * 4 < 0x100000 && a.ldG * 8 * 4 < 0x100000;
-        if (fast) {
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                if (k < nxr && !W24_NO_DMA) {
-                    const int r = xr0 + k;
-                    const int base = (unsigned)(iy0 + r) < (unsigned)a.H ? xTile + r * xRowB : OOB;
-                    char* dst = xdst + r * (XW * IT * 4);
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_ptr24)dst, 16, base + xlc, 0, 0, 0);
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_ptr24)(dst + 1024), 16, base + 8 * xld * 4 + xlc, 0, 0, 0);
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_ptr24)(dst + 2048), 4, base + 16 * xld * 4 + xlt, 0, 0, 0);
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                if (row >= 2 && !W24_NO_DMA) {
-                    const int r = gr0 + k;
-                    const int base = oy0 + r < a.Ho ? gTile + r * gRowB + hf * 128 : OOB;
-                    char* dst = gdst + r * (GW * 32 * 4);
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsG, (lds_ptr24)dst, 16, base + glc, 0, 0, 0);
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsG, (lds_ptr24)(dst + 1024), 16, base + 8 * a.ldG * 4 + glc, 0, 0, 0);
-                }
-            }
-        } else {
-            const int l8 = lane >> 3, l32 = lane >> 5;
-            const int xbadq = xq < a.Ctot ? 0 : -1, xbadt = xt < a.Ctot ? 0 : -1;
-            const int gbad = gq + hf * 32 < a.Co ? 0 : -1;
-            const int cx0 = (unsigned)(ix0 + l8) < (unsigned)a.W ? 0 : -1;
-            const int cx1 = (unsigned)(ix0 + 8 + l8) < (unsigned)a.W ? 0 : -1;
-            const int cxt = (unsigned)(ix0 + 16 + l32) < (unsigned)a.W ? 0 : -1;
-            const int cg0 = ox0 + l8 < a.Wo ? 0 : -1, cg1 = ox0 + 8 + l8 < a.Wo ? 0 : -1;
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                if (k < nxr && !W24_NO_DMA) {
-                    const int r = xr0 + k;
-                    const int rbad = (unsigned)(iy0 + r) < (unsigned)a.H ? 0 : -1;
-                    const int base = xTile + r * xRowB;
-                    char* dst = xdst + r * (XW * IT * 4);
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_ptr24)dst, 16, (base + xlc) | xbadq | rbad | cx0, 0, 0, 0);
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_ptr24)(dst + 1024), 16,
-                                                             (base + 8 * xld * 4 + xlc) | xbadq | rbad | cx1, 0, 0, 0);
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_ptr24)(dst + 2048), 4,
-                                                             (base + 16 * xld * 4 + xlt) | xbadt | rbad | cxt, 0, 0, 0);
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                if (row >= 2 && !W24_NO_DMA) {
-                    const int r = gr0 + k;
-                    const int rbad = oy0 + r < a.Ho ? 0 : -1;
-                    const int base = gTile + r * gRowB + hf * 128;
-                    char* dst = gdst + r * (GW * 32 * 4);
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsG, (lds_ptr24)dst, 16, (base + glc) | gbad | rbad | cg0, 0, 0, 0);
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsG, (lds_ptr24)(dst + 1024), 16,
-                                                             (base + 8 * a.ldG * 4 + glc) | gbad | rbad | cg1, 0, 0, 0);
-                }
-            }
-        }
-        // advance
-        if (REFID_W24_ABLATE == 7) return;
-        qx += 1;
-        if (qx != a.tilesX) {
-            xTile += GW * xld * 4;
-            gTile += GW * a.ldG * 4;
-        } else {
-            qx = 0;
-            qy += 1;
-            if (qy == a.tilesY) {
-                qy = 0;
-                qn += 1;
-                if (qn == a.N) {
-                    qn = 0;
-                    qg = min(qg + 1, a.groups - 1);
-                    gPtr = a.g[qg];
-                    xPtr = xFromA ? a.inA[qg] : a.inB[qg];
-                }
-            }
-            xTile = x_origin(qn, qy, 0);
-            gTile = (qn * a.Ho + qy * GH) * a.Wo * a.ldG * 4;
-        }
+        dma.request(a, pair_share(row, hf), smem + (hf * PAIR_STAGES + st) * X_BYTES, smem + PAIR_G0 + st * (2 * GS_BYTES), lane);
     };
 
     f32x16 acc[6][NS];                                     // [j][o half]
-#pragma unroll
-    for (int j = 0; j < 6; ++j)
-#pragma unroll
-        for (int sm = 0; sm < NS; ++sm)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[j][sm][r] = 0.f;
-
-    // The bases point into stage 0 of the wave's X half and of the gradient ring and never change: stage s is s x 54 (X) /
-    // s x 64 (dY) units of 256 bytes further, an immediate of the same ds_read2st64.
+    w24_zero(acc);
+    // stage s is s x 54 (X) / s x 64 (dY) units of 256 bytes behind stage 0
     static_assert(X_BYTES % 256 == 0 && (PAIR_STAGES * X_BYTES) / 256 < 256 && (PAIR_STAGES * 2 * GS_BYTES) / 256 < 256,
                   "ds_read2st64 offset range");
-    lds_cf24* xe = (lds_cf24*)(smem + hf * PAIR_STAGES * X_BYTES) + (2 * kh) * (XW * IT) + li;
-    lds_cf24* ge = (lds_cf24*)(smem + PAIR_G0) + (2 * kh) * (GW * 32) + li;
-    lds_cf24* xb[4] = {xe, xe + IT, xe + 2 * IT, xe + 3 * IT};
-    lds_cf24* gb[4] = {ge, ge + 32, ge + 2 * 32, ge + 3 * 32};
-    asm volatile("" : "+v"(xb[0]), "+v"(xb[1]), "+v"(xb[2]), "+v"(xb[3]), "+v"(xe));
-    asm volatile("" : "+v"(gb[0]), "+v"(gb[1]), "+v"(gb[2]), "+v"(gb[3]));
+    const W24Bases b(smem + hf * PAIR_STAGES * X_BYTES, smem + PAIR_G0, 2 * kh, li);
 
-    auto kloop = [&](auto TI) {
+    w24_for_row(row, [&](auto TI) {
         constexpr int I = decltype(TI)::value;
-        using R = W24Row<I>;
-        float bs[NS];                                      // (row 1 only: the tile sums live and die in its K loop)
-#pragma unroll
-        for (int sm = 0; sm < NS; ++sm) bs[sm] = 0.f;
-        auto tile = [&](auto ST) {
-            constexpr int XO = decltype(ST)::value * (X_BYTES / 4), GO = decltype(ST)::value * (2 * GS_BYTES / 4);      // floats
-            lds_cf24* xbb[4] = {xb[0] + XO, xb[1] + XO, xb[2] + XO, xb[3] + XO};
-            lds_cf24* gbb[4] = {gb[0] + GO, gb[1] + GO, gb[2] + GO, gb[3] + GO};
-            f32x2 t[6], p4, p5;
-#pragma unroll
-            for (int s = 0; s < TC; s += 2) {
-                R::x_rows(xbb, s, t);
-                if (s == 0) {
-                    const f32x2 a01 = R::x_rows01(xe + XO);
-                    t[0] = w24_pair<0, 0>(a01, t[4]);
-                    t[1] = w24_pair<1, 0>(a01, t[5]);
-                } else {
-                    t[0] = w24_pair<1, 0>(p4, t[4]);
-                    t[1] = w24_pair<1, 0>(p5, t[5]);
-                }
-                p4 = t[4]; p5 = t[5];
-                f32x2 v[6];
-                R::v_cols(t, v);
-#pragma unroll
-                for (int sm = 0; sm < NS; ++sm) {
-                    f32x2 x[4], z[6];
-                    R::g_rows(gbb, s, sm, x);
-                    R::z_cols(x, z);
-                    if constexpr (I == 1) bs[sm] += z[1][0] + z[1][1];
-#pragma unroll
-                    for (int h = 0; h < 2; ++h)
-#pragma unroll
-                        for (int j = 0; j < 6; ++j) {
-                            if (W24_NO_MFMA) { asm volatile("" :: "v"(v[j][h]), "v"(z[j][h])); continue; }
-                            acc[j][sm] = __builtin_amdgcn_mfma_f32_32x32x2f32(v[j][h], z[j][h], acc[j][sm], 0, 0, 0);
-                        }
-                }
-            }
-        };
+        float bs[NS] = {};                                 // (row 1 only: the tile sums live and die in its K loop)
         // tile j of the range: my pieces of it have landed once at most the requests of tile j + 1 (if any) are in flight;
         // behind the barrier everybody's have, and everybody has left tile j - 1, whose stage tile j + 2 goes to
-        const int n = p1 - p0;
+        const int n = dma.w.p1 - dma.w.p0;
         auto step = [&](auto ST, int j) {
             constexpr int S = decltype(ST)::value;
-            if (j + 1 < n) __builtin_amdgcn_s_waitcnt(I < 2 ? 0x0F76 : 0x0F77);        // vmcnt(6) / vmcnt(7)
+            if (j + 1 < n) __builtin_amdgcn_s_waitcnt(I < 2 ? 0x0F76 : 0x0F77);        // vmcnt(6) / vmcnt(7): pair_share
             else __builtin_amdgcn_s_waitcnt(0x0F70);
             if (!W24_NO_BAR) __builtin_amdgcn_s_barrier();
             __builtin_amdgcn_sched_barrier(0);
             if (j + 2 < n) request((S + 2) % PAIR_STAGES);
-            tile(ST);
+            w24_tile<I, NS, S * (X_BYTES / 4), S * (2 * GS_BYTES / 4)>(b, acc, bs);
         };
         if (n > 0) request(0);
         if (n > 1) request(1);
         // (triples in the loop, the last one or two tiles after it: no exit from the middle of the loop body)
         int j = 0;
         for (; j + 3 <= n; j += 3) {
-            step(std::integral_constant<int, 0>{}, j);
-            step(std::integral_constant<int, 1>{}, j + 1);
-            step(std::integral_constant<int, 2>{}, j + 2);
+            step(w24_ic<0>{}, j);
+            step(w24_ic<1>{}, j + 1);
+            step(w24_ic<2>{}, j + 2);
         }
         if (j < n) {
-            step(std::integral_constant<int, 0>{}, j);
-            if (j + 1 < n) step(std::integral_constant<int, 1>{}, j + 1);
+            step(w24_ic<0>{}, j);
+            if (j + 1 < n) step(w24_ic<1>{}, j + 1);
         }
         if constexpr (I == 1) {
-            // row 1 of the half that holds input tile 0 has the tile sums of the output channels: the two tile rows (kh) by
-            // one shuffle -- fixed order
+            // row 1 of the half that holds input tile 0 has the tile sums of the output channels
             if (a.bslabs != nullptr && blockIdx.y == 0 && hf == 0) {
                 const int le = w24_lane_again();
-#pragma unroll
-                for (int sm = 0; sm < NS; ++sm) {
-                    const float tot = bs[sm] + __shfl_xor(bs[sm], 32, 64);
-                    if ((le >> 5) == 0) {
-                        float* dst = a.bslabs + (long long)split * a.CoP + co0 + sm * 32 + (le & 31);
-                        *dst = a.accum ? *dst + tot : tot;
-                    }
-                }
+                w24_store_bias(a, split, bs, co0 + (le & 31), (le >> 5) == 0);
             }
         }
-    };
-    switch (row) {
-        case 0: kloop(std::integral_constant<int, 0>{}); break;
-        case 1: kloop(std::integral_constant<int, 1>{}); break;
-        case 2: kloop(std::integral_constant<int, 2>{}); break;
-        default: kloop(std::integral_constant<int, 3>{}); break;
-    }
+    });
 
-    // ---- slab: as the four-wave kernel's, for input tile 2 blockIdx.y + hf.  (The lane's coordinates are derived again: kept
+    // slab: as the four-wave kernel's, for input tile 2 blockIdx.y + hf.  (The lane's coordinates are derived again: kept
     // from the top of the kernel they would be the two registers too many next to 192 accumulators -- a spill.)
-    const int le = w24_lane_again(), lie = le & 31, khe = le >> 5;
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        float* sl = a.slabs + ((long long)(split * NXI + row * 6 + j) * a.CoP) * a.CiP;
-#pragma unroll
-        for (int sm = 0; sm < NS; ++sm) {
-            const int co = co0 + sm * 32 + lie;
-#pragma unroll
-            for (int qd = 0; qd < 4; ++qd) {
-                const int ci = ci0 + 8 * qd + 4 * khe;
-                f32x4 vv;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) vv[k] = acc[j][sm][4 * qd + k];
-                f32x4* dst = reinterpret_cast<f32x4*>(sl + (long long)co * a.CiP + ci);
-                if (a.accum) vv += *dst;
-                *dst = vv;
-            }
-        }
-    }
+    const int le = w24_lane_again();
+    w24_store_slabs(a, split * NXI + row * 6, acc, co0 + (le & 31), ci0 + 4 * (le >> 5));
 }
 
 // The weight gradient of conv_down (4x4, stride 2, pad 1; recurrent_sub_modules.py:12-14; refid_wgrad_desc.algo = 7), F(2,3) x

@@ -1116,7 +1116,8 @@ class Engine:
             gy_keep.append(g_y)                           # y = ev + img + ...: image gets g_y (deferred sum)
         else:
             ops.add(img_grad, g_y, out=img_grad)
-        # NOT in place: conv3's weight-gradient kernel may still be reading g_y on the side stream
+        # NOT in place: g_y is read again later -- conv3's weight gradient waits in w_pend for the sweep's one grouped launch,
+        # and gy_keep defers the image's sum
         g_ev = ops.layernorm2d_bwd(g_lne, e["ev"], A.p("norm1_e.weight"), torch.empty_like(g_y),
                                    A.g("norm1_e.weight"), A.g("norm1_e.bias"), res=g_y)
         return g_ev                                       # = g_y + LN1e-backward: gradient w.r.t. ev

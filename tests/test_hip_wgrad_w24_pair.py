@@ -3,9 +3,10 @@ workgroup, the gradient tile staged once, a three-stage LDS-DMA ring) against th
 
 A wave of the pair form runs the four-wave form's K loop on the same tiles in the same order, so the two forms must agree
 BIT FOR BIT (torch.equal, no tolerance): every case runs the same call with REFID_W24_PAIR=0 and then =1.  Which form a call
-took is observed through REFID_W24_PAIR=2, which turns the fallback to the four-wave form into an error.  One case on exact
-data (small integers times powers of two: every sum is exact in fp32 whatever its order) is also held to a float64 per-tap
-GEMM at zero tolerance, so a lost or doubled K tile fails even if both forms shared the bug."""
+took is observed through REFID_W24_PAIR=2, which turns the fallback to the four-wave form into an error.  Three cases on exact
+data (small integers times powers of two: every sum is exact in fp32 whatever its order) -- 64 -> 64 (pair form), 64 -> 32 and
+96 -> 64 (the four-wave kernel under both modes) -- are also held to a float64 per-tap GEMM at zero tolerance, so a lost or
+doubled K tile fails even if both forms shared the bug."""
 import pytest
 import torch
 
@@ -163,14 +164,26 @@ def test_short_k_ranges(monkeypatch, wgs):
     assert float((res[1][0] - ref).abs().max()) <= 1e-5 * float(ref.abs().max())       # another split plan: fp32 reordering only
 
 
-def test_exact_data_against_float64_taps(monkeypatch):
+# (Ca, Co) -> the split plan of 2 x 12 x 40 (18 K tiles) under REFID_W24_WGS=8, and the slab planes' padded channel counts:
+#   64 -> 64  two input tiles, pair form:          8 / 2 = 4 splits of 5, 5, 5, 3 tiles
+#   64 -> 32  32-channel output tile (NS = 1):     8 * 3 / 2 / 2 = 6 splits of 3
+#   96 -> 64  three input tiles, four-wave form:   ceil(8 / 3) = 3 splits of 6
+EXACT_CASES = {(64, 64): dict(nsplit=4, CoP=64, CiP=64), (64, 32): dict(nsplit=6, CoP=32, CiP=64),
+               (96, 64): dict(nsplit=3, CoP=64, CiP=96)}
+
+
+@pytest.mark.parametrize("chan", list(EXACT_CASES), ids=["64to64", "64to32", "96to64"])
+def test_exact_data_against_float64_taps(monkeypatch, chan):
     """Small integers times powers of two: every product and every partial sum of the K loop is an integer below 2^24 times a
     power of two, so the slabs are exact in fp32 and 48 dW is an INTEGER combination of their transform planes
     (2 Ay^T and 24 Ax^T have integer entries) -- compared in float64 with 48 x the per-tap GEMM at zero tolerance.  The
     final gradients of the two forms are compared bit for bit as everywhere else; the bias gradient (a plain sum) is exact
-    too.  REFID_W24_WGS=8: four splits of 5, 5, 5, 3 tiles."""
+    too.  K is pixels, not channels, so the data stay exact for every channel count: 64 -> 32 (NS = 1) and 96 -> 64 (an odd
+    number of input tiles) take the four-wave kernel under both REFID_W24_PAIR modes and are held to float64 here."""
     ops = _ops()
-    N, H, W, Ca, Co = 2, 12, 40, 64, 64
+    N, H, W = 2, 12, 40
+    Ca, Co = chan
+    plan = EXACT_CASES[chan]
     monkeypatch.setenv("REFID_W24_WGS", "8")
     gen = torch.Generator().manual_seed(5)
     x = torch.randint(-4, 5, (N, H, W, Ca), generator=gen).double() * 2.0 ** -3
@@ -180,14 +193,15 @@ def test_exact_data_against_float64_taps(monkeypatch):
                        for ky in range(3)], -2)                                     # (Co, Ca, 3, 3), float64, exact
     steps = [(g.float().cuda(), x.float().cuda(), None)]
     geo = geo_of(Ca, 0)
-    nsplit, planes = 4, 24 * Co * Ca
+    nsplit, CoP, CiP = plan["nsplit"], plan["CoP"], plan["CiP"]
+    planes = 24 * CoP * CiP
 
     def run():
         dw = torch.zeros(Co, Ca, 3, 3, device="cuda"); db = torch.zeros(Co, device="cuda")
         sl = ops.conv2d_wgrad(*steps[0][:2], dw, db=db, phase=1, **geo)
         ops.conv2d_wgrad(*steps[0][:2], dw, db=db, phase=3, slabs=sl, **geo)
-        assert sl.numel() > nsplit * (planes + Co) and (sl.numel() - nsplit * (planes + Co)) % planes == 0, "split plan"
-        u = sl[:nsplit * planes].double().cpu().view(nsplit, 4, 6, Co, Ca).sum(0)      # [row][column point][o][i]
+        assert sl.numel() > nsplit * (planes + CoP) and (sl.numel() - nsplit * (planes + CoP)) % planes == 0, "split plan"
+        u = sl[:nsplit * planes].double().cpu().view(nsplit, 4, 6, CoP, CiP).sum(0)[:, :, :Co, :Ca]   # [row][column point][o][i]
         t = [2 * u[0] + u[1] + u[2], u[1] - u[2], u[1] + u[2] + 2 * u[3]]          # 2 Ay^T u: [p][column point][o][i]
         dw48 = torch.stack([torch.stack([6 * tp[0] - 4 * (tp[1] + tp[2]) + (tp[3] + tp[4]),
                                          4 * (tp[2] - tp[1]) + 2 * (tp[3] - tp[4]),

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """What does each piece of the 2x4-tile Winograd weight-gradient kernel cost?  Builds refid_amd/csrc/wgrad_wino24.hip with
 -DREFID_W24_ABLATE=n (one piece removed, results wrong) next to the product build and times config-2 shapes with each
-(8 grouped time steps per launch as in the train step).  Both workgroup forms carry the switches: the shapes below take the pair
-form (eight waves, three-stage ring) unless REFID_W24_PAIR=0 asks for the four-wave form, so a run of each prices both.
+(8 grouped time steps per launch as in the train step).  Both 3x3 workgroup forms carry the switches (they sit in their shared
+pieces; conv_down's kernel has none): the shapes below take the pair form (eight waves, three-stage ring) unless REFID_W24_PAIR=0
+asks for the four-wave form, so a run of each prices both.
 
   python tools/probes/w24_ablate.py --build      (CPU container: cross-compile the variants)
   python tools/probes/w24_ablate.py              (GPU box)
