@@ -698,6 +698,47 @@ typedef struct refid_seq_desc {
 /* Runs the chosen stages (REFID_ASSEMBLE_*) in the order zero, scatter, finish, frames on `stream`: one launch each. */
 int refid_seq_assemble(const refid_seq_desc* d, int stages, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Test-time assembly for the single-image deblurring network from ONE resident sequence: every item (a blurry frame + a
+ * row window of the stream, its exposure) becomes one sample of `lq` / `voxel` in the layout of refid_assemble_single,
+ * without ground truth, crop or flips, at any frame size.  Items are refid_seq_pair rows: `left` is the blurry frame,
+ * `right` is not read, [row0, row1) is the event window, first_stamp / last_stamp as above.
+ * The voxel of an item is what refid_assemble_single gives for the same frame and events at a whole-frame crop without
+ * flips, bit for bit: the same scatter arithmetic, and voxel_norm's statistics taken over the UNPADDED (bins, height,
+ * width) scratch of the item, so that an element's place in the fixed summation order depends on its index in the
+ * unpadded sample only; the padding (zero in voxel channels, the replicated last row / column in image channels) is
+ * written by the same launches and never enters the statistics.  The departures of refid_assemble_single carry over:
+ * events outside the frame or with a negative normalised time are dropped, and an item whose non-zero elements have no
+ * spread (no event, one element, all equal) comes out all zeros where the reference's voxel_norm returns NaN.
+ * Windows may overlap, be empty, or repeat.  Every field and the host table are validated on each call: -1 with
+ * refid_last_error() naming the offending field, nothing launched.  The library allocates nothing and does not
+ * synchronise.  No floating-point atomics.
+ * ---------------------------------------------------------------------------------- */
+typedef struct refid_seq_single_desc {
+    const float* events;                        /* device, (n_events,4) float32 rows [t,x,y,p], 16-byte aligned    */
+    long long n_events;                         /* may be 0                                                       */
+    const unsigned char* frames;                /* device, n_frames u8 HWC blurry frames                          */
+    int n_frames;
+    long long frame_stride;                     /* bytes from one frame to the next                               */
+    int row_pitch;                              /* bytes from one row to the next                                 */
+    int height, width;
+    int bgr;                                    /* != 0: BGR as decoded by cv2 (swapped to RGB); 0: RGB           */
+    const refid_seq_pair* items_host;           /* the item table in host memory (validated on every call)        */
+    const refid_seq_pair* items_dev;            /* the same table in device memory (read by the kernels)          */
+    int n_items;
+    int bins;                                   /* as refid_single_bins: >= 1 and != 3                            */
+    int norm;                                   /* 0: voxel = the plain bins; 1: voxel_norm per item              */
+    int out_h, out_w;                           /* >= height, width: the padded size the network takes            */
+    long long* scratch;                         /* int64 [n_items][bins][height*width]                            */
+    void* parts;                                /* refid_voxel_norm_parts(n_items, bins*height*width) words; norm */
+    float* lq;                                  /* (P, 3, out_h, out_w)                                           */
+    float* voxel;                               /* (P, bins, out_h, out_w): plain bins, not sliding pairs         */
+} refid_seq_single_desc;
+/* Runs the chosen stages (REFID_ASSEMBLE_* and REFID_ASSEMBLE_STATS) in the order zero, scatter, stats, finish, frames
+ * on `stream`: one launch each for all items.  stats is skipped when norm == 0.  Fewer than 2^30 events per item with
+ * norm (S1 stays inside int64). */
+int refid_seq_assemble_single(const refid_seq_single_desc* d, int stages, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

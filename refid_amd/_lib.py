@@ -132,7 +132,22 @@ class SeqDesc(C.Structure):
     ]
 
 
-LAYOUT_BLUR, LAYOUT_SHARP = 0, 1                 # == REFID_LAYOUT_* in include/refid_hip.h
+class SeqSingleDesc(C.Structure):
+    """refid_seq_single_desc: single-image items (blurry frame + exposure window) of a resident sequence."""
+    _fields_ = [
+        ("events", C.c_void_p), ("n_events", C.c_longlong),
+        ("frames", C.c_void_p), ("n_frames", C.c_int),
+        ("frame_stride", C.c_longlong), ("row_pitch", C.c_int), ("height", C.c_int), ("width", C.c_int), ("bgr", C.c_int),
+        ("items_host", C.c_void_p), ("items_dev", C.c_void_p), ("n_items", C.c_int),
+        ("bins", C.c_int), ("norm", C.c_int),
+        ("out_h", C.c_int), ("out_w", C.c_int),
+        ("scratch", C.c_void_p),
+        ("parts", C.c_void_p),
+        ("lq", C.c_void_p), ("voxel", C.c_void_p),
+    ]
+
+
+LAYOUT_BLUR, LAYOUT_SHARP = 0, 1                # == REFID_LAYOUT_* in include/refid_hip.h
 ASSEMBLE_ZERO, ASSEMBLE_SCATTER, ASSEMBLE_FINISH, ASSEMBLE_FRAMES, ASSEMBLE_ALL = 1, 2, 4, 8, 15
 ASSEMBLE_STATS = 16                              # refid_assemble_single only: voxel_norm's statistics, between scatter and finish
 
@@ -260,6 +275,7 @@ def _bind_extra(L):
     L.refid_voxel_norm.argtypes = [vp, vp, i, ll, vp, vp]
     L.refid_single_bins.argtypes = [i]
     L.refid_assemble_single.argtypes = [C.POINTER(SingleDesc), i, vp]
+    L.refid_seq_assemble_single.argtypes = [C.POINTER(SeqSingleDesc), i, vp]
 
 
 def check(rc, what):

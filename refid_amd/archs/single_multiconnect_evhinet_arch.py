@@ -119,6 +119,11 @@ class SingleMultiConnectEVHINet(nn.Module):
     def notify_params_changed(self):
         self._touch()
 
+    @property
+    def size_multiple(self):
+        """Both sides of the input must be multiples of this: depth - 1 stride-2 downsamplings."""
+        return 2 ** (self._cfg["depth"] - 1)
+
     def get_input_chn(self, in_chn):
         return in_chn
 

@@ -1020,3 +1020,8 @@ def voxel_norm(x, out=None):
 def assemble_single(desc, stages=_lib.ASSEMBLE_ALL | _lib.ASSEMBLE_STATS):
     """Runs the single-image assembly of csrc/sample.hip for an _lib.SingleDesc on the current stream."""
     check(lib().refid_assemble_single(C.byref(desc), int(stages), _stream()), "refid_assemble_single")
+
+
+def seq_assemble_single(desc, stages=_lib.ASSEMBLE_ALL | _lib.ASSEMBLE_STATS):
+    """Runs the single-image item assembly of csrc/sequence.hip for an _lib.SeqSingleDesc on the current stream."""
+    check(lib().refid_seq_assemble_single(C.byref(desc), int(stages), _stream()), "refid_seq_assemble_single")

@@ -5,7 +5,8 @@ key-frame indices and a row window of the stream -- becomes one sample of ``lq``
 csrc/sequence.hip, padded up to the multiple the network takes.  ``SequenceInterpolator`` runs the network over the
 pairs in minibatches, assembling minibatch k+1 on a side stream while minibatch k computes (the way ``CUDAPrefetcher``
 does it), crops the result back, quantises it with ``metrics.val_tail`` and hands the uint8 frames to
-``validation.FrameWriter``.
+``validation.FrameWriter``.  ``SequenceDeblurrer`` does the same for the single-image deblurring network: one blurry frame
+and the events of its exposure per item (``frame_windows``, ``SequenceAssembler(layout='single')``).
 
 Window search stays on the host: the host loaded the events, so ``np.searchsorted`` over the same float32 timestamp
 column the kernel reads costs nothing and needs no synchronisation."""
@@ -54,6 +55,16 @@ def exposure_windows(starts, ends):
         raise RefidHipError(f"exposure_windows: {s.size} exposure starts, {e.size} exposure ends")
     k = np.arange(max(len(s) - 1, 0))
     return k, k + 1, s[:-1], e[1:]
+
+
+def frame_windows(starts, ends):
+    """Single blurry frames with exposures [starts[k], ends[k]): item k is frame k with the window [start_k, end_k).
+    Returns (k, k, starts, ends) for ``make_pairs`` (the single layout reads ``left`` only)."""
+    s, e = np.asarray(starts).reshape(-1), np.asarray(ends).reshape(-1)
+    if s.shape != e.shape:
+        raise RefidHipError(f"frame_windows: {s.size} exposure starts, {e.size} exposure ends")
+    k = np.arange(len(s))
+    return k, k, s, e
 
 
 def make_pairs(t, lefts, rights, begins, ends, stamps="events"):
@@ -109,20 +120,30 @@ def _round_up(v, multiple):
 class SequenceAssembler:
     """``{'lq', 'voxel'}`` for frame pairs of one resident sequence (csrc/sequence.hip), in the layouts of
     ``DeviceBatchAssembler``: ``layout='sharp'``: n+1 bins, lq (P, 2, 3, h, w); ``layout='blur'``: 2m+n+1 bins, lq
-    (P, 6+2(m-1), h, w) = frame[left] | bins 1..m-1 | frame[right] | bins m+2+n..; voxel (P, bins-1, 2, h, w).  (h, w) is
-    the frame size rounded up to ``multiple``: image channels replicate the last row / column there, voxel channels are
-    zero.  Everything runs on the current stream; the cached scratch and pair table are ordered by that stream only: use
-    one assembler per stream."""
+    (P, 6+2(m-1), h, w) = frame[left] | bins 1..m-1 | frame[right] | bins m+2+n..; voxel (P, bins-1, 2, h, w).
+    ``layout='single'`` (``m`` and ``n`` are not used): ``num_bins`` bins, one blurry frame per item (``left``; ``right`` is
+    not read): lq (P, 3, h, w), voxel (P, num_bins, h, w) = the plain bins after ``voxel_norm`` unless ``norm_voxel=False``;
+    the statistics are taken over the unpadded frame, and an item without spread comes out all zeros.  (h, w) is the frame
+    size rounded up to ``multiple`` (default 8, single layout 4): image channels replicate the last row / column there,
+    voxel channels are zero.  Everything runs on the current stream; the cached scratch and pair table are ordered by that
+    stream only: use one assembler per stream."""
 
-    def __init__(self, m, n, layout="sharp", multiple=8, device=None):
-        if layout not in ("blur", "sharp"):
-            raise RefidHipError(f"SequenceAssembler: unknown layout {layout!r} ('blur' or 'sharp')")
+    def __init__(self, m=None, n=None, layout="sharp", multiple=None, device=None, num_bins=6, norm_voxel=True):
+        if layout not in ("blur", "sharp", "single"):
+            raise RefidHipError(f"SequenceAssembler: unknown layout {layout!r} ('blur', 'sharp' or 'single')")
         from . import ops
-        self.m, self.n = int(m), int(n)
         self.layout = layout
-        self._layout = _lib.LAYOUT_BLUR if layout == "blur" else _lib.LAYOUT_SHARP
-        self.bins = ops.assemble_bins(self.m, self.n, self._layout)
-        self.multiple = int(multiple)
+        self.norm_voxel = bool(norm_voxel)
+        if layout == "single":
+            self.m = self.n = self._layout = None
+            self.bins = ops.single_bins(num_bins)
+        else:
+            if m is None or n is None:
+                raise RefidHipError(f"SequenceAssembler: layout {layout!r} needs m and n")
+            self.m, self.n = int(m), int(n)
+            self._layout = _lib.LAYOUT_BLUR if layout == "blur" else _lib.LAYOUT_SHARP
+            self.bins = ops.assemble_bins(self.m, self.n, self._layout)
+        self.multiple = int((4 if layout == "single" else 8) if multiple is None else multiple)
         if self.multiple < 1:
             raise RefidHipError(f"SequenceAssembler: multiple {multiple} must be >= 1")
         self.device = torch.device("cuda" if device is None else device)
@@ -159,10 +180,13 @@ class SequenceAssembler:
                  "table_dev": torch.empty(nbytes, dtype=torch.uint8, device=self.device),
                  "table_pin": torch.empty(nbytes, dtype=torch.uint8).pin_memory(),
                  "uploaded": None}
+            if self.layout == "single" and self.norm_voxel:
+                from . import ops
+                c["parts"] = ops.voxel_norm_parts(count, self.bins * self.height * self.width, self.device)
             self._cache[key] = c
         return c
 
-    def assemble(self, pairs, stages=_lib.ASSEMBLE_ALL):
+    def assemble(self, pairs, stages=_lib.ASSEMBLE_ALL | _lib.ASSEMBLE_STATS):
         from . import ops
         if self.frames is None:
             raise RefidHipError("SequenceAssembler.assemble: load() a sequence first")
@@ -183,22 +207,33 @@ class SequenceAssembler:
         c["uploaded"] = torch.cuda.Event()
         c["uploaded"].record()
         h, w = self.out_h, self.out_w
-        if self.layout == "blur":
-            lq = torch.empty((count, 6 + 2 * (self.m - 1), h, w), dtype=torch.float32, device=self.device)
+        single = self.layout == "single"
+        if single:
+            lq = torch.empty((count, 3, h, w), dtype=torch.float32, device=self.device)
+            voxel = torch.empty((count, self.bins, h, w), dtype=torch.float32, device=self.device)
         else:
-            lq = torch.empty((count, 2, 3, h, w), dtype=torch.float32, device=self.device)
-        voxel = torch.empty((count, self.bins - 1, 2, h, w), dtype=torch.float32, device=self.device)
-        desc = _lib.SeqDesc()
+            if self.layout == "blur":
+                lq = torch.empty((count, 6 + 2 * (self.m - 1), h, w), dtype=torch.float32, device=self.device)
+            else:
+                lq = torch.empty((count, 2, 3, h, w), dtype=torch.float32, device=self.device)
+            voxel = torch.empty((count, self.bins - 1, 2, h, w), dtype=torch.float32, device=self.device)
+        desc = _lib.SeqSingleDesc() if single else _lib.SeqDesc()
         n_ev = int(self.events.shape[0])
         desc.events, desc.n_events = (self.events.data_ptr() if n_ev else None), n_ev
         desc.frames, desc.n_frames = self.frames.data_ptr(), int(self.frames.shape[0])
         desc.frame_stride, desc.row_pitch = self.height * self.width * 3, self.width * 3
         desc.height, desc.width, desc.bgr = self.height, self.width, int(self.bgr)
-        desc.pairs_host, desc.pairs_dev, desc.n_pairs = C.addressof(table), c["table_dev"].data_ptr(), count
-        desc.m, desc.n, desc.layout = self.m, self.n, self._layout
         desc.out_h, desc.out_w = h, w
         desc.scratch, desc.lq, desc.voxel = c["scratch"].data_ptr(), lq.data_ptr(), voxel.data_ptr()
-        ops.seq_assemble(desc, stages)
+        if single:
+            desc.items_host, desc.items_dev, desc.n_items = C.addressof(table), c["table_dev"].data_ptr(), count
+            desc.bins, desc.norm = self.bins, int(self.norm_voxel)
+            desc.parts = c["parts"].data_ptr() if self.norm_voxel else None
+            ops.seq_assemble_single(desc, stages)
+        else:
+            desc.pairs_host, desc.pairs_dev, desc.n_pairs = C.addressof(table), c["table_dev"].data_ptr(), count
+            desc.m, desc.n, desc.layout = self.m, self.n, self._layout
+            ops.seq_assemble(desc, stages & _lib.ASSEMBLE_ALL)
         self._last = (desc, table)
         cur = torch.cuda.current_stream(self.device)
         for t in (self.frames, self.events):  # (uploaded on another stream: they stay valid until the kernels ran)
@@ -206,35 +241,22 @@ class SequenceAssembler:
         return {"lq": lq, "voxel": voxel}
 
 
-class SequenceInterpolator:
-    """Runs ``net`` over the frame pairs of a sequence.  ``run`` uploads the sequence once, assembles minibatch k+1 on a
-    side stream while minibatch k runs, and turns every output into uint8 RGB frames of the original (H, W).  The
-    minibatch composition is part of the contract: pairs [0, max_minibatch), [max_minibatch, 2 max_minibatch), ... go
-    through ``net(x=lq, event=voxel)`` together, under ``eval()`` / ``no_grad()``."""
-
-    def __init__(self, net, m, n, layout="sharp", max_minibatch=2):
-        self.net = net
-        self.max_minibatch = int(max_minibatch)
-        if self.max_minibatch < 1:
-            raise RefidHipError(f"SequenceInterpolator: max_minibatch {max_minibatch} must be >= 1")
-        if not hasattr(net, "num_encoders"):
-            raise RefidHipError("SequenceInterpolator: the network has no num_encoders (the padding multiple is taken from it)")
-        self.device = next(net.parameters()).device
-        self.assembler = SequenceAssembler(m, n, layout, multiple=1 << int(net.num_encoders), device=self.device)
-        self.stream = torch.cuda.Stream(device=self.device)
+class _SequenceRunner:
+    """What ``SequenceInterpolator`` and ``SequenceDeblurrer`` share: upload the sequence once, assemble minibatch k+1 on a
+    side stream while minibatch k runs, crop back to (H, W), quantise with ``metrics.val_tail`` and hand the uint8 frames to
+    ``validation.FrameWriter``.  A subclass sets ``net``, ``assembler``, ``max_minibatch``, ``device`` and ``stream`` and
+    gives ``_forward(batch)`` -> (P, ..., 3, h, w) and ``_paths(out_dir, name, u8_item)`` -> one path per frame of an item."""
 
     def run(self, frames, events, pairs, out_dir=None, names=None, keep=False, bgr=False):
-        """``frames`` uint8 (N, H, W, 3), ``events`` float32 (E, 4), ``pairs`` from ``make_pairs``.  With ``out_dir`` frame f
-        of pair k goes to ``{out_dir}/{names[k]}_{f:02d}.png`` (default name: the left key frame's index, six digits, as
-        the validation dumps are named).  ``keep=True`` returns the uint8 frames (P, T, H, W, 3) on the host, else None."""
         from .validation import FrameWriter
+        what = type(self).__name__
         pairs = list(pairs)
         if not pairs:
-            raise RefidHipError("SequenceInterpolator.run: no pairs")
+            raise RefidHipError(f"{what}.run: no pairs")
         if names is None:
             names = [f"{p[0]:06d}" for p in pairs]
         if len(names) != len(pairs):
-            raise RefidHipError(f"SequenceInterpolator.run: {len(names)} names for {len(pairs)} pairs")
+            raise RefidHipError(f"{what}.run: {len(names)} names for {len(pairs)} pairs")
         asm, side = self.assembler, self.stream
         cur = torch.cuda.current_stream(self.device)
         asm.load(frames, events, bgr=bgr)
@@ -261,14 +283,12 @@ class SequenceInterpolator:
                     for v in batch.values():
                         v.record_stream(cur)
                     nxt = preload(k + 1)
-                    out = self.net(x=batch["lq"], event=batch["voxel"])
-                    u8 = metrics.val_tail(out[..., :H, :W], bgr=False).pred_u8       # (P, T, H, W, 3)
-                    t = u8.shape[1]
+                    out = self._forward(batch)
+                    u8 = metrics.val_tail(out[..., :H, :W], bgr=False).pred_u8       # (P, [T,] H, W, 3)
                     if writer is not None:
                         base = k * self.max_minibatch
-                        paths = [os.path.join(out_dir, f"{names[base + i]}_{f:02d}.png")
-                                 for i in range(len(chunk)) for f in range(t)]
-                        writer.dump([(u8.view(len(chunk) * t, H, W, 3), paths)])
+                        paths = [p for i in range(len(chunk)) for p in self._paths(out_dir, names[base + i], u8[i])]
+                        writer.dump([(u8.view(-1, H, W, 3), paths)])
                     if keep:
                         kept.append(u8)
         finally:
@@ -277,3 +297,77 @@ class SequenceInterpolator:
             if writer is not None:
                 writer.close()
         return torch.cat(kept, dim=0).cpu().numpy() if keep else None
+
+
+class SequenceInterpolator(_SequenceRunner):
+    """Runs ``net`` over the frame pairs of a sequence.  ``run`` uploads the sequence once, assembles minibatch k+1 on a
+    side stream while minibatch k runs, and turns every output into uint8 RGB frames of the original (H, W).  The
+    minibatch composition is part of the contract: pairs [0, max_minibatch), [max_minibatch, 2 max_minibatch), ... go
+    through ``net(x=lq, event=voxel)`` together, under ``eval()`` / ``no_grad()``."""
+
+    def __init__(self, net, m, n, layout="sharp", max_minibatch=2):
+        self.net = net
+        self.max_minibatch = int(max_minibatch)
+        if self.max_minibatch < 1:
+            raise RefidHipError(f"SequenceInterpolator: max_minibatch {max_minibatch} must be >= 1")
+        if not hasattr(net, "num_encoders"):
+            raise RefidHipError("SequenceInterpolator: the network has no num_encoders (the padding multiple is taken from it)")
+        self.device = next(net.parameters()).device
+        self.assembler = SequenceAssembler(m, n, layout, multiple=1 << int(net.num_encoders), device=self.device)
+        self.stream = torch.cuda.Stream(device=self.device)
+
+    def run(self, frames, events, pairs, out_dir=None, names=None, keep=False, bgr=False):
+        """``frames`` uint8 (N, H, W, 3), ``events`` float32 (E, 4), ``pairs`` from ``make_pairs``.  With ``out_dir`` frame f
+        of pair k goes to ``{out_dir}/{names[k]}_{f:02d}.png`` (default name: the left key frame's index, six digits, as
+        the validation dumps are named).  ``keep=True`` returns the uint8 frames (P, T, H, W, 3) on the host, else None."""
+        return super().run(frames, events, pairs, out_dir, names, keep, bgr)
+
+    def _forward(self, batch):
+        return self.net(x=batch["lq"], event=batch["voxel"])
+
+    def _paths(self, out_dir, name, u8_item):
+        return [os.path.join(out_dir, f"{name}_{f:02d}.png") for f in range(u8_item.shape[0])]
+
+
+class SequenceDeblurrer(_SequenceRunner):
+    """Runs a single-image deblurring ``net`` (``SingleMultiConnectEVHINet``: ``net(x, event)`` returns a list whose last
+    element is the output) over the blurry frames of a sequence, as ``SequenceInterpolator`` does for pairs: one upload,
+    assembly of minibatch k+1 (``SequenceAssembler(layout='single')``, padded to ``net.size_multiple``) on a side stream
+    while minibatch k runs, ``eval()`` / ``no_grad()``, the minibatch composition [0, mb), [mb, 2mb), ... as part of the
+    contract.  ``crop_size``: every item goes through ``tiling.tiled_forward`` on the padded frame instead (tiles in
+    minibatches of ``max_minibatch``); half-instance-norm statistics are then per tile, so the output differs from the
+    whole-frame one by design."""
+
+    def __init__(self, net, num_bins, max_minibatch=1, crop_size=None, norm_voxel=True):
+        self.net = net
+        self.max_minibatch = int(max_minibatch)
+        if self.max_minibatch < 1:
+            raise RefidHipError(f"SequenceDeblurrer: max_minibatch {max_minibatch} must be >= 1")
+        if not hasattr(net, "size_multiple"):
+            raise RefidHipError("SequenceDeblurrer: the network has no size_multiple (the padding multiple is taken from it)")
+        self.crop_size = None if crop_size is None else int(crop_size)
+        if self.crop_size is not None and (self.crop_size < 1 or self.crop_size % int(net.size_multiple)):
+            raise RefidHipError(f"SequenceDeblurrer: crop_size {crop_size} must be a positive multiple of "
+                                f"net.size_multiple ({net.size_multiple})")
+        self.device = next(net.parameters()).device
+        self.assembler = SequenceAssembler(layout="single", num_bins=num_bins, norm_voxel=norm_voxel,
+                                           multiple=int(net.size_multiple), device=self.device)
+        self.stream = torch.cuda.Stream(device=self.device)
+
+    def run(self, frames, events, items, out_dir=None, names=None, keep=False, bgr=False):
+        """``frames`` uint8 (N, H, W, 3), ``events`` float32 (E, 4), ``items`` from ``make_pairs(t, *frame_windows(...))``.
+        With ``out_dir`` item k goes to ``{out_dir}/{names[k]}.png`` (default name: the frame index, six digits).
+        ``keep=True`` returns the uint8 frames (P, H, W, 3) on the host, else None."""
+        return super().run(frames, events, items, out_dir, names, keep, bgr)
+
+    def _forward(self, batch):
+        if self.crop_size is None:
+            return self.net(x=batch["lq"], event=batch["voxel"])[-1]
+        from . import tiling
+        return torch.cat([tiling.tiled_forward(self.net, batch["lq"][i:i + 1], batch["voxel"][i:i + 1], self.crop_size,
+                                               self.max_minibatch) for i in range(batch["lq"].shape[0])], dim=0)
+
+    def _paths(self, out_dir, name, u8_item):
+        return [os.path.join(out_dir, f"{name}.png")]
+
+

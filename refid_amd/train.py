@@ -690,6 +690,18 @@ class ImageEventRestorationModel(TwoImageEventRecurrentRestorationModel):
             self.output = torch.cat(outs, dim=0)
         self.net_g.train()
 
+    def _val_forward(self):
+        """test(), or with val.grids the tiled pass of Test_image_event_restoration_model.py:186-266, :405-416 through
+        ``tiling.tiled_forward`` (val.crop_size, val.max_minibatch tiles per call).  The tile transposes (val.trans_num) and
+        the extra random tiles (val.random_crop_num) of the reference's grids() are not implemented and are rejected."""
+        val = self.opt.get("val", {})
+        if val.get("grids") is not None:
+            if val.get("trans_num", 1) != 1:
+                raise RefidHipError(f"val.trans_num = {val['trans_num']} is not supported with val.grids (only 1: no transposed tiles)")
+            if (val.get("random_crop_num") or 0) > 0:
+                raise RefidHipError(f"val.random_crop_num = {val['random_crop_num']} is not supported with val.grids (only 0)")
+        return super()._val_forward()
+
     # ---- validation (image_event_restoration_model.py:372-496): the base class's loop, tail and PNG writer (a 4-D output
     # is one frame per sample) with this model's book, attributes and file names --------------------------------------
     # (feed_data stays the base class's: the reference's requires `seq` and `origin_index` (:105-109), but training batches
