@@ -739,6 +739,36 @@ typedef struct refid_seq_single_desc {
  * norm (S1 stays inside int64). */
 int refid_seq_assemble_single(const refid_seq_single_desc* d, int stages, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * NIQE (basicsr/metrics/niqe.py calculate_niqe, convert_to='y'): the per-pixel half on the device (csrc/niqe.hip).  From
+ * n_frames uint8 HWC frames (h, w, 3) -- RGB, or BGR with REFID_NIQE_BGR -- it produces, for both scales, the five moment
+ * sums of the five maps of every block; the host turns them into AGGD features and the score (refid_amd/niqe.py).
+ * The frame is cropped by crop_border on every side and then to hc x wc = floor(./96)*96 from the top-left; fewer than
+ * 96 rows or columns: error.  Arithmetic, every step one correctly rounded operation, no contraction:
+ *   v_c = fl32(u8/255);  y64 = ((b*24.966 + g*128.553) + r*65.481) + 16.0 in float64;  Y = fl32(fl32(y64/255.0) * 255)
+ *   scale 2: Y2 = fl32(m(fl32(Y/255)) * 255), m the float32 2x2 mean, horizontal pair first, each a*0.5 + b*0.5
+ *            (cv2.resize INTER_LINEAR at an exact factor 2; a stand-in that was never compared with a real cv2)
+ *   mu64 / sq64 = sum over the 49 taps of window49 (float64, row-major, from a zero accumulator, acc = acc + w*x) of Y
+ *            and of fl32(Y*Y), coordinates clamped at the edges of the cropped image;  mu = fl32(mu64), sq = fl32(sq64)
+ *   n = (Y - mu) / (sqrt(|sq - mu*mu|) + 1) in float32
+ *   maps of a block (96x96 at scale 1, 48x48 at scale 2): n, and fl32(n * roll(n, s)) for s = (0,1), (1,0), (1,1), (1,-1),
+ *            the roll wrapping inside the block as np.roll does
+ * sums: float64 [n_frames][2 scales][blocks][5 maps][5] with blocks = (hc/96)*(wc/96) in width-major order (block column
+ * bw, block row bh -> bw*(hc/96) + bh, as the reference walks them) and the five entries
+ *   count(x < 0), count(x > 0), sum_{x<0} x^2, sum_{x>0} x^2, sum |x|
+ * the counts as exact float64 integers, the squares exact in float64, every sum a fixed-order tree without atomics: the
+ * bits do not depend on the run, on n_frames or on the frame's place in the call.  Inside an area of constant colour mu
+ * equals Y exactly and the map is exactly zero, as in the reference: zeros count on neither side.
+ * parts: refid_niqe_moments_parts(...) 8-byte words of scratch; 0 with the present tiling (one workgroup per block), and
+ * then parts may be NULL.  y_out (n_frames, hc, wc), mscn1_out (n_frames, hc, wc), mscn2_out (n_frames, hc/2, wc/2):
+ * float32 planes Y and n per scale for tests, each may be NULL.  Two launches on `stream`; nothing is allocated.
+ * ---------------------------------------------------------------------------------- */
+#define REFID_NIQE_BGR 1
+long long refid_niqe_moments_parts(int n_frames, int h, int w);
+int refid_niqe_moments(const unsigned char* frames_u8, int n_frames, int h, int w, int flags, int crop_border,
+                       const double* window49, double* sums, void* parts, float* y_out, float* mscn1_out,
+                       float* mscn2_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -152,6 +152,7 @@ ASSEMBLE_ZERO, ASSEMBLE_SCATTER, ASSEMBLE_FINISH, ASSEMBLE_FRAMES, ASSEMBLE_ALL 
 ASSEMBLE_STATS = 16                              # refid_assemble_single only: voxel_norm's statistics, between scatter and finish
 
 VAL_TAIL_BGR = 1         # == REFID_VAL_TAIL_BGR in include/refid_hip.h
+NIQE_BGR = 1             # == REFID_NIQE_BGR in include/refid_hip.h
 ABI_VERSION = 9          # == REFID_ABI_VERSION in include/refid_hip.h
 _lib = None
 
@@ -276,6 +277,9 @@ def _bind_extra(L):
     L.refid_single_bins.argtypes = [i]
     L.refid_assemble_single.argtypes = [C.POINTER(SingleDesc), i, vp]
     L.refid_seq_assemble_single.argtypes = [C.POINTER(SeqSingleDesc), i, vp]
+    L.refid_niqe_moments_parts.argtypes = [i, i, i]
+    L.refid_niqe_moments_parts.restype = ll
+    L.refid_niqe_moments.argtypes = [vp, i, i, i, i, i, vp, vp, vp, vp, vp, vp, vp]
 
 
 def check(rc, what):

@@ -7,13 +7,16 @@
 ``val.grids`` is set, ``val.crop_size`` (tiled inference); or give ``--checkpoint`` with ``--num-bins``: the network is then
 ``SingleMultiConnectEVHINet`` with its defaults and ``ev_chn = num_bins``.  ``--frames`` is a directory of 8-bit PNGs
 (sorted by name) or a ``.npy`` stack (N, H, W, 3) uint8 RGB; ``--stamps`` a text file with the exposure ``start end`` of
-every frame per line, in the events' clock.  Frame k is written to ``{out}/{k:06d}.png``."""
+every frame per line, in the events' clock.  Frame k is written to ``{out}/{k:06d}.png``.  ``--niqe PARAMS.npz`` (the
+reference's ``niqe_pris_params.npz``) also scores every output frame with NIQE: ``{out}/niqe.txt`` holds one ``file score``
+line per frame and a last ``mean`` line over the finite scores, which is printed too."""
 import argparse
+import os
 import sys
 
 import numpy as np
 
-from .interpolate import load_frames
+from .interpolate import load_frames, write_niqe
 
 
 def settings(args):
@@ -57,12 +60,17 @@ def main(argv=None):
     ap.add_argument("--swap-xy", action="store_true", help="the HighREV files' swapped x / y columns")
     ap.add_argument("--stamps-mode", choices=("events", "bounds"), default="events",
                     help="normalise event times from the first to the last event of a window, or from start to end")
+    ap.add_argument("--niqe", metavar="PARAMS.npz", help="score every output frame with NIQE (niqe_pris_params.npz) -> niqe.txt")
     args = ap.parse_args(argv)
 
     import torch
     from . import sequence
     from .archs import define_network
     net_opt, ckpt, bins, mb, crop = settings(args)
+    niqe_model = None
+    if args.niqe:
+        from .niqe import NiqeModel
+        niqe_model = NiqeModel.load(args.niqe)
     frames = load_frames(args.frames)
     events = sequence.load_event_npz(args.events, swap_xy=args.swap_xy)
     stamps = np.loadtxt(args.stamps, dtype=np.float64, ndmin=2)
@@ -79,8 +87,12 @@ def main(argv=None):
     else:
         print("warning: no checkpoint given: the network runs with its initial weights", file=sys.stderr)
     names = [f"{k:06d}" for k in range(len(items))]
-    sequence.SequenceDeblurrer(net, bins, mb, crop).run(frames, events, items, out_dir=args.out, names=names)
+    runner = sequence.SequenceDeblurrer(net, bins, mb, crop)
+    runner.run(frames, events, items, out_dir=args.out, names=names, niqe=niqe_model)
     print(f"{len(items)} frames -> {args.out}")
+    if niqe_model is not None:
+        mean = write_niqe(args.out, [f"{name}.png" for name, _, _ in runner.niqe_scores], [s for _, _, s in runner.niqe_scores])
+        print(f"NIQE mean {mean:.6f} over {len(runner.niqe_scores)} frames -> {os.path.join(args.out, 'niqe.txt')}")
     return 0
 
 

@@ -7,7 +7,9 @@
 type: the ``*Sharp*`` classes take sharp key frames); or give ``--checkpoint`` with ``--n`` / ``--m`` / ``--layout`` and the
 released network size.  ``--frames`` is a directory of 8-bit PNGs (sorted by name) or a ``.npy`` stack (N, H, W, 3) uint8
 RGB; ``--stamps`` a text file with one key-frame timestamp per line (sharp layout) or an exposure ``start end`` per line
-(blur layout), in the events' clock.  Frame f of pair k is written to ``{out}/{k:06d}_{f:02d}.png``."""
+(blur layout), in the events' clock.  Frame f of pair k is written to ``{out}/{k:06d}_{f:02d}.png``.  ``--niqe PARAMS.npz``
+(the reference's ``niqe_pris_params.npz``) also scores every output frame with NIQE: ``{out}/niqe.txt`` holds one
+``file score`` line per frame and a last ``mean`` line over the finite scores, which is printed too."""
 import argparse
 import glob
 import os
@@ -35,6 +37,18 @@ def load_frames(path):
     if stack.dtype != np.uint8 or stack.ndim != 4 or stack.shape[3] != 3:
         raise SystemExit(f"--frames: {path} must hold uint8 (N, H, W, 3), got {stack.dtype} {stack.shape}")
     return stack
+
+
+def write_niqe(out_dir, files, scores):
+    """``{out_dir}/niqe.txt``: one ``file score`` line per frame, then ``mean`` over the finite scores (nan when there is
+    none).  Returns the mean."""
+    finite = [s for s in scores if np.isfinite(s)]
+    mean = float(np.mean(finite)) if finite else float("nan")
+    with open(os.path.join(out_dir, "niqe.txt"), "w") as f:
+        for name, s in zip(files, scores):
+            f.write(f"{name} {s:.6f}\n")
+        f.write(f"mean {mean:.6f}\n")
+    return mean
 
 
 def settings(args):
@@ -72,12 +86,17 @@ def main(argv=None):
     ap.add_argument("--out", required=True, help="output directory")
     ap.add_argument("--max-minibatch", type=int, default=2)
     ap.add_argument("--swap-xy", action="store_true", help="the HighREV files' swapped x / y columns")
+    ap.add_argument("--niqe", metavar="PARAMS.npz", help="score every output frame with NIQE (niqe_pris_params.npz) -> niqe.txt")
     args = ap.parse_args(argv)
 
     import torch
     from . import sequence
     from .archs import define_network
     net_opt, ckpt, m, n, layout = settings(args)
+    niqe_model = None
+    if args.niqe:
+        from .niqe import NiqeModel
+        niqe_model = NiqeModel.load(args.niqe)
     frames = load_frames(args.frames)
     events = sequence.load_event_npz(args.events, swap_xy=args.swap_xy)
     stamps = np.loadtxt(args.stamps, dtype=np.float64, ndmin=2)
@@ -98,8 +117,12 @@ def main(argv=None):
     else:
         print("warning: no checkpoint given: the network runs with its initial weights", file=sys.stderr)
     names = [f"{k:06d}" for k in range(len(pairs))]
-    sequence.SequenceInterpolator(net, m, n, layout, args.max_minibatch).run(frames, events, pairs, out_dir=args.out, names=names)
+    runner = sequence.SequenceInterpolator(net, m, n, layout, args.max_minibatch)
+    runner.run(frames, events, pairs, out_dir=args.out, names=names, niqe=niqe_model)
     print(f"{len(pairs)} pairs -> {args.out}")
+    if niqe_model is not None:
+        mean = write_niqe(args.out, [f"{name}_{f:02d}.png" for name, f, _ in runner.niqe_scores], [s for _, _, s in runner.niqe_scores])
+        print(f"NIQE mean {mean:.6f} over {len(runner.niqe_scores)} frames -> {os.path.join(args.out, 'niqe.txt')}")
     return 0
 
 

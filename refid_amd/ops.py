@@ -1025,3 +1025,27 @@ def assemble_single(desc, stages=_lib.ASSEMBLE_ALL | _lib.ASSEMBLE_STATS):
 def seq_assemble_single(desc, stages=_lib.ASSEMBLE_ALL | _lib.ASSEMBLE_STATS):
     """Runs the single-image item assembly of csrc/sequence.hip for an _lib.SeqSingleDesc on the current stream."""
     check(lib().refid_seq_assemble_single(C.byref(desc), int(stages), _stream()), "refid_seq_assemble_single")
+
+
+def niqe_moments(u8, window, bgr=False, crop_border=0, planes=False):
+    """refid_niqe_moments (csrc/niqe.hip) on the current stream: ``u8`` uint8 CUDA (..., H, W, 3), ``window`` the 49 float64
+    weights on the device -> float64 sums (nf, 2 scales, blocks, 5 maps, 5) in the layout of include/refid_hip.h.
+    ``planes=True`` also returns the float32 [Y, MSCN scale 1, MSCN scale 2] planes.  Does not synchronise."""
+    if not u8.is_cuda or u8.dtype != torch.uint8 or u8.dim() < 3 or u8.shape[-1] != 3 or u8.numel() == 0:
+        raise _lib.RefidHipError("niqe_moments: a non-empty uint8 CUDA tensor (..., H, W, 3) is required")
+    if not window.is_cuda or window.dtype != torch.float64 or window.numel() != 49 or not window.is_contiguous():
+        raise _lib.RefidHipError("niqe_moments: window must hold 49 contiguous float64 weights on the device")
+    u8 = u8.contiguous()
+    h, w, cb = int(u8.shape[-3]), int(u8.shape[-2]), int(crop_border)
+    nf = u8.numel() // (3 * h * w)
+    if cb < 0 or h - 2 * cb < 96 or w - 2 * cb < 96:
+        raise _lib.RefidHipError(f"niqe_moments: a {h}x{w} frame with crop_border {cb} holds no 96x96 block")
+    hc, wc = (h - 2 * cb) // 96 * 96, (w - 2 * cb) // 96 * 96
+    sums = torch.empty((nf, 2, (hc // 96) * (wc // 96), 5, 5), dtype=torch.float64, device=u8.device)
+    words = lib().refid_niqe_moments_parts(nf, h, w)
+    parts = torch.empty(words, dtype=torch.int64, device=u8.device) if words > 0 else None
+    outs = [torch.empty((nf, hc // s, wc // s), dtype=torch.float32, device=u8.device) for s in (1, 1, 2)] if planes else [None] * 3
+    ptr = lambda t: None if t is None else t.data_ptr()       # noqa: E731
+    check(lib().refid_niqe_moments(u8.data_ptr(), nf, h, w, _lib.NIQE_BGR if bgr else 0, cb, window.data_ptr(), sums.data_ptr(),
+                                   ptr(parts), ptr(outs[0]), ptr(outs[1]), ptr(outs[2]), _stream()), "refid_niqe_moments")
+    return (sums, outs) if planes else sums

@@ -245,9 +245,17 @@ class _SequenceRunner:
     """What ``SequenceInterpolator`` and ``SequenceDeblurrer`` share: upload the sequence once, assemble minibatch k+1 on a
     side stream while minibatch k runs, crop back to (H, W), quantise with ``metrics.val_tail`` and hand the uint8 frames to
     ``validation.FrameWriter``.  A subclass sets ``net``, ``assembler``, ``max_minibatch``, ``device`` and ``stream`` and
-    gives ``_forward(batch)`` -> (P, ..., 3, h, w) and ``_paths(out_dir, name, u8_item)`` -> one path per frame of an item."""
+    gives ``_forward(batch)`` -> (P, ..., 3, h, w) and ``_paths(out_dir, name, u8_item)`` -> one path per frame of an item.
 
-    def run(self, frames, events, pairs, out_dir=None, names=None, keep=False, bgr=False):
+    ``niqe``: a ``niqe.NiqeModel``.  Every minibatch's uint8 frames then also go through the NIQE moments kernel
+    (csrc/niqe.hip) on the current stream and the few sums per block are copied, non-blocking, into one pinned buffer; the
+    host finish of all frames runs after the loop, which gains no synchronisation.  ``niqe_scores`` then holds
+    ``(name, frame index, score)`` per frame, in output order (None when ``niqe`` was not given)."""
+
+    niqe_scores = None
+
+    def run(self, frames, events, pairs, out_dir=None, names=None, keep=False, bgr=False, niqe=None):
+        from . import niqe as niqe_mod
         from .validation import FrameWriter
         what = type(self).__name__
         pairs = list(pairs)
@@ -262,6 +270,10 @@ class _SequenceRunner:
         asm.load(frames, events, bgr=bgr)
         side.wait_stream(cur)                 # the upload was issued on the current stream
         H, W = asm.height, asm.width
+        self.niqe_scores = None
+        if niqe is not None:
+            niqe_mod.cropped_size(H, W)        # a frame without one 96x96 block raises here, before any work
+        sums_pin, per_item = None, 0           # pinned (all frames, 2, blocks, 5, 5) float64, allocated at the first minibatch
         chunks = [pairs[i:i + self.max_minibatch] for i in range(0, len(pairs), self.max_minibatch)]
 
         def preload(k):
@@ -289,6 +301,13 @@ class _SequenceRunner:
                         base = k * self.max_minibatch
                         paths = [p for i in range(len(chunk)) for p in self._paths(out_dir, names[base + i], u8[i])]
                         writer.dump([(u8.view(-1, H, W, 3), paths)])
+                    if niqe is not None:
+                        sums = niqe_mod.moments(u8.view(-1, H, W, 3), niqe)
+                        if sums_pin is None:
+                            per_item = sums.shape[0] // len(chunk)
+                            sums_pin = torch.empty((len(pairs) * per_item,) + tuple(sums.shape[1:]), dtype=sums.dtype).pin_memory()
+                        at = k * self.max_minibatch * per_item
+                        sums_pin[at:at + sums.shape[0]].copy_(sums, non_blocking=True)
                     if keep:
                         kept.append(u8)
         finally:
@@ -296,6 +315,10 @@ class _SequenceRunner:
             cur.wait_stream(side)
             if writer is not None:
                 writer.close()
+        if niqe is not None:
+            cur.synchronize()                  # the last sums have arrived
+            scores = niqe_mod.finish(sums_pin.numpy(), niqe)
+            self.niqe_scores = [(names[i // per_item], i % per_item, sc) for i, sc in enumerate(scores)]
         return torch.cat(kept, dim=0).cpu().numpy() if keep else None
 
 
@@ -316,11 +339,12 @@ class SequenceInterpolator(_SequenceRunner):
         self.assembler = SequenceAssembler(m, n, layout, multiple=1 << int(net.num_encoders), device=self.device)
         self.stream = torch.cuda.Stream(device=self.device)
 
-    def run(self, frames, events, pairs, out_dir=None, names=None, keep=False, bgr=False):
+    def run(self, frames, events, pairs, out_dir=None, names=None, keep=False, bgr=False, niqe=None):
         """``frames`` uint8 (N, H, W, 3), ``events`` float32 (E, 4), ``pairs`` from ``make_pairs``.  With ``out_dir`` frame f
         of pair k goes to ``{out_dir}/{names[k]}_{f:02d}.png`` (default name: the left key frame's index, six digits, as
-        the validation dumps are named).  ``keep=True`` returns the uint8 frames (P, T, H, W, 3) on the host, else None."""
-        return super().run(frames, events, pairs, out_dir, names, keep, bgr)
+        the validation dumps are named).  ``keep=True`` returns the uint8 frames (P, T, H, W, 3) on the host, else None.
+        ``niqe``: a ``NiqeModel``; ``niqe_scores`` then holds (name, f, score) per output frame."""
+        return super().run(frames, events, pairs, out_dir, names, keep, bgr, niqe)
 
     def _forward(self, batch):
         return self.net(x=batch["lq"], event=batch["voxel"])
@@ -354,11 +378,12 @@ class SequenceDeblurrer(_SequenceRunner):
                                            multiple=int(net.size_multiple), device=self.device)
         self.stream = torch.cuda.Stream(device=self.device)
 
-    def run(self, frames, events, items, out_dir=None, names=None, keep=False, bgr=False):
+    def run(self, frames, events, items, out_dir=None, names=None, keep=False, bgr=False, niqe=None):
         """``frames`` uint8 (N, H, W, 3), ``events`` float32 (E, 4), ``items`` from ``make_pairs(t, *frame_windows(...))``.
         With ``out_dir`` item k goes to ``{out_dir}/{names[k]}.png`` (default name: the frame index, six digits).
-        ``keep=True`` returns the uint8 frames (P, H, W, 3) on the host, else None."""
-        return super().run(frames, events, items, out_dir, names, keep, bgr)
+        ``keep=True`` returns the uint8 frames (P, H, W, 3) on the host, else None.
+        ``niqe``: a ``NiqeModel``; ``niqe_scores`` then holds (name, 0, score) per output frame."""
+        return super().run(frames, events, items, out_dir, names, keep, bgr, niqe)
 
     def _forward(self, batch):
         if self.crop_size is None:
