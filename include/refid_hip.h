@@ -769,6 +769,31 @@ int refid_niqe_moments(const unsigned char* frames_u8, int n_frames, int h, int 
                        const double* window49, double* sums, void* parts, float* y_out, float* mscn1_out,
                        float* mscn2_out, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * PNG reconstruction of inflated key frames (csrc/png.hip): the input is the inflate output of n_frames PNGs of one
+ * (height, width, channels), unchanged and back to back -- per frame `height` rows of 1 + width*channels bytes, the first
+ * byte of a row its filter type (0 None, 1 Sub, 2 Up, 3 Average, 4 Paeth); the output is uint8 (n_frames, height, width, 3)
+ * in the file's channel order, a grey file (channels 1) replicated to three channels.  The arithmetic is the PNG
+ * specification's: per byte a = the byte bpp to the left, b = the byte above, c = the byte above-left, each 0 outside the
+ * image; Sub adds a, Up b, Average (a + b) >> 1 in more than 8 bits, Paeth its predictor with the tie order a, b, c; every
+ * sum modulo 256.  Integers only, no atomics: the bytes do not depend on the launch or on `bands`.
+ * bands: NULL (n_bands 0): one wave per frame.  Otherwise int32 (n_bands, 3) rows [frame, row0, row1): one wave per band,
+ * which decodes rows row0 .. row1-1 taking the row above row0 as zero -- so a band must start at row 0 or at a row of
+ * filter type 0 or 1, which do not read the row above (the caller reads the filter bytes; refid_amd.png.find_bands), and
+ * the bands must cover every row once.  A band outside the frame set is skipped.  A filter byte above 4 adds nothing (as
+ * type 0); callers reject such files on the host.  No row alignment is assumed (the pitch is odd for RGB).
+ * width*channels <= REFID_PNG_MAX_ROW_BYTES (the LDS line that carries a block's last row to the next block): wider files
+ * are decoded on the host.  One launch on `stream`; nothing is allocated, nothing synchronises.
+ * ---------------------------------------------------------------------------------- */
+#define REFID_PNG_MAX_ROW_BYTES 32760
+typedef struct refid_png_unfilter_desc {
+    const uint8_t* rows;                        /* device: n_frames * height * (1 + width*channels) bytes          */
+    uint8_t* frames;                            /* device: (n_frames, height, width, 3)                            */
+    const int32_t* bands;                       /* device or NULL: (n_bands, 3) = frame, row0, row1                */
+    int32_t n_bands, n_frames, height, width, channels;   /* n_bands 0 with bands NULL; channels: 1 or 3          */
+} refid_png_unfilter_desc;
+int refid_png_unfilter(const refid_png_unfilter_desc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

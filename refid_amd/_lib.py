@@ -147,12 +147,21 @@ class SeqSingleDesc(C.Structure):
     ]
 
 
+class PngUnfilterDesc(C.Structure):
+    """refid_png_unfilter_desc: the inflate output of n_frames PNGs of one size -> uint8 (n_frames, height, width, 3)."""
+    _fields_ = [
+        ("rows", C.c_void_p), ("frames", C.c_void_p), ("bands", C.c_void_p),
+        ("n_bands", C.c_int32), ("n_frames", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("channels", C.c_int32),
+    ]
+
+
 LAYOUT_BLUR, LAYOUT_SHARP = 0, 1                # == REFID_LAYOUT_* in include/refid_hip.h
 ASSEMBLE_ZERO, ASSEMBLE_SCATTER, ASSEMBLE_FINISH, ASSEMBLE_FRAMES, ASSEMBLE_ALL = 1, 2, 4, 8, 15
 ASSEMBLE_STATS = 16                              # refid_assemble_single only: voxel_norm's statistics, between scatter and finish
 
 VAL_TAIL_BGR = 1         # == REFID_VAL_TAIL_BGR in include/refid_hip.h
 NIQE_BGR = 1             # == REFID_NIQE_BGR in include/refid_hip.h
+PNG_MAX_ROW_BYTES = 32760    # == REFID_PNG_MAX_ROW_BYTES in include/refid_hip.h
 ABI_VERSION = 9          # == REFID_ABI_VERSION in include/refid_hip.h
 _lib = None
 
@@ -280,6 +289,7 @@ def _bind_extra(L):
     L.refid_niqe_moments_parts.argtypes = [i, i, i]
     L.refid_niqe_moments_parts.restype = ll
     L.refid_niqe_moments.argtypes = [vp, i, i, i, i, i, vp, vp, vp, vp, vp, vp, vp]
+    L.refid_png_unfilter.argtypes = [C.POINTER(PngUnfilterDesc), vp]
 
 
 def check(rc, what):

@@ -16,7 +16,7 @@ import sys
 
 import numpy as np
 
-from .interpolate import load_frames, write_niqe
+from .interpolate import load_frames, load_frames_resident, write_niqe  # noqa: F401  (load_frames: for other callers)
 
 
 def settings(args):
@@ -71,7 +71,7 @@ def main(argv=None):
     if args.niqe:
         from .niqe import NiqeModel
         niqe_model = NiqeModel.load(args.niqe)
-    frames = load_frames(args.frames)
+    frames = load_frames_resident(args.frames)
     events = sequence.load_event_npz(args.events, swap_xy=args.swap_xy)
     stamps = np.loadtxt(args.stamps, dtype=np.float64, ndmin=2)
     if stamps.shape[0] != frames.shape[0]:

@@ -39,6 +39,24 @@ def load_frames(path):
     return stack
 
 
+def load_frames_resident(path):
+    """``--frames`` of the command lines: a directory of PNGs is inflated by a thread pool and unfiltered on the GPU
+    (``sequence.load_png_frames``, csrc/png.hip) into the resident uint8 (N, H, W, 3) tensor the runners take, the same bytes
+    ``load_frames`` gives; a ``.npy`` stack, or a machine without a GPU, goes through ``load_frames``."""
+    import torch
+    if not (os.path.isdir(path) and torch.cuda.is_available()):
+        return load_frames(path)
+    from . import sequence
+    from ._lib import RefidHipError
+    files = sorted(glob.glob(os.path.join(path, "*.png")))
+    if not files:
+        raise SystemExit(f"--frames: no *.png under {path}")
+    try:
+        return sequence.load_png_frames(files)
+    except RefidHipError as e:
+        raise SystemExit(f"--frames: {e}")
+
+
 def write_niqe(out_dir, files, scores):
     """``{out_dir}/niqe.txt``: one ``file score`` line per frame, then ``mean`` over the finite scores (nan when there is
     none).  Returns the mean."""
@@ -97,7 +115,7 @@ def main(argv=None):
     if args.niqe:
         from .niqe import NiqeModel
         niqe_model = NiqeModel.load(args.niqe)
-    frames = load_frames(args.frames)
+    frames = load_frames_resident(args.frames)
     events = sequence.load_event_npz(args.events, swap_xy=args.swap_xy)
     stamps = np.loadtxt(args.stamps, dtype=np.float64, ndmin=2)
     if stamps.shape[0] != frames.shape[0]:

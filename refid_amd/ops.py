@@ -1049,3 +1049,46 @@ def niqe_moments(u8, window, bgr=False, crop_border=0, planes=False):
     check(lib().refid_niqe_moments(u8.data_ptr(), nf, h, w, _lib.NIQE_BGR if bgr else 0, cb, window.data_ptr(), sums.data_ptr(),
                                    ptr(parts), ptr(outs[0]), ptr(outs[1]), ptr(outs[2]), _stream()), "refid_niqe_moments")
     return (sums, outs) if planes else sums
+
+
+def png_unfilter(rows_u8, n, h, w, channels, out=None, split_bands=True, bands=None):
+    """refid_png_unfilter (csrc/png.hip) on the current stream: ``rows_u8`` holds the inflate output of ``n`` PNGs of one
+    (h, w, channels) -- uint8 on the device, n*h*(1 + w*channels) bytes, filter byte first in every row -> uint8
+    (n, h, w, 3), a grey file replicated to three channels.  ``out``: a contiguous uint8 (n, h, w, 3) view to write into.
+    ``split_bands``: one wave per band of rows that does not read the row above it (``png.find_bands``) instead of one per
+    frame; the bytes are the same.  ``bands``: that int32 (n_bands, 3) table from a caller that holds the filter bytes on
+    the host and has checked them; without it the filter-byte column is copied back and checked here, which
+    synchronises.  Does not synchronise otherwise."""
+    import numpy as np
+    from . import png
+    n, h, w, channels = int(n), int(h), int(w), int(channels)
+    if channels not in (1, 3) or min(n, h, w) < 1:
+        raise _lib.RefidHipError(f"png_unfilter: n={n}, h={h}, w={w} must be positive and channels={channels} 1 or 3")
+    if w * channels > _lib.PNG_MAX_ROW_BYTES:
+        raise _lib.RefidHipError(f"png_unfilter: rows of {w * channels} bytes exceed the kernel's line of "
+                                 f"{_lib.PNG_MAX_ROW_BYTES} (decode such files on the host)")
+    pitch = 1 + w * channels
+    if not rows_u8.is_cuda or rows_u8.dtype != torch.uint8 or not rows_u8.is_contiguous() or rows_u8.numel() != n * h * pitch:
+        raise _lib.RefidHipError(f"png_unfilter: rows must be a contiguous uint8 CUDA tensor of {n}*{h}*{pitch} bytes, got "
+                                 f"{rows_u8.dtype} {tuple(rows_u8.shape)} on {rows_u8.device}")
+    if out is None:
+        out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=rows_u8.device)
+    elif out.dtype != torch.uint8 or out.device != rows_u8.device or tuple(out.shape) != (n, h, w, 3) or not out.is_contiguous():
+        raise _lib.RefidHipError(f"png_unfilter: out must be a contiguous uint8 ({n}, {h}, {w}, 3) tensor on {rows_u8.device}")
+    table = None
+    if bands is not None:
+        table = np.ascontiguousarray(np.asarray(bands, dtype=np.int32).reshape(-1, 3))
+    else:
+        filters = png.check_filters(rows_u8.view(n, h, pitch)[:, :, 0].cpu().numpy())
+        if split_bands:
+            table = png.find_bands(filters)
+    if table is not None:
+        if not len(table) or table[:, 0].min() < 0 or table[:, 0].max() >= n or (table[:, 1] < 0).any() or \
+                (table[:, 2] > h).any() or (table[:, 1] >= table[:, 2]).any():
+            raise _lib.RefidHipError(f"png_unfilter: a band lies outside the {n} frames of {h} rows")
+        table = torch.from_numpy(table).pin_memory().to(rows_u8.device, non_blocking=True)
+    desc = _lib.PngUnfilterDesc(rows=rows_u8.data_ptr(), frames=out.data_ptr(), bands=None if table is None else table.data_ptr(),
+                                n_bands=0 if table is None else int(table.shape[0]), n_frames=n, height=h, width=w,
+                                channels=channels)
+    check(lib().refid_png_unfilter(C.byref(desc), _stream()), "refid_png_unfilter")
+    return out

@@ -1,5 +1,6 @@
 """A PNG writer and a reader for 8-bit RGB / grey files on the standard library alone: the validation image dumps of the
-reference go through cv2.imwrite (utils/img_util.py:152-170), and cv2 is not a dependency here.
+reference go through cv2.imwrite (utils/img_util.py:152-170), and cv2 is not a dependency here.  ``read_png`` decodes on
+the host; ``read_filtered`` stops after inflate and leaves the per-row filters to the GPU (csrc/png.hip).
 
 8-bit RGB (H, W, 3) or 8-bit grey (H, W); signature, IHDR, one IDAT, IEND; filter type 0 on every row; one
 ``zlib.compress``.  Level 1 by default: validation writes thousands of 720p frames and the encoder runs on the host."""
@@ -60,8 +61,9 @@ def read_chunks(data):
 def _unfilter(rows, bpp):
     """Undoes the per-row PNG filters (0 None, 1 Sub, 2 Up, 3 Average, 4 Paeth) of ``rows`` (h, 1 + stride) uint8; returns
     (h, stride).  Sub is a running sum along the row and Up adds the finished row above: both vectorised.  Average and
-    Paeth depend on the byte just reconstructed, so they walk the row byte by byte -- correctness first; frames written
-    by this package use filter 0 and never get here."""
+    Paeth depend on the byte just reconstructed, so they walk the row byte by byte: this is the host reference of
+    csrc/png.hip, which decodes the command lines' frame directories on the GPU (``read_filtered``,
+    ``sequence.load_png_frames``); frames written by this package use filter 0 and never get here."""
     h, stride = rows.shape[0], rows.shape[1] - 1
     out = np.zeros((h, stride), dtype=np.uint8)
     zero = np.zeros(stride, dtype=np.uint8)
@@ -93,8 +95,10 @@ def _unfilter(rows, bpp):
     return out
 
 
-def read_png(path):
-    """Decodes an 8-bit RGB / grey, non-interlaced PNG (all five filter types) into a uint8 array (H, W, 3) / (H, W)."""
+def _inflate(path):
+    """(width, height, channels, rows) of an 8-bit RGB / grey, non-interlaced PNG: ``rows`` is the inflate output as uint8
+    (H, 1 + W*channels), filter byte first, not unfiltered (a read-only view of the inflated bytes).  What ``read_png``
+    and ``read_filtered`` share: signature, CRCs, IHDR and the length of the image data."""
     with open(path, "rb") as f:
         chunks = read_chunks(f.read())
     if not chunks or chunks[0][0] != b"IHDR" or chunks[-1][0] != b"IEND":
@@ -106,7 +110,51 @@ def read_png(path):
     raw = zlib.decompress(b"".join(p for t, p in chunks if t == b"IDAT"))
     if len(raw) != h * (1 + w * ch):
         raise ValueError("read_png: image data has the wrong length")
-    rows = np.frombuffer(raw, dtype=np.uint8).reshape(h, 1 + w * ch)
+    return w, h, ch, np.frombuffer(raw, dtype=np.uint8).reshape(h, 1 + w * ch)
+
+
+def read_png(path):
+    """Decodes an 8-bit RGB / grey, non-interlaced PNG (all five filter types) into a uint8 array (H, W, 3) / (H, W)."""
+    w, h, ch, rows = _inflate(path)
     data = _unfilter(rows, ch) if rows[:, 0].any() else rows[:, 1:]
     img = data.reshape(h, w, ch) if ch == 3 else data
     return np.ascontiguousarray(img)
+
+
+def check_filters(filters):
+    """Raises ``_unfilter``'s ValueError for the first filter byte above 4 of ``filters`` (..., H); returns them."""
+    filters = np.asarray(filters)
+    bad = np.flatnonzero(filters.reshape(-1) > 4)
+    if bad.size:
+        raise ValueError(f"read_png: unknown filter type {int(filters.reshape(-1)[bad[0]])} in row {int(bad[0]) % filters.shape[-1]}")
+    return filters
+
+
+def read_filtered(path):
+    """(width, height, channels, rows) with ``rows`` the inflate output, uint8 (H, 1 + W*channels), still filtered: the
+    input of ``ops.png_unfilter`` (csrc/png.hip).  The file checks are ``read_png``'s; the filter bytes are checked here,
+    on the host, so that the kernel never sees one above 4."""
+    w, h, ch, rows = _inflate(path)
+    check_filters(rows[:, 0])
+    return w, h, ch, rows
+
+
+def find_bands(filters, min_rows=64):
+    """The band table of ``refid_png_unfilter`` for the filter bytes ``filters`` (N, H): int32 (n_bands, 3) rows
+    [frame, row0, row1).  A row of type 0 (None) or 1 (Sub) does not read the row above, so a band may start there; one
+    does where the band before has at least ``min_rows`` rows (64: a full wave of the kernel's four; shorter bands leave
+    lanes idle, longer ones leave workgroups idle; 1: every independent run its own band)."""
+    filters = np.asarray(filters)
+    filters = check_filters(filters.reshape(-1, filters.shape[-1]))
+    h, out = filters.shape[1], []
+    for f, column in enumerate(filters):
+        starts = np.flatnonzero(column <= 1)
+        row0 = 0
+        while True:
+            k = np.searchsorted(starts, row0 + max(int(min_rows), 1))
+            row1 = int(starts[k]) if k < starts.size else h
+            out.append((f, row0, row1))
+            if row1 == h:
+                break
+            row0 = row1
+    return np.asarray(out, dtype=np.int32).reshape(-1, 3)

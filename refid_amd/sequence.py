@@ -113,6 +113,88 @@ def load_event_npz(paths, swap_xy=False):
     return out
 
 
+PNG_WORKERS_MAX = 16      # the inflate pool never grows with the machine: a shared box shows more CPUs than a job may use
+
+
+def load_png_frames(paths, device=None, workers=8, frames_per_launch=8):
+    """8-bit RGB / grey PNG key frames of one size -> uint8 (N, H, W, 3) on the device, a grey file replicated to three
+    channels: what ``SequenceAssembler.load`` takes.  ``paths``: the files in order, or a directory (its ``*.png`` sorted
+    by name).  The files are read and inflated by ``workers`` threads (``zlib`` releases the GIL; at most
+    ``PNG_WORKERS_MAX``), their filter bytes are checked on the host, and every chunk of ``frames_per_launch`` frames is
+    copied into one of two pinned staging buffers, uploaded without blocking and unfiltered by one ``refid_png_unfilter``
+    launch (csrc/png.hip) on the current stream, while the pool inflates the next chunk.  A staging buffer is written again
+    only after the event behind its last upload has completed.  Files that differ in (H, W, channels): RefidHipError
+    naming the first one; a broken file: ``png.read_png``'s ValueError.  Rows wider than the kernel's line
+    (``_lib.PNG_MAX_ROW_BYTES``) are decoded on the host by ``png.read_png``.  Does not synchronise at the end."""
+    import glob
+    from concurrent.futures import ThreadPoolExecutor
+    from . import ops, png
+    if isinstance(paths, (str, os.PathLike)):
+        paths = sorted(glob.glob(os.path.join(paths, "*.png"))) if os.path.isdir(paths) else [paths]
+    paths = [os.fspath(p) for p in paths]
+    workers, per = int(workers), int(frames_per_launch)
+    if not paths:
+        raise RefidHipError("load_png_frames: no files")
+    if not 1 <= workers <= PNG_WORKERS_MAX or per < 1:
+        raise RefidHipError(f"load_png_frames: workers {workers} must be 1..{PNG_WORKERS_MAX} and frames_per_launch {per} >= 1")
+    device = torch.device("cuda" if device is None else device)
+    if device.type != "cuda":
+        raise RefidHipError("load_png_frames: a GPU device is required (the HIP path has no CPU fallback)")
+    chunks = [paths[i:i + per] for i in range(0, len(paths), per)]
+    with ThreadPoolExecutor(max_workers=workers) as pool, torch.cuda.device(device):
+        ahead = collections.deque(maxlen=2)                # the chunks being inflated: the one in hand and the next
+
+        def submit(k):
+            if k < len(chunks):
+                ahead.append([pool.submit(png.read_filtered, p) for p in chunks[k]])
+
+        def cancel():
+            for futures in ahead:
+                for f in futures:
+                    f.cancel()
+
+        submit(0)
+        submit(1)
+        w, h, ch, _ = ahead[0][0].result()
+        if w * ch > _lib.PNG_MAX_ROW_BYTES:                # the host route for this file set
+            cancel()
+            imgs = list(pool.map(png.read_png, paths))
+            if len({i.shape for i in imgs}) != 1:
+                first = next(p for p, i in zip(paths, imgs) if i.shape != imgs[0].shape)
+                raise RefidHipError(f"load_png_frames: {first} differs in size from {paths[0]}")
+            imgs = [np.repeat(i[:, :, None], 3, axis=2) if i.ndim == 2 else i for i in imgs]
+            return torch.from_numpy(np.stack(imgs)).to(device)
+        pitch = 1 + w * ch
+        out = torch.empty((len(paths), h, w, 3), dtype=torch.uint8, device=device)
+        staging = [torch.empty((per, h, pitch), dtype=torch.uint8).pin_memory() for _ in range(min(2, len(chunks)))]
+        copied = [None] * len(staging)                     # the event after the upload that last read each buffer
+        for k, chunk in enumerate(chunks):
+            futures = ahead.popleft()
+            submit(k + 2)
+            buf = staging[k % 2]
+            if copied[k % 2] is not None:
+                copied[k % 2].synchronize()
+            for i, (path, fut) in enumerate(zip(chunk, futures)):
+                try:
+                    wi, hi, ci, rows = fut.result()
+                except BaseException:
+                    cancel()
+                    raise
+                if (wi, hi, ci) != (w, h, ch):
+                    cancel()
+                    raise RefidHipError(f"load_png_frames: {path} is {hi}x{wi}x{ci}, {paths[0]} is {h}x{w}x{ch}: the files of a "
+                                        "sequence must share (H, W, channels)")
+                buf[i].numpy()[...] = rows
+            n = len(chunk)
+            bands = png.find_bands(buf[:n, :, 0].numpy())
+            rows_dev = torch.empty((n, h, pitch), dtype=torch.uint8, device=device)
+            rows_dev.copy_(buf[:n], non_blocking=True)
+            copied[k % 2] = torch.cuda.Event()
+            copied[k % 2].record()
+            ops.png_unfilter(rows_dev, n, h, w, ch, out=out[k * per:k * per + n], bands=bands)
+    return out
+
+
 def _round_up(v, multiple):
     return (v + multiple - 1) // multiple * multiple
 
