@@ -794,6 +794,30 @@ typedef struct refid_png_unfilter_desc {
 } refid_png_unfilter_desc;
 int refid_png_unfilter(const refid_png_unfilter_desc* d, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * PNG forward filtering of resident frames (csrc/png_filter.hip): the encoder's half of the section above.  frames: uint8
+ * (n_frames, height, width, 3), contiguous; rows: n_frames * height rows of 1 + 3*width bytes back to back, the filter
+ * type first, then the filtered bytes -- the layout refid_png_unfilter reads, and what deflate takes as it stands.
+ * Per byte a = the byte 3 to the left, b = the byte above, c = the byte above-left, each 0 outside the frame (row 0 of a
+ * frame never reads the frame before); type 0 x, 1 x - a, 2 x - b, 3 x - ((a + b) >> 1), 4 x - Paeth(a, b, c) with the tie
+ * order a, b, c; every residual modulo 256.  mode 0..4 puts that type on every row; REFID_PNG_FILTER_ADAPTIVE chooses per
+ * row the type with the least sum of |residual read as int8| (libpng's heuristic), the lowest type on a tie.  costs: NULL,
+ * or uint32 (n_frames, height, 5): the five sums of every row, in every mode.  Integers only, no atomics: the bytes do not
+ * depend on n_frames, on a frame's position in the call or on the alignment of `rows` (none is assumed; costs: 4 bytes).
+ * Nothing outside [rows, rows + n_frames*height*(1 + 3*width)) is written.  width <= REFID_PNG_FILTER_MAX_WIDTH, where a
+ * row's sum still fits uint32: the kernel itself has no row limit.  One launch on `stream`; nothing is allocated, nothing
+ * synchronises.  A bad argument returns 1 with a message (refid_last_error) and launches nothing.
+ * ---------------------------------------------------------------------------------- */
+#define REFID_PNG_FILTER_ADAPTIVE 5
+#define REFID_PNG_FILTER_MAX_WIDTH 11184810
+typedef struct refid_png_filter_desc {
+    const uint8_t* frames;                      /* device: (n_frames, height, width, 3)                            */
+    uint8_t* rows;                              /* device: n_frames * height * (1 + 3*width) bytes                 */
+    uint32_t* costs;                            /* device or NULL: (n_frames, height, 5)                           */
+    int32_t n_frames, height, width, mode;      /* mode: 0..4 or REFID_PNG_FILTER_ADAPTIVE                          */
+} refid_png_filter_desc;
+int refid_png_filter(const refid_png_filter_desc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -155,6 +155,14 @@ class PngUnfilterDesc(C.Structure):
     ]
 
 
+class PngFilterDesc(C.Structure):
+    """refid_png_filter_desc: uint8 (n_frames, height, width, 3) -> the filtered rows deflate takes, filter byte first."""
+    _fields_ = [
+        ("frames", C.c_void_p), ("rows", C.c_void_p), ("costs", C.c_void_p),
+        ("n_frames", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("mode", C.c_int32),
+    ]
+
+
 LAYOUT_BLUR, LAYOUT_SHARP = 0, 1                # == REFID_LAYOUT_* in include/refid_hip.h
 ASSEMBLE_ZERO, ASSEMBLE_SCATTER, ASSEMBLE_FINISH, ASSEMBLE_FRAMES, ASSEMBLE_ALL = 1, 2, 4, 8, 15
 ASSEMBLE_STATS = 16                              # refid_assemble_single only: voxel_norm's statistics, between scatter and finish
@@ -162,6 +170,8 @@ ASSEMBLE_STATS = 16                              # refid_assemble_single only: v
 VAL_TAIL_BGR = 1         # == REFID_VAL_TAIL_BGR in include/refid_hip.h
 NIQE_BGR = 1             # == REFID_NIQE_BGR in include/refid_hip.h
 PNG_MAX_ROW_BYTES = 32760    # == REFID_PNG_MAX_ROW_BYTES in include/refid_hip.h
+PNG_FILTER_ADAPTIVE = 5      # == REFID_PNG_FILTER_ADAPTIVE in include/refid_hip.h
+PNG_FILTER_MAX_WIDTH = 11184810    # == REFID_PNG_FILTER_MAX_WIDTH in include/refid_hip.h
 ABI_VERSION = 9          # == REFID_ABI_VERSION in include/refid_hip.h
 _lib = None
 
@@ -290,6 +300,7 @@ def _bind_extra(L):
     L.refid_niqe_moments_parts.restype = ll
     L.refid_niqe_moments.argtypes = [vp, i, i, i, i, i, vp, vp, vp, vp, vp, vp, vp]
     L.refid_png_unfilter.argtypes = [C.POINTER(PngUnfilterDesc), vp]
+    L.refid_png_filter.argtypes = [C.POINTER(PngFilterDesc), vp]
 
 
 def check(rc, what):

@@ -16,7 +16,7 @@ import sys
 
 import numpy as np
 
-from .interpolate import load_frames, load_frames_resident, write_niqe  # noqa: F401  (load_frames: for other callers)
+from .interpolate import load_frames, load_frames_resident, png_filter_setting, write_niqe  # noqa: F401  (load_frames: for other callers)
 
 
 def settings(args):
@@ -61,6 +61,9 @@ def main(argv=None):
     ap.add_argument("--stamps-mode", choices=("events", "bounds"), default="events",
                     help="normalise event times from the first to the last event of a window, or from start to end")
     ap.add_argument("--niqe", metavar="PARAMS.npz", help="score every output frame with NIQE (niqe_pris_params.npz) -> niqe.txt")
+    ap.add_argument("--png-filter", choices=("none", "adaptive"),
+                    help="PNG row filters of the output: none (type 0 on every row) or adaptive (chosen per row on the GPU: "
+                         "smaller files, cheaper to write); default: val.png_filter of --opt, else none")
     args = ap.parse_args(argv)
 
     import torch
@@ -88,7 +91,7 @@ def main(argv=None):
         print("warning: no checkpoint given: the network runs with its initial weights", file=sys.stderr)
     names = [f"{k:06d}" for k in range(len(items))]
     runner = sequence.SequenceDeblurrer(net, bins, mb, crop)
-    runner.run(frames, events, items, out_dir=args.out, names=names, niqe=niqe_model)
+    runner.run(frames, events, items, out_dir=args.out, names=names, niqe=niqe_model, png_filter=png_filter_setting(args))
     print(f"{len(items)} frames -> {args.out}")
     if niqe_model is not None:
         mean = write_niqe(args.out, [f"{name}.png" for name, _, _ in runner.niqe_scores], [s for _, _, s in runner.niqe_scores])

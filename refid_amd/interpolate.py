@@ -91,6 +91,23 @@ def settings(args):
     return net, ckpt, int(m), int(n), layout
 
 
+def png_filter_setting(args):
+    """``--png-filter``, else ``val.png_filter`` of ``--opt``, else 'none' (what ``settings`` leaves out: it is the same
+    for both command lines)."""
+    from ._lib import RefidHipError
+    from .validation import check_png_filter
+    if args.png_filter is not None:
+        return args.png_filter
+    if args.opt:
+        from .options import parse
+        val = parse(args.opt, is_train=False).get("val") or {}
+        try:
+            return check_png_filter(val.get("png_filter"), "--opt: val.png_filter")
+        except RefidHipError as ex:
+            raise SystemExit(str(ex))
+    return "none"
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m refid_amd.interpolate", description=__doc__.split("\n\n")[0])
     ap.add_argument("--opt", help="a test YAML: network_g, path.pretrain_network_g, datasets.test.num_*")
@@ -105,6 +122,9 @@ def main(argv=None):
     ap.add_argument("--max-minibatch", type=int, default=2)
     ap.add_argument("--swap-xy", action="store_true", help="the HighREV files' swapped x / y columns")
     ap.add_argument("--niqe", metavar="PARAMS.npz", help="score every output frame with NIQE (niqe_pris_params.npz) -> niqe.txt")
+    ap.add_argument("--png-filter", choices=("none", "adaptive"),
+                    help="PNG row filters of the output: none (type 0 on every row) or adaptive (chosen per row on the GPU: "
+                         "smaller files, cheaper to write); default: val.png_filter of --opt, else none")
     args = ap.parse_args(argv)
 
     import torch
@@ -136,7 +156,7 @@ def main(argv=None):
         print("warning: no checkpoint given: the network runs with its initial weights", file=sys.stderr)
     names = [f"{k:06d}" for k in range(len(pairs))]
     runner = sequence.SequenceInterpolator(net, m, n, layout, args.max_minibatch)
-    runner.run(frames, events, pairs, out_dir=args.out, names=names, niqe=niqe_model)
+    runner.run(frames, events, pairs, out_dir=args.out, names=names, niqe=niqe_model, png_filter=png_filter_setting(args))
     print(f"{len(pairs)} pairs -> {args.out}")
     if niqe_model is not None:
         mean = write_niqe(args.out, [f"{name}_{f:02d}.png" for name, f, _ in runner.niqe_scores], [s for _, _, s in runner.niqe_scores])

@@ -1092,3 +1092,37 @@ def png_unfilter(rows_u8, n, h, w, channels, out=None, split_bands=True, bands=N
                                 channels=channels)
     check(lib().refid_png_unfilter(C.byref(desc), _stream()), "refid_png_unfilter")
     return out
+
+
+def png_filter(frames_u8, mode="adaptive", out=None, costs=None):
+    """refid_png_filter (csrc/png_filter.hip) on the current stream: uint8 CUDA frames (N, H, W, 3) -> the filtered rows of
+    N PNGs, uint8 (N, H, 1 + 3W), the filter byte first in every row: what ``png.encode_png_rows`` deflates and what
+    ``png_unfilter`` reads.  ``mode``: 'adaptive' (per row the type with the least sum of |residual as int8|, the lowest
+    type on a tie) or a type number 0..4 (None, Sub, Up, Average, Paeth) for every row.  ``out``: a contiguous uint8
+    tensor of N*H*(1 + 3W) elements to write into (any alignment; nothing outside it is written); the result is a view of
+    it.  ``costs``: an int32 tensor (N, H, 5) that receives the five sums of every row (the bits of the header's
+    uint32).  Does not synchronise."""
+    f = frames_u8
+    if not isinstance(f, torch.Tensor) or not f.is_cuda or f.dtype != torch.uint8 or f.dim() != 4 or f.shape[-1] != 3 or \
+            f.numel() == 0 or not f.is_contiguous():
+        raise _lib.RefidHipError("png_filter: a non-empty contiguous uint8 CUDA tensor (N, H, W, 3) is required, got "
+                                 + (f"{f.dtype} {tuple(f.shape)} on {f.device}" if isinstance(f, torch.Tensor) else type(f).__name__))
+    if mode != "adaptive" and not (type(mode) is int and 0 <= mode <= 4):
+        raise _lib.RefidHipError(f"png_filter: mode {mode!r} is neither 'adaptive' nor a type number 0..4")
+    code = _lib.PNG_FILTER_ADAPTIVE if mode == "adaptive" else mode
+    n, h, w = int(f.shape[0]), int(f.shape[1]), int(f.shape[2])
+    if w > _lib.PNG_FILTER_MAX_WIDTH:
+        raise _lib.RefidHipError(f"png_filter: width {w} exceeds {_lib.PNG_FILTER_MAX_WIDTH} (write such frames with filter 0)")
+    pitch = 1 + 3 * w
+    if out is None:
+        out = torch.empty((n, h, pitch), dtype=torch.uint8, device=f.device)
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != f.device or \
+            out.numel() != n * h * pitch or not out.is_contiguous():
+        raise _lib.RefidHipError(f"png_filter: out must be a contiguous uint8 tensor of {n}*{h}*{pitch} elements on {f.device}")
+    if costs is not None and (not isinstance(costs, torch.Tensor) or costs.dtype != torch.int32 or costs.device != f.device or
+                              tuple(costs.shape) != (n, h, 5) or not costs.is_contiguous()):
+        raise _lib.RefidHipError(f"png_filter: costs must be a contiguous int32 ({n}, {h}, 5) tensor on {f.device}")
+    desc = _lib.PngFilterDesc(frames=f.data_ptr(), rows=out.data_ptr(), costs=None if costs is None else costs.data_ptr(),
+                              n_frames=n, height=h, width=w, mode=code)
+    check(lib().refid_png_filter(C.byref(desc), _stream()), "refid_png_filter")
+    return out.view(n, h, pitch)

@@ -3,7 +3,8 @@ reference go through cv2.imwrite (utils/img_util.py:152-170), and cv2 is not a d
 the host; ``read_filtered`` stops after inflate and leaves the per-row filters to the GPU (csrc/png.hip).
 
 8-bit RGB (H, W, 3) or 8-bit grey (H, W); signature, IHDR, one IDAT, IEND; filter type 0 on every row; one
-``zlib.compress``.  Level 1 by default: validation writes thousands of 720p frames and the encoder runs on the host."""
+``zlib.compress``.  Level 1 by default: validation writes thousands of 720p frames and the encoder runs on the host.
+``encode_png_rows`` / ``write_png_rows`` take rows the GPU has already filtered (``ops.png_filter``, csrc/png_filter.hip)."""
 import os
 import struct
 import zlib
@@ -31,6 +32,35 @@ def encode_png(img, level=1):
 def write_png(path, img, level=1):
     """img: uint8 numpy array, (H, W, 3) in RGB order or (H, W).  Creates the parent directory, as imwrite does."""
     data = encode_png(img, level)
+    parent = os.path.dirname(os.path.abspath(path))
+    os.makedirs(parent, exist_ok=True)
+    with open(path, "wb") as f:
+        f.write(data)
+    return path
+
+
+def encode_png_rows(rows, width, height, level=1, strategy=zlib.Z_HUFFMAN_ONLY):
+    """The PNG (8-bit RGB) of rows that are ALREADY filtered: uint8, ``height`` rows of 1 + 3*``width`` bytes, the filter type
+    (0..4) first in every row -- the output of ``ops.png_filter`` (csrc/png_filter.hip).  Signature, IHDR, one IDAT, IEND;
+    the IDAT is one zlib stream from ``zlib.compressobj(level, DEFLATED, 15, 8, strategy)``.  Filtered rows are mostly small
+    residuals, which Huffman codes already capture: Z_HUFFMAN_ONLY (the default) and Z_RLE skip the string matcher, where
+    a deflate at level 1 spends its time.  Z_HUFFMAN_ONLY was the faster and the smaller of the two on every measured set
+    (tools/bench_png_encode.py); it spends at least one bit per byte, so frames with large flat areas
+    (long runs of zero residuals) come out smaller with ``strategy=zlib.Z_RLE``.  Every strategy gives a stream any
+    inflate reads."""
+    rows = np.asarray(rows)
+    width, height = int(width), int(height)
+    if rows.dtype != np.uint8 or width < 1 or height < 1 or rows.size != height * (1 + 3 * width):
+        raise ValueError(f"write_png_rows: uint8 rows of {height}*(1 + 3*{width}) bytes expected, got {rows.dtype} {rows.shape}")
+    deflate = zlib.compressobj(level, zlib.DEFLATED, 15, 8, strategy)
+    data = deflate.compress(np.ascontiguousarray(rows).reshape(-1).data) + deflate.flush()
+    ihdr = struct.pack(">IIBBBBB", width, height, 8, 2, 0, 0, 0)
+    return SIGNATURE + _chunk(b"IHDR", ihdr) + _chunk(b"IDAT", data) + _chunk(b"IEND", b"")
+
+
+def write_png_rows(path, rows, width, height, level=1, strategy=zlib.Z_HUFFMAN_ONLY):
+    """As ``write_png``, for rows that are already filtered (``encode_png_rows``)."""
+    data = encode_png_rows(rows, width, height, level, strategy)
     parent = os.path.dirname(os.path.abspath(path))
     os.makedirs(parent, exist_ok=True)
     with open(path, "wb") as f:

@@ -3,21 +3,38 @@
 The uint8 frames that ``metrics.val_tail`` leaves on the device go to one of two pinned host buffers on a side stream;
 a small thread pool encodes and writes the PNGs.  The buffers alternate, so the copy and the encoding of item k overlap
 the forward pass of item k+1.  A worker reads a pinned buffer only after the copy's event has completed, and a buffer
-is reused only after every job that reads it has finished.  No fp32 frame leaves the device."""
+is reused only after every job that reads it has finished.  No fp32 frame leaves the device.
+
+``png_filter='adaptive'``: the frames are first filtered on the device (``ops.png_filter``, csrc/png_filter.hip: per row the
+PNG filter type libpng's heuristic picks) on the current stream; the filtered rows -- one byte per row more than the
+frames -- take the frames' place in the pinned buffers and the workers only deflate them (``png.write_png_rows``).  The
+files hold the same pixels; they are smaller and cheaper to deflate on anything but flat frames."""
 import threading
 from concurrent.futures import ThreadPoolExecutor
 
 import torch
 
-from .png import write_png
+from . import _lib
+from .png import write_png, write_png_rows
+
+PNG_FILTERS = ("none", "adaptive")
+
+
+def check_png_filter(value, where="png_filter"):
+    """'none' (or None: an absent key) / 'adaptive'; anything else raises, naming ``where``."""
+    value = "none" if value is None else value
+    if value not in PNG_FILTERS:
+        raise _lib.RefidHipError(f"{where}: {value!r} is not one of {', '.join(PNG_FILTERS)}")
+    return value
 
 
 class FrameWriter:
     WORKERS = 4              # encoding is zlib (releases the GIL); never sized from the machine's core count
     QUEUE = 32               # jobs submitted and not finished; `dump` blocks beyond that
 
-    def __init__(self, device, level=1):
+    def __init__(self, device, level=1, png_filter="none"):
         self.level = level
+        self.png_filter = check_png_filter(png_filter, "FrameWriter: png_filter")
         self.stream = torch.cuda.Stream(device)
         self.slots = [dict(buf=None, jobs=[]), dict(buf=None, jobs=[])]
         self.turn = 0
@@ -29,29 +46,43 @@ class FrameWriter:
         slot = self.slots[self.turn]
         self.turn ^= 1
         self._drain(slot)                                   # its previous item is written: the buffer may be overwritten
-        total = sum(t.numel() for t, _ in batches)
+        # (tensor, paths, width): the width marks rows the device has filtered, launched here on the current stream
+        batches = [self._filtered(t, paths) if self.png_filter == "adaptive" else (t, paths, None) for t, paths in batches]
+        total = sum(t.numel() for t, _, _ in batches)
         if slot["buf"] is None or slot["buf"].numel() < total:
             slot["buf"] = torch.empty(total, dtype=torch.uint8).pin_memory()
         self.stream.wait_stream(torch.cuda.current_stream())
         views, off = [], 0
         with torch.cuda.stream(self.stream):
-            for t, paths in batches:
+            for t, paths, width in batches:
                 dst = slot["buf"][off:off + t.numel()].view(t.shape)
                 dst.copy_(t, non_blocking=True)
                 t.record_stream(self.stream)                # the allocator must not hand t's block out before the copy ran
-                views.append((dst.numpy(), paths))
+                views.append((dst.numpy(), paths, width))
                 off += t.numel()
             done = torch.cuda.Event()
             done.record(self.stream)
-        for frames, paths in views:
+        for frames, paths, width in views:
             for i, path in enumerate(paths):
                 self.room.acquire()
-                slot["jobs"].append(self.pool.submit(self._job, done, frames[i], path))
+                slot["jobs"].append(self.pool.submit(self._job, done, frames[i], path, width))
 
-    def _job(self, done, frame, path):
+    @staticmethod
+    def _filtered(t, paths):
+        """(filtered rows (N, H, 1 + 3W) of t, paths, W), launched on the current stream; frames wider than the kernel
+        takes stay as they are (filter 0 on the host)."""
+        from . import ops
+        if t.dim() != 4 or t.shape[-1] != 3 or t.shape[2] > _lib.PNG_FILTER_MAX_WIDTH:
+            return t, paths, None
+        return ops.png_filter(t.contiguous(), "adaptive"), paths, int(t.shape[2])
+
+    def _job(self, done, frame, path, width=None):
         try:
             done.synchronize()                              # nothing reads the pinned buffer before its copy has completed
-            write_png(path, frame, self.level)
+            if width is None:
+                write_png(path, frame, self.level)
+            else:                                           # rows the device has filtered
+                write_png_rows(path, frame, width, frame.shape[0], self.level)
         finally:
             self.room.release()
 
