@@ -4,7 +4,7 @@
 //     restricted to the crop window,
 //   * triple_random_crop + augment (transforms.py:110-129, 212-231): crop, hflip, vflip, transpose,
 //   * img2tensor + imfrombytes' /255 (img_util.py:9-33, 147): BGR -> RGB, HWC -> CHW, float32,
-//   * lq = blur0 | bins 1..m-1 | blur1 | bins m+2+n.. and the sliding two-bin `voxel` (image_npy_dataset.py:211-232).
+//   * lq = blur0 | bins 1..m-1 | blur1 | bins m+2+n.. and the sliding two-bin `voxel` (:211-232; event_fixed.h's helpers).
 // Three kernels per BATCH (grid.y/z walk the samples through a device-resident descriptor table), after one memset.
 //
 // Arithmetic.  ts = (bins-1)*(t-first)/dT is three correctly rounded fp32 operations in the reference's order (numpy
@@ -44,7 +44,6 @@ struct BatchGeom {
     int oh, ow;          // output plane
     int lq_chn;          // blur layout: channels of lq
 };
-constexpr int LAYOUT_SINGLE = 2;   // refid_assemble_single only: frame 0 -> lq (B,3,h,w), frame 1 -> gt (B,3,h,w)
 
 // (cy, cx) in the crop -> flat index in the output plane: hflip, vflip, then transpose (transforms.py:116-128)
 __device__ __forceinline__ int out_index(const refid_sample_desc& s, const BatchGeom& g, int cy, int cx) {
@@ -88,14 +87,7 @@ __global__ __launch_bounds__(256) void sample_finish_kernel(BatchGeom g, const l
     } else {
         v[0] = fixed_to_float(src[0]);
     }
-    float* vox = voxel + (long long)b * (g.bins - 1) * 2 * plane + e;           // (bins-1, 2, h, w)
-    if (i < g.bins - 1) store_v<V>(vox + ((long long)i * 2 + 0) * plane, v);   // image_npy_dataset.py:226-232
-    if (i >= 1) store_v<V>(vox + ((long long)(i - 1) * 2 + 1) * plane, v);
-    if (g.layout == REFID_LAYOUT_BLUR) {                                       // image_npy_dataset.py:211-221
-        float* l = lq + (long long)b * g.lq_chn * plane + e;
-        if (i >= 1 && i <= g.m - 1) store_v<V>(l + (long long)(3 + (i - 1)) * plane, v);
-        if (i >= g.m + 2 + g.n) store_v<V>(l + (long long)(3 + (g.m - 1) + 3 + (i - (g.m + 2 + g.n))) * plane, v);
-    }
+    store_bin_plane<V>(g, b, i, plane, e, v, lq, voxel);
 }
 
 // grid = (chunks of the plane, 2 + n_gt frames, batch); one thread = V consecutive output pixels x 3 channels
@@ -120,11 +112,10 @@ __global__ __launch_bounds__(256) void sample_frames_kernel(const refid_sample_d
         c[1][k] = (float)px[1] / 255.f;
         c[2][k] = (float)px[0] / 255.f;
     }
-    float* dst;
-    if (g.layout == LAYOUT_SINGLE) dst = (f == 0 ? lq : gt) + (long long)b * 3 * plane;
+    float* dst;                                                                // single: frame 1 -> gt, laid out as lq
+    if (g.layout == LAYOUT_SINGLE) dst = lq_frame_dst(g, f == 0 ? lq : gt, b, f, plane);
     else if (f >= 2) dst = gt + ((long long)b * (g.bins - 1) + (f - 2)) * 3 * plane;
-    else if (g.layout == REFID_LAYOUT_BLUR) dst = lq + ((long long)b * g.lq_chn + (f == 0 ? 0 : 3 + (g.m - 1))) * plane;
-    else dst = lq + ((long long)b * 2 + f) * 3 * plane;
+    else dst = lq_frame_dst(g, lq, b, f, plane);
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) store_v<V>(dst + ch * plane + e, c[ch]);
 }
@@ -185,9 +176,7 @@ static int launch_zero_scatter(const refid_sample_desc* tab_dev, int batch, cons
         REFID_CHECK(e == hipSuccess, "assemble: memset failed: %s", hipGetErrorString(e));
     }
     if ((stages & REFID_ASSEMBLE_SCATTER) && max_events > 0) {
-        long long nbx = (max_events + 255) / 256;
-        if (nbx > 2048) nbx = 2048;
-        hipLaunchKernelGGL(sample_scatter_kernel, dim3((unsigned)nbx, batch), dim3(256), 0, st, tab_dev, g,
+        hipLaunchKernelGGL(sample_scatter_kernel, dim3(scatter_grid_x(max_events), batch), dim3(256), 0, st, tab_dev, g,
                            reinterpret_cast<unsigned long long*>(scratch));
         REFID_LAUNCH_CHECK("assemble: scatter");
     }

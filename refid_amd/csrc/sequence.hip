@@ -4,8 +4,9 @@
 // image_npy_dataset.py:155-232) minus the ground truth, the crop and the flips.  Three kernels per call (grid.y/z walk
 // the pairs through a device-resident table), after one memset.
 //
-// Arithmetic: event_fixed.h, shared with sample.hip -- fp32 normalisation in three roundings, 64-bit fixed point with 32
-// fractional bits by integer atomics, one rounding to fp32.  Frames are u8 -> x / 255.f, one correctly rounded division.
+// Arithmetic and output layouts: event_fixed.h, shared with sample.hip -- fp32 normalisation in three roundings, 64-bit fixed
+// point with 32 fractional bits by integer atomics, one rounding to fp32.  Frames are u8 -> x / 255.f, one correctly rounded
+// division.  Host side: seq_plan.h has the argument checks of both entry points, seq_launch below their launch sequence.
 //
 // Padding: the network takes sides that are multiples of 2^num_encoders, frames come in any size (BS-ERGB: 970x625).  The
 // outputs are (out_h, out_w) planes; the finish and frames kernels write EVERY element of them, so there is no separate
@@ -21,11 +22,10 @@
 
 #include "common.h"
 #include "event_fixed.h"
+#include "seq_plan.h"
 #include "voxel_norm.h"
 
 namespace {
-
-constexpr int LAYOUT_SINGLE = 2;   // refid_seq_assemble_single only: frame `left` -> lq (P, 3, oh, ow)
 
 struct SeqGeom {
     int bins, m, n, layout;
@@ -64,16 +64,8 @@ __global__ __launch_bounds__(256) void seq_finish_kernel(SeqGeom g, const long l
     const int r = (int)(e / g.ow), c0 = (int)(e % g.ow);
     const long long* src = scratch + ((long long)b * g.bins + i) * ((long long)g.h * g.w) + (long long)r * g.w;
     float v[V];
-#pragma unroll
-    for (int k = 0; k < V; ++k) v[k] = (r < g.h && c0 + k < g.w) ? fixed_to_float(src[c0 + k]) : 0.f;
-    float* vox = voxel + (long long)b * (g.bins - 1) * 2 * oplane + e;          // (bins-1, 2, oh, ow)
-    if (i < g.bins - 1) store_v<V>(vox + ((long long)i * 2 + 0) * oplane, v);  // image_npy_dataset.py:226-232
-    if (i >= 1) store_v<V>(vox + ((long long)(i - 1) * 2 + 1) * oplane, v);
-    if (g.layout == REFID_LAYOUT_BLUR) {                                       // image_npy_dataset.py:211-221
-        float* l = lq + (long long)b * g.lq_chn * oplane + e;
-        if (i >= 1 && i <= g.m - 1) store_v<V>(l + (long long)(3 + (i - 1)) * oplane, v);
-        if (i >= g.m + 2 + g.n) store_v<V>(l + (long long)(3 + (g.m - 1) + 3 + (i - (g.m + 2 + g.n))) * oplane, v);
-    }
+    load_padded<V>(g, src, r, c0, v);
+    store_bin_plane<V>(g, b, i, oplane, e, v, lq, voxel);
 }
 
 // grid = (chunks of the OUTPUT plane, 2 key frames, pairs); one thread = V consecutive output pixels x 3 channels
@@ -97,10 +89,7 @@ __global__ __launch_bounds__(256) void seq_frames_kernel(const unsigned char* __
         c[1][k] = (float)px[1] / 255.f;
         c[2][k] = (float)px[2 - rch] / 255.f;
     }
-    float* dst;
-    if (g.layout == LAYOUT_SINGLE) dst = lq + (long long)b * 3 * oplane;       // (launched with one frame per item: f == 0)
-    else if (g.layout == REFID_LAYOUT_BLUR) dst = lq + ((long long)b * g.lq_chn + (f == 0 ? 0 : 3 + (g.m - 1))) * oplane;
-    else dst = lq + ((long long)b * 2 + f) * 3 * oplane;
+    float* dst = lq_frame_dst(g, lq, b, f, oplane);                            // (single: one frame per item, f == 0)
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) store_v<V>(dst + ch * oplane + e, c[ch]);
 }
@@ -123,160 +112,101 @@ __global__ __launch_bounds__(256) void seq_single_finish_kernel(SeqGeom g, const
     const int r = (int)(e / g.ow), c0 = (int)(e % g.ow);
     const long long* src = scratch + ((long long)b * g.bins + i) * ((long long)g.h * g.w) + (long long)r * g.w;
     float v[V];
-#pragma unroll
-    for (int k = 0; k < V; ++k) v[k] = (r < g.h && c0 + k < g.w) ? fixed_to_float(src[c0 + k]) : 0.f;
+    load_padded<V>(g, src, r, c0, v);
     if (parts) vn_apply<V>(v, sh_ok != 0, sh_ms[0], sh_ms[1]);
     store_v<V>(voxel + ((long long)b * g.bins + i) * oplane + e, v);
 }
 
 }  // namespace
 
-#define SEQ_CHECK(cond, ...)                      \
-    do {                                          \
-        if (!(cond)) {                            \
-            refid_set_error(__VA_ARGS__);         \
-            return -1;                            \
-        }                                         \
-    } while (0)
+static int seq_launched(const char* who, const char* stage) {                  // REFID_LAUNCH_CHECK with the caller's prefix
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) refid_set_error("%s: %s: launch failed: %s", who, stage, hipGetErrorString(e));
+    return e != hipSuccess ? 2 : 0;
+}
 
-extern "C" int refid_seq_assemble(const refid_seq_desc* d, int stages, void* stream) {
-    SEQ_CHECK(d, "seq_assemble: null descriptor");
-    SEQ_CHECK(d->lq && d->voxel, "seq_assemble: null outputs (lq %p, voxel %p)", (void*)d->lq, (void*)d->voxel);
-    SEQ_CHECK(d->scratch, "seq_assemble: null scratch");
-    SEQ_CHECK(d->pairs_host && d->pairs_dev && d->n_pairs > 0 && d->n_pairs <= 65535,
-              "seq_assemble: n_pairs %d needs 1..65535 pairs and both pair tables", d->n_pairs);
-    const int bins = refid_assemble_bins(d->m, d->n, d->layout);               // sets the error text itself
-    if (bins < 0) return -1;
-    SEQ_CHECK(d->n_events >= 0 && (d->n_events == 0 || d->events) && ((uintptr_t)d->events & 15) == 0,
-              "seq_assemble: events must be %lld 16-byte aligned float32 rows", d->n_events);
-    SEQ_CHECK(d->frames && d->n_frames > 0 && d->height > 0 && d->width > 0, "seq_assemble: no frames (n_frames %d, %dx%d)",
-              d->n_frames, d->height, d->width);
-    SEQ_CHECK((long long)d->row_pitch >= 3ll * d->width &&
-              d->frame_stride >= (long long)(d->height - 1) * d->row_pitch + 3ll * d->width,
-              "seq_assemble: row_pitch %d / frame_stride %lld too small for %dx%d frames", d->row_pitch, d->frame_stride,
-              d->height, d->width);
-    SEQ_CHECK(d->out_h >= d->height, "seq_assemble: out_h %d < height %d", d->out_h, d->height);
-    SEQ_CHECK(d->out_w >= d->width, "seq_assemble: out_w %d < width %d", d->out_w, d->width);
-    SEQ_CHECK((long long)d->out_h * d->out_w <= (1ll << 30), "seq_assemble: out_h x out_w %dx%d too large", d->out_h, d->out_w);
-    long long max_rows = 0;
-    for (int p = 0; p < d->n_pairs; ++p) {
-        const refid_seq_pair& s = d->pairs_host[p];
-        SEQ_CHECK(s.left >= 0 && s.left < d->n_frames, "seq_assemble: pair %d: left %d outside the %d frames", p, s.left, d->n_frames);
-        SEQ_CHECK(s.right >= 0 && s.right < d->n_frames, "seq_assemble: pair %d: right %d outside the %d frames", p, s.right,
-                  d->n_frames);
-        SEQ_CHECK(s.row0 >= 0 && s.row0 <= s.row1, "seq_assemble: pair %d: row0 %lld > row1 %lld (or negative)", p, s.row0, s.row1);
-        SEQ_CHECK(s.row1 <= d->n_events, "seq_assemble: pair %d: row1 %lld > n_events %lld", p, s.row1, d->n_events);
-        if (s.row1 - s.row0 > max_rows) max_rows = s.row1 - s.row0;
-    }
+static SeqGeom seq_geom(const SeqArgs& a, int bins, int m, int n, int layout) {
     SeqGeom g;
-    g.bins = bins; g.m = d->m; g.n = d->n; g.layout = d->layout;
-    g.h = d->height; g.w = d->width; g.oh = d->out_h; g.ow = d->out_w;
-    g.lq_chn = 6 + 2 * (d->m - 1);
-    g.bgr = d->bgr; g.row_pitch = d->row_pitch; g.frame_stride = d->frame_stride;
+    g.bins = bins; g.m = m; g.n = n; g.layout = layout;
+    g.h = a.height; g.w = a.width; g.oh = a.out_h; g.ow = a.out_w;
+    g.lq_chn = layout == LAYOUT_SINGLE ? 3 : 6 + 2 * (m - 1);
+    g.bgr = a.bgr; g.row_pitch = a.row_pitch; g.frame_stride = a.frame_stride;
+    return g;
+}
+
+// The stages of both entry points in their order: zero, scatter, the entry point's own `finish(vec, chunks)` (its
+// statistics and finish launches, which test `stages` themselves; non-zero: returned), frames (n_frames per item).
+// vec: four-element stores; chunks: grid.x of the finish and frames kernels.
+template <class Finish>
+static int seq_launch(const SeqArgs& a, const SeqGeom& g, long long max_rows, int n_frames, int stages, hipStream_t st,
+                      Finish finish) {
     const long long plane = (long long)g.h * g.w, oplane = (long long)g.oh * g.ow;
-    hipStream_t st = (hipStream_t)stream;
     if (stages & REFID_ASSEMBLE_ZERO) {
-        hipError_t e = hipMemsetAsync(d->scratch, 0, sizeof(long long) * (size_t)d->n_pairs * bins * plane, st);
-        SEQ_CHECK(e == hipSuccess, "seq_assemble: memset failed: %s", hipGetErrorString(e));
+        hipError_t e = hipMemsetAsync(a.scratch, 0, sizeof(long long) * (size_t)a.count * g.bins * plane, st);
+        SEQ_CHECK(e == hipSuccess, "%s: memset failed: %s", a.who, hipGetErrorString(e));
     }
     if ((stages & REFID_ASSEMBLE_SCATTER) && max_rows > 0) {
-        long long nbx = (max_rows + 255) / 256;
-        if (nbx > 2048) nbx = 2048;
-        hipLaunchKernelGGL(seq_scatter_kernel, dim3((unsigned)nbx, d->n_pairs), dim3(256), 0, st,
-                           reinterpret_cast<const float4*>(d->events), d->pairs_dev, g,
-                           reinterpret_cast<unsigned long long*>(d->scratch));
-        REFID_LAUNCH_CHECK("seq_assemble: scatter");
+        hipLaunchKernelGGL(seq_scatter_kernel, dim3(scatter_grid_x(max_rows), a.count), dim3(256), 0, st,
+                           reinterpret_cast<const float4*>(a.events), a.tab_dev, g,
+                           reinterpret_cast<unsigned long long*>(a.scratch));
+        if (int rc = seq_launched(a.who, "scatter")) return rc;
     }
     // four-element stores: rows are a whole number of them, and every plane of both outputs starts 16-byte aligned
-    const bool vec = (g.ow & 3) == 0 && (((uintptr_t)d->lq | (uintptr_t)d->voxel) & 15) == 0;
+    const bool vec = (g.ow & 3) == 0 && (((uintptr_t)a.lq | (uintptr_t)a.voxel) & 15) == 0;
     const unsigned chunks = (unsigned)(((vec ? oplane / 4 : oplane) + 255) / 256);
-    if (stages & REFID_ASSEMBLE_FINISH) {
-        if (vec) hipLaunchKernelGGL(seq_finish_kernel<4>, dim3(chunks, bins, d->n_pairs), dim3(256), 0, st, g, d->scratch, d->lq, d->voxel);
-        else hipLaunchKernelGGL(seq_finish_kernel<1>, dim3(chunks, bins, d->n_pairs), dim3(256), 0, st, g, d->scratch, d->lq, d->voxel);
-        REFID_LAUNCH_CHECK("seq_assemble: finish");
-    }
+    if (int rc = finish(vec, chunks)) return rc;
     if (stages & REFID_ASSEMBLE_FRAMES) {
-        if (vec) hipLaunchKernelGGL(seq_frames_kernel<4>, dim3(chunks, 2, d->n_pairs), dim3(256), 0, st, d->frames, d->pairs_dev, g, d->lq);
-        else hipLaunchKernelGGL(seq_frames_kernel<1>, dim3(chunks, 2, d->n_pairs), dim3(256), 0, st, d->frames, d->pairs_dev, g, d->lq);
-        REFID_LAUNCH_CHECK("seq_assemble: frames");
+        if (vec) hipLaunchKernelGGL(seq_frames_kernel<4>, dim3(chunks, n_frames, a.count), dim3(256), 0, st, a.frames, a.tab_dev, g, a.lq);
+        else hipLaunchKernelGGL(seq_frames_kernel<1>, dim3(chunks, n_frames, a.count), dim3(256), 0, st, a.frames, a.tab_dev, g, a.lq);
+        return seq_launched(a.who, "frames");
     }
     return 0;
 }
 
+extern "C" int refid_seq_assemble(const refid_seq_desc* d, int stages, void* stream) {
+    SEQ_CHECK(d, "seq_assemble: null descriptor");
+    const SeqArgs a{d->events, d->n_events, d->frames, d->n_frames, d->frame_stride, d->row_pitch, d->height, d->width, d->bgr,
+                    d->pairs_host, d->pairs_dev, d->n_pairs, d->out_h, d->out_w, d->scratch, d->lq, d->voxel,
+                    "seq_assemble", "pair", "n_pairs", /*check_right*/ true, /*limit_events*/ false};
+    long long max_rows = 0;
+    if (seq_check(a, &max_rows)) return -1;
+    const int bins = refid_assemble_bins(d->m, d->n, d->layout);               // sets the error text itself
+    if (bins < 0) return -1;
+    const SeqGeom g = seq_geom(a, bins, d->m, d->n, d->layout);
+    hipStream_t st = (hipStream_t)stream;
+    return seq_launch(a, g, max_rows, 2, stages, st, [&](bool vec, unsigned chunks) {
+        if (!(stages & REFID_ASSEMBLE_FINISH)) return 0;
+        if (vec) hipLaunchKernelGGL(seq_finish_kernel<4>, dim3(chunks, bins, a.count), dim3(256), 0, st, g, a.scratch, a.lq, a.voxel);
+        else hipLaunchKernelGGL(seq_finish_kernel<1>, dim3(chunks, bins, a.count), dim3(256), 0, st, g, a.scratch, a.lq, a.voxel);
+        return seq_launched(a.who, "finish");
+    });
+}
+
 extern "C" int refid_seq_assemble_single(const refid_seq_single_desc* d, int stages, void* stream) {
     SEQ_CHECK(d, "seq_assemble_single: null descriptor");
-    SEQ_CHECK(d->lq && d->voxel, "seq_assemble_single: null outputs (lq %p, voxel %p)", (void*)d->lq, (void*)d->voxel);
-    SEQ_CHECK(d->scratch, "seq_assemble_single: null scratch");
-    SEQ_CHECK(d->items_host && d->items_dev && d->n_items > 0 && d->n_items <= 65535,
-              "seq_assemble_single: n_items %d needs 1..65535 items and both item tables", d->n_items);
+    const SeqArgs a{d->events, d->n_events, d->frames, d->n_frames, d->frame_stride, d->row_pitch, d->height, d->width, d->bgr,
+                    d->items_host, d->items_dev, d->n_items, d->out_h, d->out_w, d->scratch, d->lq, d->voxel,
+                    "seq_assemble_single", "item", "n_items", /*check_right*/ false, /*limit_events*/ d->norm != 0};
+    long long max_rows = 0;
+    if (seq_check(a, &max_rows)) return -1;
     if (refid_single_bins(d->bins) < 0) return -1;                             // sets the error text itself
     SEQ_CHECK(d->bins <= 65535, "seq_assemble_single: bins %d > 65535", d->bins);
     SEQ_CHECK(!d->norm || (d->parts && ((uintptr_t)d->parts & 7) == 0),
               "seq_assemble_single: parts %p must be non-null and 8-byte aligned with norm", d->parts);
-    SEQ_CHECK(d->n_events >= 0 && (d->n_events == 0 || d->events) && ((uintptr_t)d->events & 15) == 0,
-              "seq_assemble_single: events must be %lld 16-byte aligned float32 rows", d->n_events);
-    SEQ_CHECK(d->frames && d->n_frames > 0 && d->height > 0 && d->width > 0,
-              "seq_assemble_single: no frames (n_frames %d, %dx%d)", d->n_frames, d->height, d->width);
-    SEQ_CHECK((long long)d->row_pitch >= 3ll * d->width &&
-              d->frame_stride >= (long long)(d->height - 1) * d->row_pitch + 3ll * d->width,
-              "seq_assemble_single: row_pitch %d / frame_stride %lld too small for %dx%d frames", d->row_pitch,
-              d->frame_stride, d->height, d->width);
-    SEQ_CHECK(d->out_h >= d->height, "seq_assemble_single: out_h %d < height %d", d->out_h, d->height);
-    SEQ_CHECK(d->out_w >= d->width, "seq_assemble_single: out_w %d < width %d", d->out_w, d->width);
-    SEQ_CHECK((long long)d->out_h * d->out_w <= (1ll << 30), "seq_assemble_single: out_h x out_w %dx%d too large", d->out_h,
-              d->out_w);
-    const long long plane = (long long)d->height * d->width, oplane = (long long)d->out_h * d->out_w;
-    const long long per_sample = d->bins * plane;                              // the UNPADDED sample: what the statistics see
+    const long long per_sample = (long long)d->bins * d->height * d->width;   // the UNPADDED sample: what the statistics see
     SEQ_CHECK(per_sample <= (1ll << 36), "seq_assemble_single: %d bins of %dx%d are too large", d->bins, d->height, d->width);
-    long long max_rows = 0;
-    for (int p = 0; p < d->n_items; ++p) {
-        const refid_seq_pair& s = d->items_host[p];
-        SEQ_CHECK(s.left >= 0 && s.left < d->n_frames, "seq_assemble_single: item %d: left %d outside the %d frames", p, s.left,
-                  d->n_frames);
-        SEQ_CHECK(s.row0 >= 0 && s.row0 <= s.row1, "seq_assemble_single: item %d: row0 %lld > row1 %lld (or negative)", p, s.row0,
-                  s.row1);
-        SEQ_CHECK(s.row1 <= d->n_events, "seq_assemble_single: item %d: row1 %lld > n_events %lld", p, s.row1, d->n_events);
-        // every event adds exactly 2^32 of magnitude to the scratch, so below 2^30 events the int64 sum S1 cannot overflow
-        SEQ_CHECK(!d->norm || s.row1 - s.row0 < (1ll << 30),
-                  "seq_assemble_single: item %d: voxel_norm supports fewer than 2^30 events per item (%lld)", p, s.row1 - s.row0);
-        if (s.row1 - s.row0 > max_rows) max_rows = s.row1 - s.row0;
-    }
-    SeqGeom g;
-    g.bins = d->bins; g.m = 1; g.n = 0; g.layout = LAYOUT_SINGLE;
-    g.h = d->height; g.w = d->width; g.oh = d->out_h; g.ow = d->out_w;
-    g.lq_chn = 3;
-    g.bgr = d->bgr; g.row_pitch = d->row_pitch; g.frame_stride = d->frame_stride;
+    const SeqGeom g = seq_geom(a, d->bins, 1, 0, LAYOUT_SINGLE);
     hipStream_t st = (hipStream_t)stream;
-    if (stages & REFID_ASSEMBLE_ZERO) {
-        hipError_t e = hipMemsetAsync(d->scratch, 0, sizeof(long long) * (size_t)d->n_items * per_sample, st);
-        SEQ_CHECK(e == hipSuccess, "seq_assemble_single: memset failed: %s", hipGetErrorString(e));
-    }
-    if ((stages & REFID_ASSEMBLE_SCATTER) && max_rows > 0) {
-        long long nbx = (max_rows + 255) / 256;
-        if (nbx > 2048) nbx = 2048;
-        hipLaunchKernelGGL(seq_scatter_kernel, dim3((unsigned)nbx, d->n_items), dim3(256), 0, st,
-                           reinterpret_cast<const float4*>(d->events), d->items_dev, g,
-                           reinterpret_cast<unsigned long long*>(d->scratch));
-        REFID_LAUNCH_CHECK("seq_assemble_single: scatter");
-    }
-    if ((stages & REFID_ASSEMBLE_STATS) && d->norm) {
-        if (int rc = voxel_norm_launch<long long>(d->scratch, nullptr, d->n_items, per_sample, d->parts, true, false, st,
-                                                  "seq_assemble_single: stats")) return rc;
-    }
-    // four-element stores: rows are a whole number of them, and every plane of both outputs starts 16-byte aligned
-    const bool vec = (g.ow & 3) == 0 && (((uintptr_t)d->lq | (uintptr_t)d->voxel) & 15) == 0;
-    const unsigned chunks = (unsigned)(((vec ? oplane / 4 : oplane) + 255) / 256);
-    if (stages & REFID_ASSEMBLE_FINISH) {
+    return seq_launch(a, g, max_rows, 1, stages, st, [&](bool vec, unsigned chunks) {
+        if ((stages & REFID_ASSEMBLE_STATS) && d->norm) {
+            if (int rc = voxel_norm_launch<long long>(a.scratch, nullptr, a.count, per_sample, d->parts, true, false, st,
+                                                      "seq_assemble_single: stats")) return rc;
+        }
+        if (!(stages & REFID_ASSEMBLE_FINISH)) return 0;
         const unsigned long long* parts = d->norm ? static_cast<const unsigned long long*>(d->parts) : nullptr;
         const int vn = (int)vn_chunks(per_sample);
-        if (vec) hipLaunchKernelGGL(seq_single_finish_kernel<4>, dim3(chunks, d->bins, d->n_items), dim3(256), 0, st, g, d->scratch, parts, vn, d->voxel);
-        else hipLaunchKernelGGL(seq_single_finish_kernel<1>, dim3(chunks, d->bins, d->n_items), dim3(256), 0, st, g, d->scratch, parts, vn, d->voxel);
-        REFID_LAUNCH_CHECK("seq_assemble_single: finish");
-    }
-    if (stages & REFID_ASSEMBLE_FRAMES) {
-        if (vec) hipLaunchKernelGGL(seq_frames_kernel<4>, dim3(chunks, 1, d->n_items), dim3(256), 0, st, d->frames, d->items_dev, g, d->lq);
-        else hipLaunchKernelGGL(seq_frames_kernel<1>, dim3(chunks, 1, d->n_items), dim3(256), 0, st, d->frames, d->items_dev, g, d->lq);
-        REFID_LAUNCH_CHECK("seq_assemble_single: frames");
-    }
-    return 0;
+        if (vec) hipLaunchKernelGGL(seq_single_finish_kernel<4>, dim3(chunks, d->bins, a.count), dim3(256), 0, st, g, a.scratch, parts, vn, a.voxel);
+        else hipLaunchKernelGGL(seq_single_finish_kernel<1>, dim3(chunks, d->bins, a.count), dim3(256), 0, st, g, a.scratch, parts, vn, a.voxel);
+        return seq_launched(a.who, "finish");
+    });
 }

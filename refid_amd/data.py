@@ -72,6 +72,47 @@ def draw_augmentation(rng, frame_h, frame_w, gt_size, use_hflip, use_rot):
     return top, left, hflip, vflip, rot90
 
 
+def layout_shapes(layout, count, bins, m, h, w):
+    """The shapes of (lq, voxel, gt) for ``count`` samples of (h, w) in a layout of both assemblers: 'blur', 'sharp'
+    (sliding bin pairs in voxel, bins-1 ground-truth frames) or 'single' (plain bins, one ground-truth frame)."""
+    if layout == "single":
+        return (count, 3, h, w), (count, bins, h, w), (count, 3, h, w)
+    lq = (count, 6 + 2 * (m - 1), h, w) if layout == "blur" else (count, 2, 3, h, w)
+    return lq, (count, bins - 1, 2, h, w), (count, bins - 1, 3, h, w)
+
+
+class GeometryCache(dict):
+    """What both assemblers keep per geometry: (count, h, w) -> {'scratch': int64 (count, bins, h, w), 'table_dev' /
+    'table_pin': the descriptor table on the device / in pinned memory, 'uploaded': the event behind the last copy out of
+    the pinned buffer, and with ``parts`` voxel_norm's 'parts'}."""
+
+    def __init__(self, device, bins, parts):
+        super().__init__()
+        self.device, self.bins, self.parts = device, bins, parts
+
+    def upload(self, key, table):
+        """The entry of ``key`` (made at its first use) with the ctypes array ``table`` copied to its device table: through
+        the pinned buffer and without blocking, once the previous copy has left that buffer."""
+        c = self.get(key)
+        if c is None:
+            count, h, w = key
+            c = {"scratch": torch.empty((count, self.bins, h, w), dtype=torch.int64, device=self.device),
+                 "table_dev": torch.empty(C.sizeof(table), dtype=torch.uint8, device=self.device),
+                 "table_pin": torch.empty(C.sizeof(table), dtype=torch.uint8).pin_memory(),
+                 "uploaded": None}
+            if self.parts:
+                from . import ops
+                c["parts"] = ops.voxel_norm_parts(count, self.bins * h * w, self.device)
+            self[key] = c
+        if c["uploaded"] is not None:
+            c["uploaded"].synchronize()
+        C.memmove(c["table_pin"].data_ptr(), C.addressof(table), C.sizeof(table))
+        c["table_dev"].copy_(c["table_pin"], non_blocking=True)
+        c["uploaded"] = torch.cuda.Event()
+        c["uploaded"].record()
+        return c
+
+
 _RAW_KEYS = ("frames", "events", "first_stamp", "last_stamp", "frame_hw", "origin", "top", "left", "hflip", "vflip", "rot90")
 
 
@@ -123,7 +164,7 @@ class DeviceBatchAssembler:
         if self.device.type != "cuda":
             raise RefidHipError("DeviceBatchAssembler: a GPU device is required (the HIP path has no CPU fallback)")
         self._last = None
-        self._cache = {}                      # (B, h, w) -> scratch, device table, pinned table, event of the last upload
+        self._cache = GeometryCache(self.device, self.bins, layout == "single" and self.norm_voxel)     # keys (B, h, w)
 
     def draw(self, rng, frame_h, frame_w):
         """``draw_augmentation`` with this assembler's gt_size / use_hflip / use_rot, as a dict for a raw sample."""
@@ -141,21 +182,6 @@ class DeviceBatchAssembler:
             ops.assemble_single(desc, stages)
         else:
             ops.assemble_batch(desc, stages & _lib.ASSEMBLE_ALL)
-
-    def _geometry(self, batch, h, w):
-        key = (batch, h, w)
-        c = self._cache.get(key)
-        if c is None:
-            nbytes = batch * C.sizeof(_lib.SampleDesc)
-            c = {"scratch": torch.empty((batch, self.bins, h, w), dtype=torch.int64, device=self.device),
-                 "table_dev": torch.empty(nbytes, dtype=torch.uint8, device=self.device),
-                 "table_pin": torch.empty(nbytes, dtype=torch.uint8).pin_memory(),
-                 "uploaded": None}
-            if self.layout == "single" and self.norm_voxel:
-                from . import ops
-                c["parts"] = ops.voxel_norm_parts(batch, self.bins * h * w, self.device)
-            self._cache[key] = c
-        return c
 
     @staticmethod
     def _samples(raw_batch):
@@ -210,41 +236,19 @@ class DeviceBatchAssembler:
             d.y0, d.x0, d.top, d.left = int(y0), int(x0), top, left
             d.hflip, d.vflip, d.rot90 = int(bool(s.get("hflip", 0))), int(bool(s.get("vflip", 0))), int(bool(s.get("rot90", 0)))
         h, w = crop
-        c = self._geometry(B, h, w)
-        if c["uploaded"] is not None:
-            c["uploaded"].synchronize()       # the previous batch's table copy has left the pinned buffer
-        C.memmove(c["table_pin"].data_ptr(), C.addressof(table), C.sizeof(table))
-        c["table_dev"].copy_(c["table_pin"], non_blocking=True)
-        c["uploaded"] = torch.cuda.Event()
-        c["uploaded"].record()
-        nb = self.bins
-        if self.layout == "single":
-            return self._finish_single(samples, table, keep, c, B, h, w, stages)
-        if self.layout == "blur":
-            lq = torch.empty((B, 6 + 2 * (self.m - 1), h, w), dtype=torch.float32, device=self.device)
-        else:
-            lq = torch.empty((B, 2, 3, h, w), dtype=torch.float32, device=self.device)
-        voxel = torch.empty((B, nb - 1, 2, h, w), dtype=torch.float32, device=self.device)
-        gt = torch.empty((B, nb - 1, 3, h, w), dtype=torch.float32, device=self.device)
-        desc = _lib.AssembleDesc()
-        desc.samples_host, desc.samples_dev = C.addressof(table), c["table_dev"].data_ptr()
-        desc.batch, desc.m, desc.n, desc.layout = B, self.m, self.n, self._layout
+        c = self._cache.upload((B, h, w), table)
+        lq, voxel, gt = (torch.empty(shape, dtype=torch.float32, device=self.device)
+                         for shape in layout_shapes(self.layout, B, self.bins, self.m, h, w))
+        single = self.layout == "single"
+        desc = _lib.SingleDesc() if single else _lib.AssembleDesc()
+        desc.samples_host, desc.samples_dev, desc.batch = C.addressof(table), c["table_dev"].data_ptr(), B
         desc.crop_h, desc.crop_w = h, w
         desc.scratch, desc.lq, desc.voxel, desc.gt = c["scratch"].data_ptr(), lq.data_ptr(), voxel.data_ptr(), gt.data_ptr()
-        return self._launch(desc, stages, samples, table, keep, lq, voxel, gt)
-
-    def _finish_single(self, samples, table, keep, c, B, h, w, stages):
-        lq, gt = (torch.empty((B, 3, h, w), dtype=torch.float32, device=self.device) for _ in range(2))
-        voxel = torch.empty((B, self.bins, h, w), dtype=torch.float32, device=self.device)
-        desc = _lib.SingleDesc()
-        desc.samples_host, desc.samples_dev = C.addressof(table), c["table_dev"].data_ptr()
-        desc.batch, desc.bins, desc.crop_h, desc.crop_w, desc.norm = B, self.bins, h, w, int(self.norm_voxel)
-        desc.scratch = c["scratch"].data_ptr()
-        desc.parts = c["parts"].data_ptr() if self.norm_voxel else None
-        desc.lq, desc.voxel, desc.gt = lq.data_ptr(), voxel.data_ptr(), gt.data_ptr()
-        return self._launch(desc, stages, samples, table, keep, lq, voxel, gt)
-
-    def _launch(self, desc, stages, samples, table, keep, lq, voxel, gt):
+        if single:
+            desc.bins, desc.norm = self.bins, int(self.norm_voxel)
+            desc.parts = c["parts"].data_ptr() if self.norm_voxel else None
+        else:
+            desc.m, desc.n, desc.layout = self.m, self.n, self._layout
         self._run(desc, stages)
         self._last = (desc, table, keep)      # rerun() launches again from these
         cur = torch.cuda.current_stream(self.device)

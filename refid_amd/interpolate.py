@@ -108,29 +108,26 @@ def png_filter_setting(args):
     return "none"
 
 
-def main(argv=None):
-    ap = argparse.ArgumentParser(prog="python -m refid_amd.interpolate", description=__doc__.split("\n\n")[0])
-    ap.add_argument("--opt", help="a test YAML: network_g, path.pretrain_network_g, datasets.test.num_*")
+def parser(prog, doc, opt_help, frames_help, stamps_help):
+    """The arguments both command lines take; the caller adds its own.  ``doc``: the module's docstring."""
+    ap = argparse.ArgumentParser(prog=prog, description=doc.split("\n\n")[0])
+    ap.add_argument("--opt", help=opt_help)
     ap.add_argument("--checkpoint", help="a .pth with the network's state dict (under 'params' or bare)")
-    ap.add_argument("--n", type=int, help="frames to interpolate between two key frames")
-    ap.add_argument("--m", type=int, help="frames to recover from each blurry key frame (blur layout)")
-    ap.add_argument("--layout", choices=("sharp", "blur"))
-    ap.add_argument("--frames", required=True, help="directory of PNG key frames, or a .npy stack (N, H, W, 3) uint8 RGB")
+    ap.add_argument("--frames", required=True, help=frames_help)
     ap.add_argument("--events", required=True, nargs="+", help="event .npz files (x, y, timestamp, polarity), in time order")
-    ap.add_argument("--stamps", required=True, help="key-frame timestamps, one per line ('start end' per line for blur)")
+    ap.add_argument("--stamps", required=True, help=stamps_help)
     ap.add_argument("--out", required=True, help="output directory")
-    ap.add_argument("--max-minibatch", type=int, default=2)
     ap.add_argument("--swap-xy", action="store_true", help="the HighREV files' swapped x / y columns")
     ap.add_argument("--niqe", metavar="PARAMS.npz", help="score every output frame with NIQE (niqe_pris_params.npz) -> niqe.txt")
     ap.add_argument("--png-filter", choices=("none", "adaptive"),
                     help="PNG row filters of the output: none (type 0 on every row) or adaptive (chosen per row on the GPU: "
                          "smaller files, cheaper to write); default: val.png_filter of --opt, else none")
-    args = ap.parse_args(argv)
+    return ap
 
-    import torch
+
+def load_inputs(args, noun):
+    """(NIQE model or None, frames, events, stamps) of a command line; ``noun``: what --stamps counts ('key frames')."""
     from . import sequence
-    from .archs import define_network
-    net_opt, ckpt, m, n, layout = settings(args)
     niqe_model = None
     if args.niqe:
         from .niqe import NiqeModel
@@ -139,14 +136,14 @@ def main(argv=None):
     events = sequence.load_event_npz(args.events, swap_xy=args.swap_xy)
     stamps = np.loadtxt(args.stamps, dtype=np.float64, ndmin=2)
     if stamps.shape[0] != frames.shape[0]:
-        raise SystemExit(f"--stamps: {stamps.shape[0]} lines for {frames.shape[0]} key frames")
-    if layout == "sharp":
-        windows = sequence.sharp_windows(stamps[:, 0])
-    elif stamps.shape[1] >= 2:
-        windows = sequence.exposure_windows(stamps[:, 0], stamps[:, 1])
-    else:
-        raise SystemExit("--stamps: the blur layout needs an exposure 'start end' per line")
-    pairs = sequence.make_pairs(events[:, 0], *windows)
+        raise SystemExit(f"--stamps: {stamps.shape[0]} lines for {frames.shape[0]} {noun}")
+    return niqe_model, frames, events, stamps
+
+
+def load_network(net_opt, ckpt):
+    """The network on the GPU with the checkpoint's weights ('params' or bare, with or without the ``module.`` prefix)."""
+    import torch
+    from .archs import define_network
     net = define_network(net_opt).to("cuda")
     if ckpt:
         state = torch.load(ckpt, map_location="cpu")
@@ -154,13 +151,43 @@ def main(argv=None):
         net.load_state_dict({(k[7:] if k.startswith("module.") else k): v for k, v in state.items()}, strict=True)
     else:
         print("warning: no checkpoint given: the network runs with its initial weights", file=sys.stderr)
-    names = [f"{k:06d}" for k in range(len(pairs))]
-    runner = sequence.SequenceInterpolator(net, m, n, layout, args.max_minibatch)
-    runner.run(frames, events, pairs, out_dir=args.out, names=names, niqe=niqe_model, png_filter=png_filter_setting(args))
-    print(f"{len(pairs)} pairs -> {args.out}")
+    return net
+
+
+def run_and_report(runner, args, frames, events, items, niqe_model, noun, file_name):
+    """Runs ``items`` (named by their index) into --out and, with --niqe, writes niqe.txt; ``file_name``: the format of an
+    output file's name from ``name`` and the frame ``f`` of the item."""
+    names = [f"{k:06d}" for k in range(len(items))]
+    runner.run(frames, events, items, out_dir=args.out, names=names, niqe=niqe_model, png_filter=png_filter_setting(args))
+    print(f"{len(items)} {noun} -> {args.out}")
     if niqe_model is not None:
-        mean = write_niqe(args.out, [f"{name}_{f:02d}.png" for name, f, _ in runner.niqe_scores], [s for _, _, s in runner.niqe_scores])
-        print(f"NIQE mean {mean:.6f} over {len(runner.niqe_scores)} frames -> {os.path.join(args.out, 'niqe.txt')}")
+        scores = runner.niqe_scores
+        mean = write_niqe(args.out, [file_name.format(name=name, f=f) for name, f, _ in scores], [s for _, _, s in scores])
+        print(f"NIQE mean {mean:.6f} over {len(scores)} frames -> {os.path.join(args.out, 'niqe.txt')}")
+
+
+def main(argv=None):
+    ap = parser("python -m refid_amd.interpolate", __doc__, "a test YAML: network_g, path.pretrain_network_g, datasets.test.num_*",
+                "directory of PNG key frames, or a .npy stack (N, H, W, 3) uint8 RGB",
+                "key-frame timestamps, one per line ('start end' per line for blur)")
+    ap.add_argument("--n", type=int, help="frames to interpolate between two key frames")
+    ap.add_argument("--m", type=int, help="frames to recover from each blurry key frame (blur layout)")
+    ap.add_argument("--layout", choices=("sharp", "blur"))
+    ap.add_argument("--max-minibatch", type=int, default=2)
+    args = ap.parse_args(argv)
+
+    from . import sequence
+    net_opt, ckpt, m, n, layout = settings(args)
+    niqe_model, frames, events, stamps = load_inputs(args, "key frames")
+    if layout == "sharp":
+        windows = sequence.sharp_windows(stamps[:, 0])
+    elif stamps.shape[1] >= 2:
+        windows = sequence.exposure_windows(stamps[:, 0], stamps[:, 1])
+    else:
+        raise SystemExit("--stamps: the blur layout needs an exposure 'start end' per line")
+    pairs = sequence.make_pairs(events[:, 0], *windows)
+    runner = sequence.SequenceInterpolator(load_network(net_opt, ckpt), m, n, layout, args.max_minibatch)
+    run_and_report(runner, args, frames, events, pairs, niqe_model, "pairs", "{name}_{f:02d}.png")
     return 0
 
 

@@ -19,6 +19,7 @@ import torch
 
 from . import _lib, metrics
 from ._lib import RefidHipError
+from .data import GeometryCache, layout_shapes
 
 Pair = collections.namedtuple("Pair", "left right row0 row1 first_stamp last_stamp")
 
@@ -232,7 +233,7 @@ class SequenceAssembler:
         if self.device.type != "cuda":
             raise RefidHipError("SequenceAssembler: a GPU device is required (the HIP path has no CPU fallback)")
         self.frames = self.events = None
-        self._cache = {}                      # (P, H, W) -> scratch, device table, pinned table, event of the last upload
+        self._cache = GeometryCache(self.device, self.bins, layout == "single" and self.norm_voxel)    # keys (P, H, W)
         self._last = None                     # descriptor and host table of the last call: lets a test or benchmark relaunch it
 
     def load(self, frames, events, bgr=False):
@@ -253,21 +254,6 @@ class SequenceAssembler:
         self.out_h, self.out_w = _round_up(self.height, self.multiple), _round_up(self.width, self.multiple)
         return self
 
-    def _geometry(self, count):
-        key = (count, self.height, self.width)
-        c = self._cache.get(key)
-        if c is None:
-            nbytes = count * C.sizeof(_lib.SeqPair)
-            c = {"scratch": torch.empty((count, self.bins, self.height, self.width), dtype=torch.int64, device=self.device),
-                 "table_dev": torch.empty(nbytes, dtype=torch.uint8, device=self.device),
-                 "table_pin": torch.empty(nbytes, dtype=torch.uint8).pin_memory(),
-                 "uploaded": None}
-            if self.layout == "single" and self.norm_voxel:
-                from . import ops
-                c["parts"] = ops.voxel_norm_parts(count, self.bins * self.height * self.width, self.device)
-            self._cache[key] = c
-        return c
-
     def assemble(self, pairs, stages=_lib.ASSEMBLE_ALL | _lib.ASSEMBLE_STATS):
         from . import ops
         if self.frames is None:
@@ -281,24 +267,11 @@ class SequenceAssembler:
             d = table[k]
             d.left, d.right, d.row0, d.row1 = int(p[0]), int(p[1]), int(p[2]), int(p[3])
             d.first_stamp, d.last_stamp = float(p[4]), float(p[5])
-        c = self._geometry(count)
-        if c["uploaded"] is not None:
-            c["uploaded"].synchronize()       # the previous table copy has left the pinned buffer
-        C.memmove(c["table_pin"].data_ptr(), C.addressof(table), C.sizeof(table))
-        c["table_dev"].copy_(c["table_pin"], non_blocking=True)
-        c["uploaded"] = torch.cuda.Event()
-        c["uploaded"].record()
+        c = self._cache.upload((count, self.height, self.width), table)
         h, w = self.out_h, self.out_w
         single = self.layout == "single"
-        if single:
-            lq = torch.empty((count, 3, h, w), dtype=torch.float32, device=self.device)
-            voxel = torch.empty((count, self.bins, h, w), dtype=torch.float32, device=self.device)
-        else:
-            if self.layout == "blur":
-                lq = torch.empty((count, 6 + 2 * (self.m - 1), h, w), dtype=torch.float32, device=self.device)
-            else:
-                lq = torch.empty((count, 2, 3, h, w), dtype=torch.float32, device=self.device)
-            voxel = torch.empty((count, self.bins - 1, 2, h, w), dtype=torch.float32, device=self.device)
+        lq, voxel = (torch.empty(shape, dtype=torch.float32, device=self.device)
+                     for shape in layout_shapes(self.layout, count, self.bins, self.m, h, w)[:2])
         desc = _lib.SeqSingleDesc() if single else _lib.SeqDesc()
         n_ev = int(self.events.shape[0])
         desc.events, desc.n_events = (self.events.data_ptr() if n_ev else None), n_ev

@@ -5,7 +5,8 @@ SequenceInterpolator on a tiny network; the sharp / test model family behind cre
 Everything the kernels compute is integer arithmetic or a single correctly rounded fp32 operation, so the assembly
 comparisons are BIT-identical.  Shapes are the smallest at which one thing can still go wrong: 40x56 (no padding, 2240
 elements: several blocks of four-element lanes), 37x50 -> 40x56 (padding on both sides, frame rows that are no multiple
-of four), 24x32 / 21x27 -> 24x32 for the blur layout with overlapping windows."""
+of four), 24x32 / 21x27 -> 24x32 for the blur layout with overlapping windows; 21x27 and 37x50 once more with multiple=1
+(rows that are no multiple of four: the one-element kernels of both pair layouts)."""
 import functools
 import logging
 import os
@@ -21,12 +22,16 @@ from oracle import refid_oracle as O
 pytestmark = pytest.mark.gpu
 
 STAMPS = [10.0, 20.0, 30.0, 31.0, 40.0]                   # five key frames
-CASES = {                                                 # name: (layout, m, n, H, W, bgr)
-    "sharp_40x56": ("sharp", 1, 3, 40, 56, True),
-    "sharp_37x50_bgr": ("sharp", 1, 3, 37, 50, True),
-    "sharp_37x50_rgb": ("sharp", 1, 3, 37, 50, False),
-    "blur_24x32": ("blur", 2, 1, 24, 32, False),
-    "blur_21x27": ("blur", 2, 1, 21, 27, True),
+CASES = {                                                 # name: (layout, m, n, H, W, bgr, multiple)
+    "sharp_40x56": ("sharp", 1, 3, 40, 56, True, 8),
+    "sharp_37x50_bgr": ("sharp", 1, 3, 37, 50, True, 8),
+    "sharp_37x50_rgb": ("sharp", 1, 3, 37, 50, False, 8),
+    "blur_24x32": ("blur", 2, 1, 24, 32, False, 8),
+    "blur_21x27": ("blur", 2, 1, 21, 27, True, 8),
+    # multiple=1: no padding and rows that are no multiple of four -> the one-element kernels (seq_finish_kernel<1>,
+    # seq_frames_kernel<1>) of both pair layouts, BGR and RGB, with lq's event channels (m = 2)
+    "blur_21x27_x1": ("blur", 2, 1, 21, 27, True, 1),
+    "sharp_37x50_rgb_x1": ("sharp", 1, 3, 37, 50, False, 1),
 }
 
 
@@ -69,15 +74,15 @@ def _pairs(ev, layout, stamps):
 
 @functools.lru_cache(maxsize=None)
 def _case(name, stamps):
-    layout, m, n, H, W, bgr = CASES[name]
+    layout, m, n, H, W, bgr, multiple = CASES[name]
     frames, ev = _sequence(H, W, seed=len(name) + H)
     pairs = _pairs(ev, layout, stamps)
     rows = [(p.row0, p.row1) for p in pairs]
     assert any(r1 == r0 for r0, r1 in rows) and any(r1 - r0 == 1 for r0, r1 in rows)     # an empty and a one-event window
-    lq, voxel = S.assemble_pairs(frames, ev, pairs, m, n, layout, multiple=8, bgr=bgr)
+    lq, voxel = S.assemble_pairs(frames, ev, pairs, m, n, layout, multiple=multiple, bgr=bgr)
     lq.setflags(write=False)
     voxel.setflags(write=False)
-    return dict(frames=frames, events=ev, pairs=pairs, lq=lq, voxel=voxel, layout=layout, m=m, n=n, bgr=bgr)
+    return dict(frames=frames, events=ev, pairs=pairs, lq=lq, voxel=voxel, layout=layout, m=m, n=n, bgr=bgr, multiple=multiple)
 
 
 def _same_bits(got, want, what):
@@ -90,7 +95,7 @@ def _same_bits(got, want, what):
 
 def _assembler(c):
     from refid_amd.sequence import SequenceAssembler
-    return SequenceAssembler(c["m"], c["n"], c["layout"], multiple=8).load(c["frames"], c["events"], bgr=c["bgr"])
+    return SequenceAssembler(c["m"], c["n"], c["layout"], multiple=c["multiple"]).load(c["frames"], c["events"], bgr=c["bgr"])
 
 
 @pytest.mark.parametrize("stamps", ["events", "bounds"])
@@ -187,6 +192,12 @@ def test_rejected_arguments_name_the_field_and_launch_nothing():
     rejected(desc, "lq", None, r"null outputs")
     rejected(desc, "voxel", None, r"null outputs")
     rejected(desc, "n_pairs", 0, r"n_pairs 0")
+    rejected(desc, "scratch", None, r"null scratch")
+    rejected(desc, "pairs_dev", None, r"both pair tables")
+    rejected(desc, "events", desc.events + 4, r"16-byte aligned")
+    rejected(desc, "n_frames", 0, r"no frames \(n_frames 0")
+    rejected(desc, "row_pitch", desc.row_pitch - 1, r"row_pitch 149 / frame_stride")
+    rejected(table[2], "row0", -1, r"pair 2: row0 -1 > row1")
     torch.cuda.synchronize()
     assert bool((out["lq"] == 7.0).all()) and bool((out["voxel"] == 7.0).all())         # nothing was launched
     ops.seq_assemble(desc)                                                             # the untouched descriptor still runs
