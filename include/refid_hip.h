@@ -818,6 +818,46 @@ typedef struct refid_png_filter_desc {
 } refid_png_filter_desc;
 int refid_png_filter(const refid_png_filter_desc* d, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Huffman-only deflate of filtered rows (csrc/png_deflate.hip): the last stage of the PNG writer.  src: n_streams runs of
+ * stream_bytes bytes back to back (per frame the height * (1 + 3*width) bytes refid_png_filter writes); stream s becomes
+ * ONE zlib stream at out + s*out_pitch, its length in lens[s]:
+ *   78 01 | one byte-aligned segment per block of block_bytes input bytes (the last may be shorter) | 01 00 00 FF FF (a final
+ *   empty stored block) | Adler-32 of the stream's input, big-endian.
+ * A DYNAMIC segment (RFC 1951 3.2.7): BFINAL 0, BTYPE 10; HLIT 0 (257 literal/length codes), HDIST 0 (one distance code),
+ * HCLEN 15; the 19 code-length-code lengths in the RFC's order, 0 for the symbols 16 17 18 and 4 for 0..15 (a complete code
+ * without run lengths: the 4-bit code of a length is the length); 257 lengths and one distance length 0 as those codes; the
+ * block's bytes as canonical Huffman codes; the end-of-block code; an empty stored block 000, padding to a byte, 00 00 FF FF.
+ * A STORED segment: 00, LEN, ~LEN, the bytes; used exactly when the dynamic one would take >= len + 5 bytes.
+ * The code of a block: frequencies of its bytes and 1 for end-of-block; the occurring symbols sorted by (frequency, symbol);
+ * two-queue merge, the leaf queue winning a tie; depths from the root down, each one more than its parent's clamped depth,
+ * a depth above 15 clamped and counted (merged nodes too); zlib's gen_bitlen repair on the counts per length; the counts
+ * dealt out longest first in the sorted order; canonical code values.  tests/deflate_ref.py restates all of it in numpy.
+ * Integers only; the only atomics are integer adds / ors in LDS, whose result does not depend on the order: bytes
+ * [0, lens[s]) of a stream do not depend on n_streams, on the stream's position in the call, on the alignment of src or
+ * out, or on the run.  Bytes [lens[s], out_pitch) are left as they were.  Nothing outside [out, out + n_streams*out_pitch),
+ * lens[0 .. n_streams) and the first refid_png_deflate_work_bytes(...) bytes of work is written.
+ * Three launches on `stream` that meet only at the kernel boundaries -- per block: histogram, Adler sums, code, segment
+ * length; per stream: segment offsets, 78 01, terminator, Adler-32, lens; per block: the bits -- nothing is allocated,
+ * nothing synchronises.  out_pitch >= refid_png_deflate_bound(stream_bytes, block_bytes) = 2 + stream_bytes + 5*blocks + 9,
+ * which must fit int32; block_bytes 1 .. 65535 (REFID_PNG_DEFLATE_BLOCK: the measured default); lens and work aligned to 4
+ * bytes.  A bad argument returns 1 with a message (refid_last_error) and launches nothing; the two size functions return 0
+ * for sizes the entry point would turn down.
+ * ---------------------------------------------------------------------------------- */
+#define REFID_PNG_DEFLATE_BLOCK 32768
+#define REFID_PNG_DEFLATE_MAX_BLOCK 65535
+#define REFID_PNG_DEFLATE_RECORD 1088           /* scratch bytes per block: segment length / kind, Adler sums, offset, 257 codes */
+typedef struct refid_png_deflate_desc {
+    const uint8_t* src;                         /* device: n_streams * stream_bytes bytes                          */
+    uint8_t* out;                               /* device: n_streams * out_pitch bytes                             */
+    uint32_t* lens;                             /* device: [n_streams], the streams' lengths                       */
+    uint32_t* work;                             /* device: refid_png_deflate_work_bytes(...) bytes of scratch      */
+    int32_t n_streams, stream_bytes, block_bytes, out_pitch;
+} refid_png_deflate_desc;
+size_t refid_png_deflate_bound(int32_t stream_bytes, int32_t block_bytes);
+size_t refid_png_deflate_work_bytes(int32_t n_streams, int32_t stream_bytes, int32_t block_bytes);
+int refid_png_deflate(const refid_png_deflate_desc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -163,6 +163,14 @@ class PngFilterDesc(C.Structure):
     ]
 
 
+class PngDeflateDesc(C.Structure):
+    """refid_png_deflate_desc: n_streams runs of filtered rows -> one zlib stream each (Huffman codes per block)."""
+    _fields_ = [
+        ("src", C.c_void_p), ("out", C.c_void_p), ("lens", C.c_void_p), ("work", C.c_void_p),
+        ("n_streams", C.c_int32), ("stream_bytes", C.c_int32), ("block_bytes", C.c_int32), ("out_pitch", C.c_int32),
+    ]
+
+
 LAYOUT_BLUR, LAYOUT_SHARP = 0, 1                # == REFID_LAYOUT_* in include/refid_hip.h
 ASSEMBLE_ZERO, ASSEMBLE_SCATTER, ASSEMBLE_FINISH, ASSEMBLE_FRAMES, ASSEMBLE_ALL = 1, 2, 4, 8, 15
 ASSEMBLE_STATS = 16                              # refid_assemble_single only: voxel_norm's statistics, between scatter and finish
@@ -172,6 +180,9 @@ NIQE_BGR = 1             # == REFID_NIQE_BGR in include/refid_hip.h
 PNG_MAX_ROW_BYTES = 32760    # == REFID_PNG_MAX_ROW_BYTES in include/refid_hip.h
 PNG_FILTER_ADAPTIVE = 5      # == REFID_PNG_FILTER_ADAPTIVE in include/refid_hip.h
 PNG_FILTER_MAX_WIDTH = 11184810    # == REFID_PNG_FILTER_MAX_WIDTH in include/refid_hip.h
+PNG_DEFLATE_BLOCK = 32768          # == REFID_PNG_DEFLATE_BLOCK in include/refid_hip.h
+PNG_DEFLATE_MAX_BLOCK = 65535      # == REFID_PNG_DEFLATE_MAX_BLOCK in include/refid_hip.h
+PNG_DEFLATE_RECORD = 1088          # == REFID_PNG_DEFLATE_RECORD in include/refid_hip.h
 ABI_VERSION = 9          # == REFID_ABI_VERSION in include/refid_hip.h
 _lib = None
 
@@ -301,6 +312,11 @@ def _bind_extra(L):
     L.refid_niqe_moments.argtypes = [vp, i, i, i, i, i, vp, vp, vp, vp, vp, vp, vp]
     L.refid_png_unfilter.argtypes = [C.POINTER(PngUnfilterDesc), vp]
     L.refid_png_filter.argtypes = [C.POINTER(PngFilterDesc), vp]
+    L.refid_png_deflate_bound.argtypes = [C.c_int32, C.c_int32]
+    L.refid_png_deflate_bound.restype = C.c_size_t
+    L.refid_png_deflate_work_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    L.refid_png_deflate_work_bytes.restype = C.c_size_t
+    L.refid_png_deflate.argtypes = [C.POINTER(PngDeflateDesc), vp]
 
 
 def check(rc, what):

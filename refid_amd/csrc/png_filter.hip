@@ -1,5 +1,5 @@
 // PNG forward filtering (PNG specification 9.2) of resident uint8 RGB frames, with libpng's adaptive heuristic: the half of
-// an encoder that is a streaming pass over bytes.  Deflate stays on the host (refid_amd/png.py: encode_png_rows).  The
+// an encoder that is a streaming pass over bytes.  Deflate is the host's (refid_amd/png.py: encode_png_rows) or png_deflate.hip's.  The
 // mirror image of png.hip: forward filtering reads original pixels only -- a = the byte 3 to the left, b = the byte above,
 // c = the byte above-left, 0 outside the frame -- so no row waits for another.
 //

@@ -12,7 +12,7 @@ reference's ``niqe_pris_params.npz``) also scores every output frame with NIQE: 
 line per frame and a last ``mean`` line over the finite scores, which is printed too."""
 import sys
 
-from .interpolate import load_frames, load_frames_resident, png_filter_setting, write_niqe  # noqa: F401  (for other callers)
+from .interpolate import load_frames, load_frames_resident, png_deflate_setting, png_filter_setting, write_niqe  # noqa: F401  (for other callers)
 from .interpolate import load_inputs, load_network, parser, run_and_report
 
 

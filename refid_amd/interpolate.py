@@ -108,6 +108,22 @@ def png_filter_setting(args):
     return "none"
 
 
+def png_deflate_setting(args):
+    """``--png-deflate``, else ``val.png_deflate`` of ``--opt``, else 'host'; as ``png_filter_setting``."""
+    from ._lib import RefidHipError
+    from .validation import check_png_deflate
+    if args.png_deflate is not None:
+        return args.png_deflate
+    if args.opt:
+        from .options import parse
+        val = parse(args.opt, is_train=False).get("val") or {}
+        try:
+            return check_png_deflate(val.get("png_deflate"), "--opt: val.png_deflate")
+        except RefidHipError as ex:
+            raise SystemExit(str(ex))
+    return "host"
+
+
 def parser(prog, doc, opt_help, frames_help, stamps_help):
     """The arguments both command lines take; the caller adds its own.  ``doc``: the module's docstring."""
     ap = argparse.ArgumentParser(prog=prog, description=doc.split("\n\n")[0])
@@ -122,6 +138,9 @@ def parser(prog, doc, opt_help, frames_help, stamps_help):
     ap.add_argument("--png-filter", choices=("none", "adaptive"),
                     help="PNG row filters of the output: none (type 0 on every row) or adaptive (chosen per row on the GPU: "
                          "smaller files, cheaper to write); default: val.png_filter of --opt, else none")
+    ap.add_argument("--png-deflate", choices=("host", "device"),
+                    help="where the output PNGs are deflated: host (zlib in the writer threads) or device (Huffman codes per "
+                         "block on the GPU; the threads only write); default: val.png_deflate of --opt, else host")
     return ap
 
 
@@ -158,7 +177,8 @@ def run_and_report(runner, args, frames, events, items, niqe_model, noun, file_n
     """Runs ``items`` (named by their index) into --out and, with --niqe, writes niqe.txt; ``file_name``: the format of an
     output file's name from ``name`` and the frame ``f`` of the item."""
     names = [f"{k:06d}" for k in range(len(items))]
-    runner.run(frames, events, items, out_dir=args.out, names=names, niqe=niqe_model, png_filter=png_filter_setting(args))
+    runner.run(frames, events, items, out_dir=args.out, names=names, niqe=niqe_model, png_filter=png_filter_setting(args),
+               png_deflate=png_deflate_setting(args))
     print(f"{len(items)} {noun} -> {args.out}")
     if niqe_model is not None:
         scores = runner.niqe_scores

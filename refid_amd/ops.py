@@ -1126,3 +1126,37 @@ def png_filter(frames_u8, mode="adaptive", out=None, costs=None):
                               n_frames=n, height=h, width=w, mode=code)
     check(lib().refid_png_filter(C.byref(desc), _stream()), "refid_png_filter")
     return out.view(n, h, pitch)
+
+
+def png_deflate(rows, block_bytes=None, out=None):
+    """refid_png_deflate (csrc/png_deflate.hip) on the current stream: uint8 CUDA ``rows`` (N, H, 1 + 3W) -- what
+    ``png_filter`` returns -- or (N, bytes) -> (out uint8 (N, pitch), lens int32 (N,)): row n of ``out`` begins with the
+    zlib stream of ``rows[n]``, ``lens[n]`` bytes long (Huffman codes only, one code per block of ``block_bytes`` input
+    bytes, 1 .. 65535; default ``_lib.PNG_DEFLATE_BLOCK``); what ``png.wrap_zlib_stream`` puts into an IDAT chunk.  The
+    bytes behind a stream are left as they were.  ``out``: a contiguous uint8 (N, pitch) tensor to write into (any
+    alignment), pitch >= ``refid_png_deflate_bound``; without it the pitch is that bound.  Does not synchronise."""
+    r = rows
+    if not isinstance(r, torch.Tensor) or not r.is_cuda or r.dtype != torch.uint8 or r.dim() not in (2, 3) or r.numel() == 0 or \
+            not r.is_contiguous():
+        raise _lib.RefidHipError("png_deflate: a non-empty contiguous uint8 CUDA tensor (N, H, 1 + 3W) or (N, bytes) is required, got "
+                                 + (f"{r.dtype} {tuple(r.shape)} on {r.device}" if isinstance(r, torch.Tensor) else type(r).__name__))
+    block = _lib.PNG_DEFLATE_BLOCK if block_bytes is None else block_bytes
+    if type(block) is not int or not 1 <= block <= _lib.PNG_DEFLATE_MAX_BLOCK:
+        raise _lib.RefidHipError(f"png_deflate: block_bytes {block_bytes!r} is not an integer 1 .. {_lib.PNG_DEFLATE_MAX_BLOCK}")
+    n, size = int(r.shape[0]), r.numel() // int(r.shape[0])
+    L = lib()
+    bound = L.refid_png_deflate_bound(size, block) if size < 2 ** 31 else 0
+    work_bytes = L.refid_png_deflate_work_bytes(n, size, block) if bound else 0
+    if not work_bytes:
+        raise _lib.RefidHipError(f"png_deflate: {n} streams of {size} bytes in blocks of {block} exceed the grid or a 31-bit stream")
+    if out is None:
+        out = torch.empty((n, bound), dtype=torch.uint8, device=r.device)
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != r.device or out.dim() != 2 or \
+            out.shape[0] != n or out.shape[1] < bound or out.shape[1] >= 2 ** 31 or not out.is_contiguous():
+        raise _lib.RefidHipError(f"png_deflate: out must be a contiguous uint8 ({n}, >= {bound}) tensor on {r.device}")
+    lens = torch.empty((n,), dtype=torch.int32, device=r.device)
+    work = torch.empty((work_bytes // 4,), dtype=torch.int32, device=r.device)
+    desc = _lib.PngDeflateDesc(src=r.data_ptr(), out=out.data_ptr(), lens=lens.data_ptr(), work=work.data_ptr(), n_streams=n,
+                               stream_bytes=size, block_bytes=block, out_pitch=int(out.shape[1]))
+    check(L.refid_png_deflate(C.byref(desc), _stream()), "refid_png_deflate")
+    return out, lens

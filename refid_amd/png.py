@@ -4,7 +4,9 @@ the host; ``read_filtered`` stops after inflate and leaves the per-row filters t
 
 8-bit RGB (H, W, 3) or 8-bit grey (H, W); signature, IHDR, one IDAT, IEND; filter type 0 on every row; one
 ``zlib.compress``.  Level 1 by default: validation writes thousands of 720p frames and the encoder runs on the host.
-``encode_png_rows`` / ``write_png_rows`` take rows the GPU has already filtered (``ops.png_filter``, csrc/png_filter.hip)."""
+``encode_png_rows`` / ``write_png_rows`` take rows the GPU has already filtered (``ops.png_filter``, csrc/png_filter.hip);
+``wrap_zlib_stream`` / ``write_png_stream`` take the finished zlib stream of such rows (``ops.png_deflate``,
+csrc/png_deflate.hip) and only add the chunk framing and the CRC."""
 import os
 import struct
 import zlib
@@ -61,6 +63,30 @@ def encode_png_rows(rows, width, height, level=1, strategy=zlib.Z_HUFFMAN_ONLY):
 def write_png_rows(path, rows, width, height, level=1, strategy=zlib.Z_HUFFMAN_ONLY):
     """As ``write_png``, for rows that are already filtered (``encode_png_rows``)."""
     data = encode_png_rows(rows, width, height, level, strategy)
+    parent = os.path.dirname(os.path.abspath(path))
+    os.makedirs(parent, exist_ok=True)
+    with open(path, "wb") as f:
+        f.write(data)
+    return path
+
+
+def wrap_zlib_stream(stream_bytes, width, height):
+    """The PNG (8-bit RGB) whose image data is the finished zlib stream ``stream_bytes`` (bytes, or a uint8 array) of
+    ``height`` filtered rows of 1 + 3*``width`` bytes -- a stream of ``ops.png_deflate`` (csrc/png_deflate.hip), cut to its
+    length.  Signature, IHDR, one IDAT, IEND; the IDAT's CRC-32 is taken here, on the host, over the compressed bytes.
+    The stream is not inflated: what it holds is the caller's business."""
+    data = stream_bytes.tobytes() if isinstance(stream_bytes, np.ndarray) else bytes(stream_bytes)
+    width, height = int(width), int(height)
+    if width < 1 or height < 1 or len(data) < 2 + 5 + 4 or data[:2] != b"\x78\x01":
+        raise ValueError(f"write_png_stream: a zlib stream (78 01 ...) for {height} rows of 1 + 3*{width} bytes expected, got "
+                         f"{len(data)} bytes starting {data[:2].hex()}")
+    ihdr = struct.pack(">IIBBBBB", width, height, 8, 2, 0, 0, 0)
+    return SIGNATURE + _chunk(b"IHDR", ihdr) + _chunk(b"IDAT", data) + _chunk(b"IEND", b"")
+
+
+def write_png_stream(path, stream_bytes, width, height):
+    """As ``write_png``, for image data that is already a zlib stream (``wrap_zlib_stream``)."""
+    data = wrap_zlib_stream(stream_bytes, width, height)
     parent = os.path.dirname(os.path.abspath(path))
     os.makedirs(parent, exist_ok=True)
     with open(path, "wb") as f:

@@ -309,11 +309,13 @@ class _SequenceRunner:
 
     niqe_scores = None
 
-    def run(self, frames, events, pairs, out_dir=None, names=None, keep=False, bgr=False, niqe=None, png_filter="none"):
+    def run(self, frames, events, pairs, out_dir=None, names=None, keep=False, bgr=False, niqe=None, png_filter="none",
+            png_deflate="host"):
         from . import niqe as niqe_mod
-        from .validation import FrameWriter, check_png_filter
+        from .validation import FrameWriter, check_png_deflate, check_png_filter
         what = type(self).__name__
         png_filter = check_png_filter(png_filter, f"{what}.run: png_filter")
+        png_deflate = check_png_deflate(png_deflate, f"{what}.run: png_deflate")
         pairs = list(pairs)
         if not pairs:
             raise RefidHipError(f"{what}.run: no pairs")
@@ -339,7 +341,7 @@ class _SequenceRunner:
                 return asm.assemble(chunks[k])
 
         was_training = self.net.training
-        writer = FrameWriter(self.device, png_filter=png_filter) if out_dir is not None else None
+        writer = FrameWriter(self.device, png_filter=png_filter, png_deflate=png_deflate) if out_dir is not None else None
         kept = []
         self.net.eval()
         try:
@@ -395,13 +397,15 @@ class SequenceInterpolator(_SequenceRunner):
         self.assembler = SequenceAssembler(m, n, layout, multiple=1 << int(net.num_encoders), device=self.device)
         self.stream = torch.cuda.Stream(device=self.device)
 
-    def run(self, frames, events, pairs, out_dir=None, names=None, keep=False, bgr=False, niqe=None, png_filter="none"):
+    def run(self, frames, events, pairs, out_dir=None, names=None, keep=False, bgr=False, niqe=None, png_filter="none",
+            png_deflate="host"):
         """``frames`` uint8 (N, H, W, 3), ``events`` float32 (E, 4), ``pairs`` from ``make_pairs``.  With ``out_dir`` frame f
         of pair k goes to ``{out_dir}/{names[k]}_{f:02d}.png`` (default name: the left key frame's index, six digits, as
         the validation dumps are named).  ``keep=True`` returns the uint8 frames (P, T, H, W, 3) on the host, else None.
         ``niqe``: a ``NiqeModel``; ``niqe_scores`` then holds (name, f, score) per output frame.  ``png_filter``: 'none' or
-        'adaptive' (``validation.FrameWriter``): the same pixels in smaller files."""
-        return super().run(frames, events, pairs, out_dir, names, keep, bgr, niqe, png_filter)
+        'adaptive' (``validation.FrameWriter``): the same pixels in smaller files.  ``png_deflate``: 'host' or 'device'
+        (the PNGs' zlib streams come from the GPU, ``ops.png_deflate``): the same pixels again."""
+        return super().run(frames, events, pairs, out_dir, names, keep, bgr, niqe, png_filter, png_deflate)
 
     def _forward(self, batch):
         return self.net(x=batch["lq"], event=batch["voxel"])
@@ -435,13 +439,14 @@ class SequenceDeblurrer(_SequenceRunner):
                                            multiple=int(net.size_multiple), device=self.device)
         self.stream = torch.cuda.Stream(device=self.device)
 
-    def run(self, frames, events, items, out_dir=None, names=None, keep=False, bgr=False, niqe=None, png_filter="none"):
+    def run(self, frames, events, items, out_dir=None, names=None, keep=False, bgr=False, niqe=None, png_filter="none",
+            png_deflate="host"):
         """``frames`` uint8 (N, H, W, 3), ``events`` float32 (E, 4), ``items`` from ``make_pairs(t, *frame_windows(...))``.
         With ``out_dir`` item k goes to ``{out_dir}/{names[k]}.png`` (default name: the frame index, six digits).
         ``keep=True`` returns the uint8 frames (P, H, W, 3) on the host, else None.
         ``niqe``: a ``NiqeModel``; ``niqe_scores`` then holds (name, 0, score) per output frame.  ``png_filter``: as for
         ``SequenceInterpolator.run``."""
-        return super().run(frames, events, items, out_dir, names, keep, bgr, niqe, png_filter)
+        return super().run(frames, events, items, out_dir, names, keep, bgr, niqe, png_filter, png_deflate)
 
     def _forward(self, batch):
         if self.crop_size is None:

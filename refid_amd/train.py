@@ -462,9 +462,10 @@ class TwoImageEventRecurrentRestorationModel:
         copied out and written as PNGs behind the next item's forward pass (validation.FrameWriter).  Every sample of an
         item is evaluated (`seq` / `origin_index` entry i names sample i; the reference looks at sample 0 only, the same
         thing at its batch_size 1).  `rgb2bgr` is accepted and unused, as in the reference's loop."""
-        from .validation import FrameWriter, check_png_filter
+        from .validation import FrameWriter, check_png_deflate, check_png_filter
         val = self.opt.get("val", {})
         png_filter = check_png_filter(val.get("png_filter"), "val.png_filter")       # this project's key: absent = none
+        png_deflate = check_png_deflate(val.get("png_deflate"), "val.png_deflate")   # this project's key: absent = host
         dataset_name = self.opt.get("name")
         save_gt = val.get("save_gt", False)
         self.m = self.opt["datasets"][self.VAL_DATASET].get("num_end_interpolation")
@@ -472,7 +473,7 @@ class TwoImageEventRecurrentRestorationModel:
         book = self._val_book(val, use_image)
         types = book.metric_types()
         was_training = self.net_g.training
-        writer = FrameWriter(self.device, png_filter=png_filter) if save_img else None
+        writer = FrameWriter(self.device, png_filter=png_filter, png_deflate=png_deflate) if save_img else None
         seen = 0                                                # samples before this item (the reference's `cnt`)
         try:
             for val_data in dataloader:

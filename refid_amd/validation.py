@@ -8,16 +8,23 @@ is reused only after every job that reads it has finished.  No fp32 frame leaves
 ``png_filter='adaptive'``: the frames are first filtered on the device (``ops.png_filter``, csrc/png_filter.hip: per row the
 PNG filter type libpng's heuristic picks) on the current stream; the filtered rows -- one byte per row more than the
 frames -- take the frames' place in the pinned buffers and the workers only deflate them (``png.write_png_rows``).  The
-files hold the same pixels; they are smaller and cheaper to deflate on anything but flat frames."""
+files hold the same pixels; they are smaller and cheaper to deflate on anything but flat frames.
+
+``png_deflate='device'``: the rows (filter 0 with ``png_filter='none'``, adaptive otherwise) are also deflated on the device
+(``ops.png_deflate``, csrc/png_deflate.hip: Huffman codes per block, no matches) on the current stream; the finished zlib
+streams and their lengths take the rows' place in the pinned buffers -- the whole pitch is copied, so nothing waits for a
+length -- and the workers only take the CRC and write the file (``png.write_png_stream``).  The files hold the same
+pixels as the host route's; their bytes differ (another block structure)."""
 import threading
 from concurrent.futures import ThreadPoolExecutor
 
 import torch
 
 from . import _lib
-from .png import write_png, write_png_rows
+from .png import write_png, write_png_rows, write_png_stream
 
 PNG_FILTERS = ("none", "adaptive")
+PNG_DEFLATES = ("host", "device")
 
 
 def check_png_filter(value, where="png_filter"):
@@ -28,13 +35,22 @@ def check_png_filter(value, where="png_filter"):
     return value
 
 
+def check_png_deflate(value, where="png_deflate"):
+    """'host' (or None: an absent key) / 'device'; anything else raises, naming ``where``."""
+    value = "host" if value is None else value
+    if value not in PNG_DEFLATES:
+        raise _lib.RefidHipError(f"{where}: {value!r} is not one of {', '.join(PNG_DEFLATES)}")
+    return value
+
+
 class FrameWriter:
     WORKERS = 4              # encoding is zlib (releases the GIL); never sized from the machine's core count
     QUEUE = 32               # jobs submitted and not finished; `dump` blocks beyond that
 
-    def __init__(self, device, level=1, png_filter="none"):
+    def __init__(self, device, level=1, png_filter="none", png_deflate="host"):
         self.level = level
         self.png_filter = check_png_filter(png_filter, "FrameWriter: png_filter")
+        self.png_deflate = check_png_deflate(png_deflate, "FrameWriter: png_deflate")
         self.stream = torch.cuda.Stream(device)
         self.slots = [dict(buf=None, jobs=[]), dict(buf=None, jobs=[])]
         self.turn = 0
@@ -46,26 +62,40 @@ class FrameWriter:
         slot = self.slots[self.turn]
         self.turn ^= 1
         self._drain(slot)                                   # its previous item is written: the buffer may be overwritten
-        # (tensor, paths, width): the width marks rows the device has filtered, launched here on the current stream
-        batches = [self._filtered(t, paths) if self.png_filter == "adaptive" else (t, paths, None) for t, paths in batches]
-        total = sum(t.numel() for t, _, _ in batches)
+        # (tensor, paths, width, (lens, height)): the width marks rows the device has filtered, the last entry zlib streams it
+        # has deflated as well; both launched here on the current stream
+        if self.png_deflate == "device":
+            batches = [self._deflated(t, paths, self.png_filter) for t, paths in batches]
+        else:
+            batches = [self._filtered(t, paths) if self.png_filter == "adaptive" else (t, paths, None, None) for t, paths in batches]
+        total = sum(t.numel() + (0 if deflated is None else 4 * deflated[0].numel() + 4) for t, _, _, deflated in batches)
         if slot["buf"] is None or slot["buf"].numel() < total:
             slot["buf"] = torch.empty(total, dtype=torch.uint8).pin_memory()
         self.stream.wait_stream(torch.cuda.current_stream())
         views, off = [], 0
         with torch.cuda.stream(self.stream):
-            for t, paths, width in batches:
+            for t, paths, width, deflated in batches:
                 dst = slot["buf"][off:off + t.numel()].view(t.shape)
                 dst.copy_(t, non_blocking=True)
                 t.record_stream(self.stream)                # the allocator must not hand t's block out before the copy ran
-                views.append((dst.numpy(), paths, width))
                 off += t.numel()
+                sizes = None
+                if deflated is not None:                    # the streams' lengths, behind them at the next multiple of 4
+                    lens, height = deflated
+                    off = (off + 3) & ~3
+                    pinned = slot["buf"][off:off + 4 * lens.numel()].view(torch.int32)
+                    pinned.copy_(lens, non_blocking=True)
+                    lens.record_stream(self.stream)
+                    off += 4 * lens.numel()
+                    sizes = (pinned.numpy(), height)
+                views.append((dst.numpy(), paths, width, sizes))
             done = torch.cuda.Event()
             done.record(self.stream)
-        for frames, paths, width in views:
+        for frames, paths, width, sizes in views:
             for i, path in enumerate(paths):
                 self.room.acquire()
-                slot["jobs"].append(self.pool.submit(self._job, done, frames[i], path, width))
+                stream = None if sizes is None else (sizes[0][i:i + 1], sizes[1])
+                slot["jobs"].append(self.pool.submit(self._job, done, frames[i], path, width, stream))
 
     @staticmethod
     def _filtered(t, paths):
@@ -73,13 +103,26 @@ class FrameWriter:
         takes stay as they are (filter 0 on the host)."""
         from . import ops
         if t.dim() != 4 or t.shape[-1] != 3 or t.shape[2] > _lib.PNG_FILTER_MAX_WIDTH:
-            return t, paths, None
-        return ops.png_filter(t.contiguous(), "adaptive"), paths, int(t.shape[2])
+            return t, paths, None, None
+        return ops.png_filter(t.contiguous(), "adaptive"), paths, int(t.shape[2]), None
 
-    def _job(self, done, frame, path, width=None):
+    @staticmethod
+    def _deflated(t, paths, png_filter):
+        """(zlib streams (N, pitch) of t's rows, paths, W, (lens (N,), H)), launched on the current stream: the rows are
+        filter 0 or adaptive.  Frames the filter kernel does not take keep the host route."""
+        from . import ops
+        if t.dim() != 4 or t.shape[-1] != 3 or t.shape[2] > _lib.PNG_FILTER_MAX_WIDTH:
+            return t, paths, None, None
+        rows = ops.png_filter(t.contiguous(), "adaptive" if png_filter == "adaptive" else 0)
+        out, lens = ops.png_deflate(rows)
+        return out, paths, int(t.shape[2]), (lens, int(t.shape[1]))
+
+    def _job(self, done, frame, path, width=None, stream=None):
         try:
             done.synchronize()                              # nothing reads the pinned buffer before its copy has completed
-            if width is None:
+            if stream is not None:                          # a zlib stream of the device: its length came with the copy
+                write_png_stream(path, frame[:int(stream[0][0])], width, stream[1])
+            elif width is None:
                 write_png(path, frame, self.level)
             else:                                           # rows the device has filtered
                 write_png_rows(path, frame, width, frame.shape[0], self.level)
