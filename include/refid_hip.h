@@ -858,6 +858,39 @@ size_t refid_png_deflate_bound(int32_t stream_bytes, int32_t block_bytes);
 size_t refid_png_deflate_work_bytes(int32_t n_streams, int32_t stream_bytes, int32_t block_bytes);
 int refid_png_deflate(const refid_png_deflate_desc* d, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Full-reference scores of uint8 frames that are already on the device (csrc/score.hip): what calculate_psnr and
+ * calculate_ssim of basicsr/metrics/psnr_ssim.py do with crop_border and test_y_channel, per frame.
+ * a_u8, b_u8: (n_frames, h, w, 3) uint8 HWC -- RGB, or BGR with REFID_SCORE_BGR -- the layout refid_val_tail writes and
+ * refid_png_unfilter produces.  Both are cropped by crop_border on every side first: hc = h - 2cb, wc = w - 2cb; every
+ * clamp below is to the cropped frame.  Each of the four outputs may be NULL; its work is then skipped.
+ *   sq_rgb[f]  sum (a - b)^2 over the cropped frame and its 3 channels, an exact integer (calculate_psnr's numerator)
+ *   sq_y[f]    sum in float64 of e = fl32(d * d), d = fl32(Ya - Yb), Y the float32 BT.601 plane of the NIQE section above
+ *              (csrc/y_plane.h, one body for both): the float32 (img1 - img2)**2 of calculate_psnr(test_y_channel=True)
+ *   ssim3d[f]  the sum refid_ssim3d_u8 gives for the cropped frames as float32 u8/255 planes R, G, B, bit for bit
+ *              (csrc/ssim3d_tile.h, one body for the three kernels)
+ *   ssim_y[f]  the sum of _ssim_cly's map in float64: the window is outer(g, g) of the 11-tap sigma-1.5 Gaussian in float64
+ *              (closed form, normalised by its sum; computed on the host); the five fields Y1, Y2, Y1^2, Y2^2, Y1*Y2 (products
+ *              exact in float64) are each the 121-tap sum acc = acc + w * x in row-major tap order from a zero accumulator,
+ *              coordinates clamped (BORDER_REPLICATE); then ((2 mu1 mu2 + C1)(2 s12 + C2)) / ((mu1^2 + mu2^2 + C1)(s1 + s2 + C2))
+ *              with C1 = (0.01*255)^2, C2 = (0.03*255)^2 in the reference's operation order.  Divide by hc*wc for the mean.
+ * Every step of sq_y and ssim_y is one correctly rounded operation without contraction.  Each sum is a fixed tree per
+ * 16x16 tile (xor-shuffle inside a wave, then the waves in order), the tiles' partials [frame][tile row][tile column] are
+ * finished in a fixed order: no atomics, and the bits do not depend on the run, on n_frames or on the frame's place in the call.
+ * parts: refid_score_u8_parts(...) 8-byte words of scratch (0 for arguments the entry point turns down).  ya_out
+ * (n_frames, hc, wc) float32 = Y of a, ssim_y_map_out (n_frames, hc, wc) float64 = the map: test taps, each may be NULL
+ * (the map needs ssim_y).  The frames are read as aligned 4-byte words that hold at least one of their bytes, so up to 3
+ * bytes either side of a buffer are read (never used); such a word lies in the page of that byte.
+ * NULL frames or parts, unknown flags, crop_border < 0, hc < 1 or wc < 1, more than 2^31 - 1 tiles or frame bytes: returns 1
+ * with a message (refid_last_error) and launches nothing.  One kernel for the colour outputs, one for the Y outputs and
+ * one row sum per output, each only when asked for: at most six launches on `stream`; nothing is allocated.
+ * ---------------------------------------------------------------------------------- */
+#define REFID_SCORE_BGR 1
+long long refid_score_u8_parts(int n_frames, int h, int w, int crop_border);
+int refid_score_u8(const unsigned char* a_u8, const unsigned char* b_u8, int n_frames, int h, int w, int flags,
+                   int crop_border, unsigned long long* sq_rgb, double* sq_y, double* ssim3d, double* ssim_y,
+                   void* parts, float* ya_out, double* ssim_y_map_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -177,6 +177,7 @@ ASSEMBLE_STATS = 16                              # refid_assemble_single only: v
 
 VAL_TAIL_BGR = 1         # == REFID_VAL_TAIL_BGR in include/refid_hip.h
 NIQE_BGR = 1             # == REFID_NIQE_BGR in include/refid_hip.h
+SCORE_BGR = 1            # == REFID_SCORE_BGR in include/refid_hip.h
 PNG_MAX_ROW_BYTES = 32760    # == REFID_PNG_MAX_ROW_BYTES in include/refid_hip.h
 PNG_FILTER_ADAPTIVE = 5      # == REFID_PNG_FILTER_ADAPTIVE in include/refid_hip.h
 PNG_FILTER_MAX_WIDTH = 11184810    # == REFID_PNG_FILTER_MAX_WIDTH in include/refid_hip.h
@@ -317,6 +318,9 @@ def _bind_extra(L):
     L.refid_png_deflate_work_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     L.refid_png_deflate_work_bytes.restype = C.c_size_t
     L.refid_png_deflate.argtypes = [C.POINTER(PngDeflateDesc), vp]
+    L.refid_score_u8_parts.argtypes = [i, i, i, i]
+    L.refid_score_u8_parts.restype = ll
+    L.refid_score_u8.argtypes = [vp, vp, i, i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp]
 
 
 def check(rc, what):

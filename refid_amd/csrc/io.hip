@@ -8,6 +8,7 @@
 // callers that want a full grid; the training path does not need it any more: sample.hip voxelises the float32 event
 // rows of the datasets inside the crop with integer (bit-reproducible) sums while it assembles the batch.
 #include "common.h"
+#include "ssim3d_tile.h"
 
 namespace {
 
@@ -77,11 +78,10 @@ __global__ __launch_bounds__(256) void tile_norm_kernel(float* __restrict__ acc,
 // ---- SSIM of the reference's _ssim_3d (metrics/psnr_ssim.py:135-182): 11x11x11 separable Gaussian
 // (sigma 1.5) over (H, W, C=3) with REPLICATE padding in all three axes, fp32, on the uint8-quantised
 // frames; ssim map mean over H*W*3.  One block = 16x16 output pixels x 3 channels.
-struct SsimConst { float g[11]; float mc[3][3]; };
-
+// The arithmetic lives in ssim3d_tile.h, shared with val_tail_kernel below and with score.hip.
 __global__ __launch_bounds__(256) void ssim3d_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                     int H, int W, const SsimConst k, double* __restrict__ out) {
-    constexpr int T = 16, R = 5, HS = T + 2 * R;          // 26
+    constexpr int T = SSIM_T, R = SSIM_R, HS = SSIM_HS;   // 16, 5, 26
     __shared__ float sA[3][HS][HS + 1], sB[3][HS][HS + 1];
     __shared__ float sH[5][3][HS][T + 1];
     __shared__ double sred[4];
@@ -96,47 +96,12 @@ __global__ __launch_bounds__(256) void ssim3d_kernel(const float* __restrict__ a
         sB[c][r][q] = quant255(pb[((long long)c * H + y) * W + x]);
     }
     __syncthreads();
-    for (int e = threadIdx.x; e < 3 * HS * T; e += 256) {          // horizontal pass, 5 fields
-        const int c = e / (HS * T), r = (e / T) % HS, q = e % T;
-        float m1 = 0.f, m2 = 0.f, s11 = 0.f, s22 = 0.f, s12 = 0.f;
-#pragma unroll
-        for (int j = 0; j < 11; ++j) {
-            const float va = sA[c][r][q + j], vb = sB[c][r][q + j], g = k.g[j];
-            m1 += g * va; m2 += g * vb; s11 += g * va * va; s22 += g * vb * vb; s12 += g * va * vb;
-        }
-        sH[0][c][r][q] = m1; sH[1][c][r][q] = m2; sH[2][c][r][q] = s11; sH[3][c][r][q] = s22; sH[4][c][r][q] = s12;
-    }
+    SSIM3D_HPASS(sA, sB, sH, k)
     __syncthreads();
     const int ty = threadIdx.x / T, tx = threadIdx.x % T;
-    float v[5][3];
-#pragma unroll
-    for (int fi = 0; fi < 5; ++fi)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            float s = 0.f;
-#pragma unroll
-            for (int j = 0; j < 11; ++j) s += k.g[j] * sH[fi][c][ty + j][tx];
-            v[fi][c] = s;
-        }
-    double acc = 0.0;
-    if (y0 + ty < H && x0 + tx < W) {
-        const float C1 = (0.01f * 255.f) * (0.01f * 255.f), C2 = (0.03f * 255.f) * (0.03f * 255.f);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {                               // channel-axis pass (replicate-padded)
-            float w[5];
-#pragma unroll
-            for (int fi = 0; fi < 5; ++fi) w[fi] = k.mc[c][0] * v[fi][0] + k.mc[c][1] * v[fi][1] + k.mc[c][2] * v[fi][2];
-            const float mu1 = w[0], mu2 = w[1];
-            const float s1 = w[2] - mu1 * mu1, s2 = w[3] - mu2 * mu2, s12 = w[4] - mu1 * mu2;
-            acc += (double)(((2.f * mu1 * mu2 + C1) * (2.f * s12 + C2)) / ((mu1 * mu1 + mu2 * mu2 + C1) * (s1 + s2 + C2)));
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-    if ((threadIdx.x & 63) == 0) sred[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0)                                           // partial [frame][tile row][tile column]
-        out[((long long)f * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = sred[0] + sred[1] + sred[2] + sred[3];
+    SSIM3D_PIXEL(acc, sH, k, ty, tx, y0 + ty < H && x0 + tx < W)
+    // partial [frame][tile row][tile column]
+    SSIM3D_BLOCK_SUM(acc, sred, out[((long long)f * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x])
 }
 
 // ---- fused validation tail (twoImage_event_recurrent_model.py:412-491): tensor2img of pred / gt into HWC uint8 images,
@@ -230,45 +195,10 @@ __global__ __launch_bounds__(256) void val_tail_kernel(const float* __restrict__
         if (threadIdx.x == 0) sq_parts[blockIdx.x] = s;
     }
     if constexpr (SSIM) {
-        for (int e = threadIdx.x; e < 3 * HS * T; e += 256) {       // horizontal pass, 5 fields
-            const int c = e / (HS * T), r = (e / T) % HS, q = e % T;
-            float m1 = 0.f, m2 = 0.f, s11 = 0.f, s22 = 0.f, s12 = 0.f;
-#pragma unroll
-            for (int j = 0; j < 11; ++j) {
-                const float va = sA[c][r][q + j], vb = sB[c][r][q + j], g = k.g[j];
-                m1 += g * va; m2 += g * vb; s11 += g * va * va; s22 += g * vb * vb; s12 += g * va * vb;
-            }
-            sH[0][c][r][q] = m1; sH[1][c][r][q] = m2; sH[2][c][r][q] = s11; sH[3][c][r][q] = s22; sH[4][c][r][q] = s12;
-        }
+        SSIM3D_HPASS(sA, sB, sH, k)
         __syncthreads();
-        float v[5][3];
-#pragma unroll
-        for (int fi = 0; fi < 5; ++fi)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                float s = 0.f;
-#pragma unroll
-                for (int j = 0; j < 11; ++j) s += k.g[j] * sH[fi][c][ty + j][tx];
-                v[fi][c] = s;
-            }
-        double acc = 0.0;
-        if (inside) {
-            const float C1 = (0.01f * 255.f) * (0.01f * 255.f), C2 = (0.03f * 255.f) * (0.03f * 255.f);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {                           // channel-axis pass (replicate-padded)
-                float w[5];
-#pragma unroll
-                for (int fi = 0; fi < 5; ++fi) w[fi] = k.mc[c][0] * v[fi][0] + k.mc[c][1] * v[fi][1] + k.mc[c][2] * v[fi][2];
-                const float mu1 = w[0], mu2 = w[1];
-                const float s1 = w[2] - mu1 * mu1, s2 = w[3] - mu2 * mu2, s12 = w[4] - mu1 * mu2;
-                acc += (double)(((2.f * mu1 * mu2 + C1) * (2.f * s12 + C2)) / ((mu1 * mu1 + mu2 * mu2 + C1) * (s1 + s2 + C2)));
-            }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-        if ((threadIdx.x & 63) == 0) sred[threadIdx.x >> 6] = acc;
-        __syncthreads();
-        if (threadIdx.x == 0) ssim_parts[blockIdx.x] = sred[0] + sred[1] + sred[2] + sred[3];
+        SSIM3D_PIXEL(acc, sH, k, ty, tx, inside)
+        SSIM3D_BLOCK_SUM(acc, sred, ssim_parts[blockIdx.x])
     }
 }
 
@@ -289,6 +219,12 @@ __global__ __launch_bounds__(256) void sum_rows_u64_kernel(const unsigned long l
 int nb(long long n) { long long b = (n + 255) / 256; return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b)); }
 
 }  // namespace
+
+int refid_launch_sum_rows_u64(const unsigned long long* part, int rows, int n, unsigned long long* out, hipStream_t st) {
+    hipLaunchKernelGGL(sum_rows_u64_kernel, dim3(rows), dim3(256), 0, st, part, n, out);
+    REFID_LAUNCH_CHECK("sum_rows_u64");
+    return 0;
+}
 
 extern "C" int refid_events_to_voxel(const double* ts, const int* xs, const int* ys, const float* ps,
                                      long long n_events, int num_bins, int width, int height, double first_stamp,
@@ -343,19 +279,6 @@ extern "C" int refid_tile_normalize(float* acc, const float* cnt, int c, int h, 
     return 0;
 }
 
-static SsimConst ssim_const() {
-    SsimConst k;
-    double g[11], s = 0.0;                                  // cv2.getGaussianKernel(11, 1.5)
-    for (int i = 0; i < 11; ++i) { g[i] = exp(-((i - 5) * (i - 5)) / (2.0 * 1.5 * 1.5)); s += g[i]; }
-    for (int i = 0; i < 11; ++i) { g[i] /= s; k.g[i] = (float)g[i]; }
-    for (int c = 0; c < 3; ++c) {                           // 11 taps along the 3-channel axis, replicate padding
-        double m[3] = {0, 0, 0};
-        for (int j = 0; j < 11; ++j) { int cc = c + j - 5; cc = cc < 0 ? 0 : (cc > 2 ? 2 : cc); m[cc] += g[j]; }
-        for (int q = 0; q < 3; ++q) k.mc[c][q] = (float)m[q];
-    }
-    return k;
-}
-
 extern "C" int refid_ssim3d_u8_parts(int n_frames, int h, int w) {
     return (n_frames > 0 && h > 0 && w > 0) ? n_frames * cdiv(w, 16) * cdiv(h, 16) : 0;
 }
@@ -398,8 +321,7 @@ extern "C" int refid_val_tail(const float* pred, const float* gt, int n_frames, 
                            SsimConst{}, pred_u8, gt_u8, sq_parts, ssim_parts);
     REFID_LAUNCH_CHECK("val_tail");
     if (sq_out) {
-        hipLaunchKernelGGL(sum_rows_u64_kernel, dim3(n_frames), dim3(256), 0, st, sq_parts, tx * ty, sq_out);
-        REFID_LAUNCH_CHECK("val_tail/sq");
+        if (int rc = refid_launch_sum_rows_u64(sq_parts, n_frames, tx * ty, sq_out, st)) return rc;
     }
     if (ssim_out) return refid_launch_sum_rows_f64(ssim_parts, n_frames, tx * ty, ssim_out, st);
     return 0;

@@ -16,6 +16,7 @@
 // the divisions, and for sqrtf the v_sqrt_f32 whose two neighbours are tried against fma residuals (the only fused
 // operations in the file are those inside these two expansions and the float64 division's).
 #include "common.h"
+#include "y_plane.h"
 
 #pragma clang fp contract(off)
 
@@ -32,10 +33,8 @@ constexpr int niqe_lds_bytes() {
 
 // to_y_channel after astype(float32): fl32(fl32(y64 / 255) * 255), y64 in float64 from the fl32(u8 / 255) channels
 __device__ __forceinline__ float niqe_y(const unsigned char* __restrict__ p, int bgr) {
-    const float c0 = __fdiv_rn((float)p[0], 255.f), c1 = __fdiv_rn((float)p[1], 255.f), c2 = __fdiv_rn((float)p[2], 255.f);
-    const double b = bgr ? c0 : c2, g = c1, r = bgr ? c2 : c0;
-    const double y64 = ((b * 24.966 + g * 128.553) + r * 65.481) + 16.0;
-    return (float)(y64 / 255.0) * 255.f;
+    const float c0 = (float)p[0], c1 = (float)p[1], c2 = (float)p[2];
+    return refid_y601_u8(bgr ? c2 : c0, c1, bgr ? c0 : c2);        // y_plane.h: shared with score.hip
 }
 
 template <int BS, int SCALE>

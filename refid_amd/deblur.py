@@ -9,7 +9,9 @@
 (sorted by name) or a ``.npy`` stack (N, H, W, 3) uint8 RGB; ``--stamps`` a text file with the exposure ``start end`` of
 every frame per line, in the events' clock.  Frame k is written to ``{out}/{k:06d}.png``.  ``--niqe PARAMS.npz`` (the
 reference's ``niqe_pris_params.npz``) also scores every output frame with NIQE: ``{out}/niqe.txt`` holds one ``file score``
-line per frame and a last ``mean`` line over the finite scores, which is printed too."""
+line per frame and a last ``mean`` line over the finite scores, which is printed too.  ``--gt DIR`` (sharp PNGs named as
+the output frames) scores every output frame against ground truth while it is on the GPU: ``{out}/scores.txt``, as for
+``refid_amd.interpolate``."""
 import sys
 
 from .interpolate import load_frames, load_frames_resident, png_deflate_setting, png_filter_setting, write_niqe  # noqa: F401  (for other callers)

@@ -9,7 +9,10 @@ released network size.  ``--frames`` is a directory of 8-bit PNGs (sorted by nam
 RGB; ``--stamps`` a text file with one key-frame timestamp per line (sharp layout) or an exposure ``start end`` per line
 (blur layout), in the events' clock.  Frame f of pair k is written to ``{out}/{k:06d}_{f:02d}.png``.  ``--niqe PARAMS.npz``
 (the reference's ``niqe_pris_params.npz``) also scores every output frame with NIQE: ``{out}/niqe.txt`` holds one
-``file score`` line per frame and a last ``mean`` line over the finite scores, which is printed too."""
+``file score`` line per frame and a last ``mean`` line over the finite scores, which is printed too.  ``--gt DIR`` (PNGs
+named as the output frames) scores every output frame against ground truth while it is on the GPU: ``{out}/scores.txt``
+holds ``file psnr ssim`` per frame and a last ``mean`` line (``python -m refid_amd.score`` scores a finished directory, with
+``--crop-border`` and the Y-channel variants)."""
 import argparse
 import glob
 import os
@@ -135,6 +138,8 @@ def parser(prog, doc, opt_help, frames_help, stamps_help):
     ap.add_argument("--out", required=True, help="output directory")
     ap.add_argument("--swap-xy", action="store_true", help="the HighREV files' swapped x / y columns")
     ap.add_argument("--niqe", metavar="PARAMS.npz", help="score every output frame with NIQE (niqe_pris_params.npz) -> niqe.txt")
+    ap.add_argument("--gt", metavar="DIR", help="ground-truth PNGs named as the output frames: PSNR and SSIM of every output "
+                                                "frame against them -> scores.txt (more: python -m refid_amd.score)")
     ap.add_argument("--png-filter", choices=("none", "adaptive"),
                     help="PNG row filters of the output: none (type 0 on every row) or adaptive (chosen per row on the GPU: "
                          "smaller files, cheaper to write); default: val.png_filter of --opt, else none")
@@ -177,9 +182,23 @@ def run_and_report(runner, args, frames, events, items, niqe_model, noun, file_n
     """Runs ``items`` (named by their index) into --out and, with --niqe, writes niqe.txt; ``file_name``: the format of an
     output file's name from ``name`` and the frame ``f`` of the item."""
     names = [f"{k:06d}" for k in range(len(items))]
-    runner.run(frames, events, items, out_dir=args.out, names=names, niqe=niqe_model, png_filter=png_filter_setting(args),
-               png_deflate=png_deflate_setting(args))
+    from ._lib import RefidHipError
+    try:
+        runner.run(frames, events, items, out_dir=args.out, names=names, niqe=niqe_model, png_filter=png_filter_setting(args),
+                   png_deflate=png_deflate_setting(args), gt=args.gt)
+    except RefidHipError as ex:
+        if args.gt and "ground truth" in str(ex):
+            raise SystemExit(f"--gt: {ex}")
+        raise
     print(f"{len(items)} {noun} -> {args.out}")
+    if args.gt:
+        from .score import format_lines
+        sc = runner.scores
+        lines = format_lines([file_name.format(name=name, f=f) for name, f, _ in sc], ["psnr", "ssim"],
+                             [(s.psnr, s.ssim) for _, _, s in sc])
+        with open(os.path.join(args.out, "scores.txt"), "w") as f:
+            f.write("\n".join(lines) + "\n")
+        print(f"scores against {args.gt}: {lines[-1]} over {len(sc)} frames -> {os.path.join(args.out, 'scores.txt')}")
     if niqe_model is not None:
         scores = runner.niqe_scores
         mean = write_niqe(args.out, [file_name.format(name=name, f=f) for name, f, _ in scores], [s for _, _, s in scores])

@@ -1160,3 +1160,35 @@ def png_deflate(rows, block_bytes=None, out=None):
                                stream_bytes=size, block_bytes=block, out_pitch=int(out.shape[1]))
     check(L.refid_png_deflate(C.byref(desc), _stream()), "refid_png_deflate")
     return out, lens
+
+
+def score_u8(a_u8, b_u8, bgr=False, crop_border=0, sq_rgb=True, sq_y=False, ssim3d=True, ssim_y=False, taps=False):
+    """refid_score_u8 (csrc/score.hip) on the current stream: two uint8 CUDA tensors (..., H, W, 3) of one shape -> an int64
+    CUDA tensor (4, nf) of 8-byte words, row 0 the integer squared errors, rows 1..3 the bits of the float64 sums sq_y,
+    ssim3d, ssim_y in the layout of include/refid_hip.h (``.view(torch.float64)``); a row that was not asked for is not
+    written.  Both frames are cropped by ``crop_border`` first.  ``taps=True`` also returns [Y of ``a_u8`` float32
+    (nf, hc, wc), the Y SSIM map float64 (nf, hc, wc) or None without ``ssim_y``].  Does not synchronise."""
+    for t in (a_u8, b_u8):
+        if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.uint8 or t.dim() < 3 or t.shape[-1] != 3 or t.numel() == 0:
+            raise _lib.RefidHipError("score_u8: non-empty uint8 CUDA tensors (..., H, W, 3) are required (no CPU fallback)")
+    if a_u8.shape != b_u8.shape or a_u8.device != b_u8.device:
+        raise _lib.RefidHipError(f"score_u8: the frames differ: {tuple(a_u8.shape)} on {a_u8.device}, {tuple(b_u8.shape)} on "
+                                 f"{b_u8.device}")
+    a_u8, b_u8 = a_u8.contiguous(), b_u8.contiguous()
+    h, w, cb = int(a_u8.shape[-3]), int(a_u8.shape[-2]), int(crop_border)
+    nf = a_u8.numel() // (3 * h * w)
+    hc, wc = h - 2 * cb, w - 2 * cb
+    if cb < 0 or hc < 1 or wc < 1:
+        raise _lib.RefidHipError(f"score_u8: crop_border {cb} leaves nothing of a {h}x{w} frame")
+    words = lib().refid_score_u8_parts(nf, h, w, cb)
+    if words <= 0:
+        raise _lib.RefidHipError(f"score_u8: {nf} frames of {h}x{w} exceed a 31-bit offset or the grid (split the call)")
+    buf = torch.empty(4 * nf + words, dtype=torch.int64, device=a_u8.device)
+    out = buf[:4 * nf].view(4, nf)
+    ya = torch.empty((nf, hc, wc), dtype=torch.float32, device=a_u8.device) if taps else None
+    ymap = torch.empty((nf, hc, wc), dtype=torch.float64, device=a_u8.device) if taps and ssim_y else None
+    ptr = lambda t, on=True: t.data_ptr() if (t is not None and on) else None      # noqa: E731
+    check(lib().refid_score_u8(a_u8.data_ptr(), b_u8.data_ptr(), nf, h, w, _lib.SCORE_BGR if bgr else 0, cb,
+                               ptr(out[0], sq_rgb), ptr(out[1], sq_y), ptr(out[2], ssim3d), ptr(out[3], ssim_y),
+                               buf[4 * nf:].data_ptr(), ptr(ya), ptr(ymap), _stream()), "refid_score_u8")
+    return (out, [ya, ymap]) if taps else out

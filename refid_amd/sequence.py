@@ -305,12 +305,20 @@ class _SequenceRunner:
     ``niqe``: a ``niqe.NiqeModel``.  Every minibatch's uint8 frames then also go through the NIQE moments kernel
     (csrc/niqe.hip) on the current stream and the few sums per block are copied, non-blocking, into one pinned buffer; the
     host finish of all frames runs after the loop, which gains no synchronisation.  ``niqe_scores`` then holds
-    ``(name, frame index, score)`` per frame, in output order (None when ``niqe`` was not given)."""
+    ``(name, frame index, score)`` per frame, in output order (None when ``niqe`` was not given).
+
+    ``gt``: ground truth for the output frames, which are then scored against it while they are resident
+    (``score.FrameScorer``, csrc/score.hip), again without a synchronisation in the loop: a directory that holds a PNG of
+    the name of every output frame (decoded on the GPU per minibatch), or uint8 (all output frames, H, W, 3) RGB in output
+    order (uploaded once).  ``score``: the ``FrameScorer`` to use -- its ``crop_border`` and which scores it takes; default
+    ``FrameScorer()``: PSNR and the 3-D SSIM, uncropped.  ``scores`` then holds ``(name, frame index, score.Scores)`` per
+    frame, a ``Scores`` field being None for what was not asked for (``scores`` is None without ``gt``)."""
 
     niqe_scores = None
+    scores = None
 
     def run(self, frames, events, pairs, out_dir=None, names=None, keep=False, bgr=False, niqe=None, png_filter="none",
-            png_deflate="host"):
+            png_deflate="host", gt=None, score=None):
         from . import niqe as niqe_mod
         from .validation import FrameWriter, check_png_deflate, check_png_filter
         what = type(self).__name__
@@ -332,6 +340,21 @@ class _SequenceRunner:
         if niqe is not None:
             niqe_mod.cropped_size(H, W)        # a frame without one 96x96 block raises here, before any work
         sums_pin, per_item = None, 0           # pinned (all frames, 2, blocks, 5, 5) float64, allocated at the first minibatch
+        self.scores = None
+        scorer, gt_dir, gt_all, scored = None, None, None, 0
+        if gt is not None:
+            from .score import FrameScorer
+            scorer = FrameScorer() if score is None else score
+            if isinstance(gt, (str, os.PathLike)):
+                gt_dir = os.fspath(gt)
+            else:
+                gt_all = torch.as_tensor(gt) if not torch.is_tensor(gt) else gt
+                if gt_all.dtype != torch.uint8 or gt_all.dim() != 4 or tuple(gt_all.shape[1:]) != (H, W, 3):
+                    raise RefidHipError(f"{what}.run: gt must be a directory or uint8 (frames, {H}, {W}, 3), got {gt_all.dtype} "
+                                        f"{tuple(gt_all.shape)}")
+                gt_all = gt_all.contiguous().to(self.device, non_blocking=True)
+        elif score is not None:
+            raise RefidHipError(f"{what}.run: score= needs gt=")
         chunks = [pairs[i:i + self.max_minibatch] for i in range(0, len(pairs), self.max_minibatch)]
 
         def preload(k):
@@ -355,8 +378,8 @@ class _SequenceRunner:
                     nxt = preload(k + 1)
                     out = self._forward(batch)
                     u8 = metrics.val_tail(out[..., :H, :W], bgr=False).pred_u8       # (P, [T,] H, W, 3)
+                    base = k * self.max_minibatch
                     if writer is not None:
-                        base = k * self.max_minibatch
                         paths = [p for i in range(len(chunk)) for p in self._paths(out_dir, names[base + i], u8[i])]
                         writer.dump([(u8.view(-1, H, W, 3), paths)])
                     if niqe is not None:
@@ -366,6 +389,23 @@ class _SequenceRunner:
                             sums_pin = torch.empty((len(pairs) * per_item,) + tuple(sums.shape[1:]), dtype=sums.dtype).pin_memory()
                         at = k * self.max_minibatch * per_item
                         sums_pin[at:at + sums.shape[0]].copy_(sums, non_blocking=True)
+                    if scorer is not None:
+                        flat = u8.view(-1, H, W, 3)
+                        if gt_dir is not None:
+                            gpaths = [p for i in range(len(chunk)) for p in self._paths(gt_dir, names[base + i], u8[i])]
+                            for p in gpaths:
+                                if not os.path.isfile(p):
+                                    raise RefidHipError(f"{what}.run: no ground truth {p}")
+                            g = load_png_frames(gpaths, device=self.device, frames_per_launch=len(gpaths))
+                            if g.shape != flat.shape:
+                                raise RefidHipError(f"{what}.run: the ground truth {gpaths[0]} is {g.shape[1]}x{g.shape[2]}, the "
+                                                    f"output {H}x{W}")
+                        else:
+                            g = gt_all[scored:scored + flat.shape[0]]
+                            if g.shape[0] != flat.shape[0]:
+                                raise RefidHipError(f"{what}.run: gt holds {gt_all.shape[0]} frames, fewer than the outputs")
+                        scorer.add(flat, g)
+                        scored += flat.shape[0]
                     if keep:
                         kept.append(u8)
         finally:
@@ -377,6 +417,14 @@ class _SequenceRunner:
             cur.synchronize()                  # the last sums have arrived
             scores = niqe_mod.finish(sums_pin.numpy(), niqe)
             self.niqe_scores = [(names[i // per_item], i % per_item, sc) for i, sc in enumerate(scores)]
+        if scorer is not None:
+            from .score import Scores
+            if gt_all is not None and scored != gt_all.shape[0]:
+                raise RefidHipError(f"{what}.run: gt holds {gt_all.shape[0]} frames for {scored} outputs")
+            sc = scorer.finish()                # the one synchronisation, after the loop
+            each = scored // len(pairs)
+            self.scores = [(names[i // each], i % each, Scores(*(None if col is None else col[i] for col in sc)))
+                           for i in range(scored)]
         return torch.cat(kept, dim=0).cpu().numpy() if keep else None
 
 
@@ -398,14 +446,16 @@ class SequenceInterpolator(_SequenceRunner):
         self.stream = torch.cuda.Stream(device=self.device)
 
     def run(self, frames, events, pairs, out_dir=None, names=None, keep=False, bgr=False, niqe=None, png_filter="none",
-            png_deflate="host"):
+            png_deflate="host", gt=None, score=None):
         """``frames`` uint8 (N, H, W, 3), ``events`` float32 (E, 4), ``pairs`` from ``make_pairs``.  With ``out_dir`` frame f
         of pair k goes to ``{out_dir}/{names[k]}_{f:02d}.png`` (default name: the left key frame's index, six digits, as
         the validation dumps are named).  ``keep=True`` returns the uint8 frames (P, T, H, W, 3) on the host, else None.
         ``niqe``: a ``NiqeModel``; ``niqe_scores`` then holds (name, f, score) per output frame.  ``png_filter``: 'none' or
         'adaptive' (``validation.FrameWriter``): the same pixels in smaller files.  ``png_deflate``: 'host' or 'device'
-        (the PNGs' zlib streams come from the GPU, ``ops.png_deflate``): the same pixels again."""
-        return super().run(frames, events, pairs, out_dir, names, keep, bgr, niqe, png_filter, png_deflate)
+        (the PNGs' zlib streams come from the GPU, ``ops.png_deflate``): the same pixels again.  ``gt`` / ``score``: ground
+        truth to score the outputs against (``_SequenceRunner``): a directory of ``{names[k]}_{f:02d}.png`` or the uint8
+        frames; ``scores`` then holds (name, f, ``score.Scores``) per output frame."""
+        return super().run(frames, events, pairs, out_dir, names, keep, bgr, niqe, png_filter, png_deflate, gt, score)
 
     def _forward(self, batch):
         return self.net(x=batch["lq"], event=batch["voxel"])
@@ -440,13 +490,13 @@ class SequenceDeblurrer(_SequenceRunner):
         self.stream = torch.cuda.Stream(device=self.device)
 
     def run(self, frames, events, items, out_dir=None, names=None, keep=False, bgr=False, niqe=None, png_filter="none",
-            png_deflate="host"):
+            png_deflate="host", gt=None, score=None):
         """``frames`` uint8 (N, H, W, 3), ``events`` float32 (E, 4), ``items`` from ``make_pairs(t, *frame_windows(...))``.
         With ``out_dir`` item k goes to ``{out_dir}/{names[k]}.png`` (default name: the frame index, six digits).
         ``keep=True`` returns the uint8 frames (P, H, W, 3) on the host, else None.
         ``niqe``: a ``NiqeModel``; ``niqe_scores`` then holds (name, 0, score) per output frame.  ``png_filter``: as for
-        ``SequenceInterpolator.run``."""
-        return super().run(frames, events, items, out_dir, names, keep, bgr, niqe, png_filter, png_deflate)
+        ``SequenceInterpolator.run``.  ``gt`` / ``score``: as there, the directory holding ``{names[k]}.png``."""
+        return super().run(frames, events, items, out_dir, names, keep, bgr, niqe, png_filter, png_deflate, gt, score)
 
     def _forward(self, batch):
         if self.crop_size is None:
