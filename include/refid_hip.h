@@ -891,6 +891,68 @@ int refid_score_u8(const unsigned char* a_u8, const unsigned char* b_u8, int n_f
                    int crop_border, unsigned long long* sq_rgb, double* sq_y, double* ssim3d, double* ssim_y,
                    void* parts, float* ya_out, double* ssim_y_map_out, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Baseline JPEG frames for Motion-JPEG video (csrc/jpeg.hip).  frames: (n_frames, height, width, 3) uint8 RGB, contiguous,
+ * what refid_val_tail writes; frame k becomes ONE baseline sequential JFIF file at out + k*out_pitch, lens[k] bytes long:
+ *   SOI | APP0 "JFIF" 1.01, density 1:1 without unit, no thumbnail | DQT, one segment with table 0 (luminance) and table 1
+ *   (chrominance), 8 bit, in zig-zag order | SOF0: 8 bit, height, width, components 1 2 3, Y sampling 2x2 (REFID_JPEG_420) or
+ *   1x1 (REFID_JPEG_444) on table 0, Cb and Cr 1x1 on table 1 | DHT x4 in the order DC0 AC0 DC1 AC1: the typical tables
+ *   K.3 .. K.6 of ITU-T T.81 Annex K, unchanged | DRI | SOS: interleaved, Y on DC0/AC0, Cb and Cr on DC1/AC1, Ss 0, Se 63,
+ *   Ah/Al 0 | the entropy-coded segments, RSTm in front of every segment but the first (m = 0 1 .. 7 0 ..) | EOI.
+ * These REFID_JPEG_HEADER_BYTES = 625 bytes in front of the first segment do not depend on the frame's content.
+ * Colour: JFIF full-range BT.601 in 16-bit fixed point, per pixel
+ *   Y  = ( 19595 R + 38470 G +  7471 B + 32768) >> 16
+ *   Cb = (-11059 R - 21709 G + 32768 B + 8421375) >> 16        (8421375 = (128 << 16) + 32767)
+ *   Cr = ( 32768 R - 27439 G -  5329 B + 8421375) >> 16
+ * A frame that does not fill its last MCU column or row (MCU: 16x16 pixels for 420, 8x8 for 444) is extended by replicating
+ * its last column and row: pixel (y, x) of the extension is pixel (min(y, height-1), min(x, width-1)); no read leaves the
+ * frame.  420 chroma: the rounded mean (a + b + c + d + 2) >> 2 of the Cb (Cr) of each 2x2 pixels of the extended frame.
+ * DCT: s = sample - 128; with T[u][k] = round(2^14 a(u) cos((2k+1) u pi / 16)), a(0) = sqrt(1/8), a(u) = 1/2, rounded half
+ * away from zero:  r[y][u] = (sum_k s[y][k] T[u][k] + 128) >> 8 (arithmetic shift), then F[v][u] = sum_k r[k][u] T[v][k], which
+ * is 2^20 times the orthonormal coefficient; F[0][0] is instead the exact (sum of the 64 s) << 17, so that a flat block
+ * quantises as its mean does, ties included (its AC terms are exactly 0: every row u > 0 of T sums to 0).  Quantisation: the Annex K tables K.1 / K.2 scaled as libjpeg does, s = 5000/q
+ * (integer division) for quality q < 50, else 200 - 2q; entry Q = clamp((base*s + 50)/100, 1, 255); the quantised coefficient
+ * is sign(F) * (((|F| + (Q << 19)) >> 20) / Q): F / (2^20 Q) rounded half away from zero (|F| + (Q << 19) < 2^31).
+ * Entropy coding (T.81 F.1.2): DC difference to the previous block of the same component, predictor 0 at every segment
+ * start, as category and bits; AC in zig-zag order as run/size, ZRL for runs over 15, EOB unless coefficient 63 is
+ * non-zero; every FF byte followed by 00; every segment padded to a byte with 1-bits.  A segment is restart_mcus MCUs
+ * (1 .. 65535; 0: the MCUs of one MCU row; the frame's last segment may be shorter).  tests/jpeg_ref.py restates all of it.
+ * Integers only; the only atomics are integer adds / ors in LDS, whose result does not depend on the order: bytes
+ * [0, lens[k]) of a frame do not depend on n_frames, on the frame's place in the call, on the alignment of frames or out,
+ * or on the run.
+ * Three launches on `stream` that meet only at the kernel boundaries -- per segment: coefficients, codes, the unstuffed
+ * bits parked in `work`, the stuffed length; per frame: segment offsets, the header, EOI, lens; per segment: RSTm and the
+ * stuffed bytes into place -- nothing is allocated, nothing synchronises.
+ * refid_jpeg_bound(height, width, subsampling, restart_mcus) is a length every frame of that geometry fits, whatever its
+ * content and quality: a block costs at most REFID_JPEG_BLOCK_BITS = 1660 bits (DC: an 11-bit code of table K.4 and 11 bits;
+ * each of 63 AC coefficients a 16-bit code and 10 bits, no EOB), a segment of b blocks ceil(1660 b / 8) bytes before
+ * stuffing, at most every byte is FF and doubles, and every segment but the first has its 2-byte RSTm in front:
+ *   bound = 625 + sum over segments of 2 * ceil(1660 * blocks / 8) + 2 * (segments - 1) + 2.
+ * out_pitch may be smaller, down to 627 (header and EOI): a frame whose file does not fit gets lens[k] = -(bytes needed),
+ * its slot may hold anything and nothing outside the slot is written.  Bytes [lens[k], out_pitch) of a slot that fitted are
+ * left as they were.  Nothing outside [out, out + n_frames*out_pitch), lens[0 .. n_frames) and the first
+ * refid_jpeg_work_bytes(...) bytes of work is written: per segment a 16-byte record and room for its unstuffed bytes,
+ *   work_bytes = n_frames * segments * (16 + round_up(ceil(1660 * blocks of the largest segment / 8), 4)).
+ * height, width 1 .. 65535; quality 1 .. 100; lens and work aligned to 4 bytes; the bound and n_frames * segments must fit
+ * int32.  A bad argument returns 1 with a message (refid_last_error) and launches nothing; the size functions return 0 for
+ * what the entry point would turn down.
+ * ---------------------------------------------------------------------------------- */
+#define REFID_JPEG_444 0
+#define REFID_JPEG_420 1
+#define REFID_JPEG_HEADER_BYTES 625
+#define REFID_JPEG_BLOCK_BITS 1660
+typedef struct refid_jpeg_desc {
+    const uint8_t* frames;                      /* device: n_frames * height * width * 3 bytes, RGB                */
+    uint8_t* out;                               /* device: n_frames * out_pitch bytes                              */
+    int32_t* lens;                              /* device: [n_frames], the files' lengths, or -(bytes needed)      */
+    uint32_t* work;                             /* device: refid_jpeg_work_bytes(...) bytes of scratch             */
+    int32_t n_frames, height, width, quality, subsampling, restart_mcus, out_pitch;
+} refid_jpeg_desc;
+int refid_jpeg_encode(const refid_jpeg_desc* d, void* stream);
+size_t refid_jpeg_header_bytes(void);
+size_t refid_jpeg_bound(int32_t height, int32_t width, int32_t subsampling, int32_t restart_mcus);
+size_t refid_jpeg_work_bytes(int32_t n_frames, int32_t height, int32_t width, int32_t subsampling, int32_t restart_mcus);
+
 #ifdef __cplusplus
 }
 #endif

@@ -171,6 +171,15 @@ class PngDeflateDesc(C.Structure):
     ]
 
 
+class JpegDesc(C.Structure):
+    """refid_jpeg_desc: uint8 RGB frames (n_frames, height, width, 3) -> one baseline JFIF file each, for Motion-JPEG."""
+    _fields_ = [
+        ("frames", C.c_void_p), ("out", C.c_void_p), ("lens", C.c_void_p), ("work", C.c_void_p),
+        ("n_frames", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("quality", C.c_int32), ("subsampling", C.c_int32),
+        ("restart_mcus", C.c_int32), ("out_pitch", C.c_int32),
+    ]
+
+
 LAYOUT_BLUR, LAYOUT_SHARP = 0, 1                # == REFID_LAYOUT_* in include/refid_hip.h
 ASSEMBLE_ZERO, ASSEMBLE_SCATTER, ASSEMBLE_FINISH, ASSEMBLE_FRAMES, ASSEMBLE_ALL = 1, 2, 4, 8, 15
 ASSEMBLE_STATS = 16                              # refid_assemble_single only: voxel_norm's statistics, between scatter and finish
@@ -184,6 +193,9 @@ PNG_FILTER_MAX_WIDTH = 11184810    # == REFID_PNG_FILTER_MAX_WIDTH in include/re
 PNG_DEFLATE_BLOCK = 32768          # == REFID_PNG_DEFLATE_BLOCK in include/refid_hip.h
 PNG_DEFLATE_MAX_BLOCK = 65535      # == REFID_PNG_DEFLATE_MAX_BLOCK in include/refid_hip.h
 PNG_DEFLATE_RECORD = 1088          # == REFID_PNG_DEFLATE_RECORD in include/refid_hip.h
+JPEG_444, JPEG_420 = 0, 1          # == REFID_JPEG_444 / REFID_JPEG_420 in include/refid_hip.h
+JPEG_HEADER_BYTES = 625            # == REFID_JPEG_HEADER_BYTES in include/refid_hip.h
+JPEG_BLOCK_BITS = 1660             # == REFID_JPEG_BLOCK_BITS in include/refid_hip.h
 ABI_VERSION = 9          # == REFID_ABI_VERSION in include/refid_hip.h
 _lib = None
 
@@ -318,6 +330,13 @@ def _bind_extra(L):
     L.refid_png_deflate_work_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     L.refid_png_deflate_work_bytes.restype = C.c_size_t
     L.refid_png_deflate.argtypes = [C.POINTER(PngDeflateDesc), vp]
+    L.refid_jpeg_encode.argtypes = [C.POINTER(JpegDesc), vp]
+    L.refid_jpeg_header_bytes.argtypes = []
+    L.refid_jpeg_header_bytes.restype = C.c_size_t
+    L.refid_jpeg_bound.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+    L.refid_jpeg_bound.restype = C.c_size_t
+    L.refid_jpeg_work_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+    L.refid_jpeg_work_bytes.restype = C.c_size_t
     L.refid_score_u8_parts.argtypes = [i, i, i, i]
     L.refid_score_u8_parts.restype = ll
     L.refid_score_u8.argtypes = [vp, vp, i, i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp]

@@ -15,7 +15,7 @@ the output frames) scores every output frame against ground truth while it is on
 import sys
 
 from .interpolate import load_frames, load_frames_resident, png_deflate_setting, png_filter_setting, write_niqe  # noqa: F401  (for other callers)
-from .interpolate import load_inputs, load_network, parser, run_and_report
+from .interpolate import load_inputs, load_network, parser, run_and_report, video_settings
 
 
 def settings(args):
@@ -55,6 +55,7 @@ def main(argv=None):
     ap.add_argument("--stamps-mode", choices=("events", "bounds"), default="events",
                     help="normalise event times from the first to the last event of a window, or from start to end")
     args = ap.parse_args(argv)
+    video_settings(args)                      # a bad flag exits before anything is loaded
 
     from . import sequence
     net_opt, ckpt, bins, mb, crop = settings(args)

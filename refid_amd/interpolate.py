@@ -135,7 +135,7 @@ def parser(prog, doc, opt_help, frames_help, stamps_help):
     ap.add_argument("--frames", required=True, help=frames_help)
     ap.add_argument("--events", required=True, nargs="+", help="event .npz files (x, y, timestamp, polarity), in time order")
     ap.add_argument("--stamps", required=True, help=stamps_help)
-    ap.add_argument("--out", required=True, help="output directory")
+    ap.add_argument("--out", help="output directory (PNG frames; optional with --video)")
     ap.add_argument("--swap-xy", action="store_true", help="the HighREV files' swapped x / y columns")
     ap.add_argument("--niqe", metavar="PARAMS.npz", help="score every output frame with NIQE (niqe_pris_params.npz) -> niqe.txt")
     ap.add_argument("--gt", metavar="DIR", help="ground-truth PNGs named as the output frames: PSNR and SSIM of every output "
@@ -146,7 +146,42 @@ def parser(prog, doc, opt_help, frames_help, stamps_help):
     ap.add_argument("--png-deflate", choices=("host", "device"),
                     help="where the output PNGs are deflated: host (zlib in the writer threads) or device (Huffman codes per "
                          "block on the GPU; the threads only write); default: val.png_deflate of --opt, else host")
+    ap.add_argument("--video", metavar="PATH", help="also (or, without --out, only) write the output frames, in order, as one "
+                                                    "Motion-JPEG AVI file; JPEG frames are encoded on the GPU")
+    ap.add_argument("--video-fps", default="30", help="frames per second of --video: a number or a fraction such as 30000/1001")
+    ap.add_argument("--video-quality", default="90", help="JPEG quality of --video, 1 .. 100")
+    ap.add_argument("--video-subsampling", default="420", help="chroma subsampling of --video: 420 or 444")
     return ap
+
+
+def video_settings(args):
+    """The keywords ``run`` takes for --video (empty without it); a bad value exits naming its flag.  Also: one of --out and
+    --video is needed, and the score files need --out."""
+    from fractions import Fraction
+    from ._lib import RefidHipError
+    from .validation import check_video_options
+    if not args.out and not args.video:
+        raise SystemExit("give --out, --video or both")
+    if not args.out and (args.gt or args.niqe):
+        raise SystemExit("--gt and --niqe write their files into --out: give --out")
+    if not args.video:
+        return {}
+    try:
+        fps = Fraction(args.video_fps)
+    except (ValueError, ZeroDivisionError):
+        raise SystemExit(f"--video-fps: {args.video_fps!r} is not a number or a fraction") from None
+    try:
+        quality = int(args.video_quality)
+    except ValueError:
+        raise SystemExit(f"--video-quality: {args.video_quality!r} is not an integer 1 .. 100") from None
+    try:
+        check_video_options(fps, quality, args.video_subsampling, None, "--video")
+    except RefidHipError as ex:
+        raise SystemExit(str(ex).replace("--video: video_", "--video-")) from None
+    out = dict(video=args.video, video_fps=fps, video_quality=quality, video_subsampling=args.video_subsampling)
+    if getattr(args, "video_no_keys", False):
+        out["video_keys"] = False
+    return out
 
 
 def load_inputs(args, noun):
@@ -185,12 +220,15 @@ def run_and_report(runner, args, frames, events, items, niqe_model, noun, file_n
     from ._lib import RefidHipError
     try:
         runner.run(frames, events, items, out_dir=args.out, names=names, niqe=niqe_model, png_filter=png_filter_setting(args),
-                   png_deflate=png_deflate_setting(args), gt=args.gt)
+                   png_deflate=png_deflate_setting(args), gt=args.gt, **video_settings(args))
     except RefidHipError as ex:
         if args.gt and "ground truth" in str(ex):
             raise SystemExit(f"--gt: {ex}")
         raise
-    print(f"{len(items)} {noun} -> {args.out}")
+    if args.out:
+        print(f"{len(items)} {noun} -> {args.out}")
+    if args.video:
+        print(f"{len(items)} {noun} -> {', '.join(runner.video_paths)}")
     if args.gt:
         from .score import format_lines
         sc = runner.scores
@@ -213,7 +251,10 @@ def main(argv=None):
     ap.add_argument("--m", type=int, help="frames to recover from each blurry key frame (blur layout)")
     ap.add_argument("--layout", choices=("sharp", "blur"))
     ap.add_argument("--max-minibatch", type=int, default=2)
+    ap.add_argument("--video-no-keys", action="store_true",
+                    help="--video holds the interpolated frames only (default for sharp key frames: the key frames too, in place)")
     args = ap.parse_args(argv)
+    video_settings(args)                      # a bad flag exits before anything is loaded
 
     from . import sequence
     net_opt, ckpt, m, n, layout = settings(args)

@@ -1162,6 +1162,63 @@ def png_deflate(rows, block_bytes=None, out=None):
     return out, lens
 
 
+JPEG_SUBSAMPLINGS = {"444": _lib.JPEG_444, "420": _lib.JPEG_420}
+
+
+def jpeg_default_pitch(height, width):
+    """The pitch ``jpeg_encode`` takes without one: the header and 3 bytes per pixel, rounded up to 4."""
+    return (_lib.JPEG_HEADER_BYTES + 3 * height * width + 3) // 4 * 4
+
+
+def jpeg_encode(frames_u8, quality=90, subsampling="420", restart_mcus=None, pitch=None, out=None):
+    """refid_jpeg_encode (csrc/jpeg.hip) on the current stream: uint8 CUDA RGB ``frames_u8`` (N, H, W, 3) -- what
+    ``val_tail`` writes -- -> (out uint8 (N, pitch), lens int32 (N,)): row n of ``out`` begins with the baseline JFIF file
+    of frame n, ``lens[n]`` bytes long; a frame whose file does not fit the pitch has ``lens[n]`` = -(bytes needed).
+    ``quality`` 1 .. 100, ``subsampling`` '420' or '444', ``restart_mcus`` 1 .. 65535 MCUs per restart interval (None: one
+    MCU row).  ``pitch``: None = the header and 3 bytes per pixel, rounded up to 4 (every natural frame fits), 'bound' =
+    ``refid_jpeg_bound`` (every frame fits), or an integer; ``out``: a contiguous uint8 (N, pitch) tensor to write into (any
+    alignment), its width is then the pitch.  The bytes behind a file are left as they were.  Does not synchronise."""
+    f = frames_u8
+    if not isinstance(f, torch.Tensor) or not f.is_cuda or f.dtype != torch.uint8 or f.dim() != 4 or f.shape[-1] != 3 or f.numel() == 0 or \
+            not f.is_contiguous():
+        raise _lib.RefidHipError("jpeg_encode: a non-empty contiguous uint8 CUDA tensor (N, H, W, 3) is required, got "
+                                 + (f"{f.dtype} {tuple(f.shape)} on {f.device}" if isinstance(f, torch.Tensor) else type(f).__name__))
+    if type(quality) is not int or not 1 <= quality <= 100:
+        raise _lib.RefidHipError(f"jpeg_encode: quality {quality!r} is not an integer 1 .. 100")
+    if subsampling not in JPEG_SUBSAMPLINGS:
+        raise _lib.RefidHipError(f"jpeg_encode: subsampling {subsampling!r} is not one of {sorted(JPEG_SUBSAMPLINGS)}")
+    if restart_mcus is not None and (type(restart_mcus) is not int or not 1 <= restart_mcus <= 65535):
+        raise _lib.RefidHipError(f"jpeg_encode: restart_mcus {restart_mcus!r} is not None or an integer 1 .. 65535")
+    n, h, w = int(f.shape[0]), int(f.shape[1]), int(f.shape[2])
+    ss, restart = JPEG_SUBSAMPLINGS[subsampling], restart_mcus or 0
+    L = lib()
+    bound = L.refid_jpeg_bound(h, w, ss, restart) if h <= 65535 and w <= 65535 else 0
+    work_bytes = L.refid_jpeg_work_bytes(n, h, w, ss, restart) if bound else 0
+    if not work_bytes:
+        raise _lib.RefidHipError(f"jpeg_encode: {n} frames of {h}x{w} exceed 65535 a side, the grid or a 31-bit file")
+    least = _lib.JPEG_HEADER_BYTES + 2
+    if out is not None:
+        if pitch is not None:
+            raise _lib.RefidHipError("jpeg_encode: give pitch or out, not both (the width of out is the pitch)")
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != f.device or out.dim() != 2 or \
+                out.shape[0] != n or out.shape[1] < least or out.shape[1] >= 2 ** 31 or not out.is_contiguous():
+            raise _lib.RefidHipError(f"jpeg_encode: out must be a contiguous uint8 ({n}, >= {least}) tensor on {f.device}")
+    else:
+        if pitch is None:
+            pitch = min(jpeg_default_pitch(h, w), 2 ** 31 - 1)
+        elif pitch == "bound":
+            pitch = bound
+        elif type(pitch) is not int or not least <= pitch < 2 ** 31:
+            raise _lib.RefidHipError(f"jpeg_encode: pitch {pitch!r} is not None, 'bound' or an integer {least} .. 2^31 - 1")
+        out = torch.empty((n, pitch), dtype=torch.uint8, device=f.device)
+    lens = torch.empty((n,), dtype=torch.int32, device=f.device)
+    work = torch.empty((work_bytes // 4,), dtype=torch.int32, device=f.device)
+    desc = _lib.JpegDesc(frames=f.data_ptr(), out=out.data_ptr(), lens=lens.data_ptr(), work=work.data_ptr(), n_frames=n, height=h,
+                         width=w, quality=quality, subsampling=ss, restart_mcus=restart, out_pitch=int(out.shape[1]))
+    check(L.refid_jpeg_encode(C.byref(desc), _stream()), "refid_jpeg_encode")
+    return out, lens
+
+
 def score_u8(a_u8, b_u8, bgr=False, crop_border=0, sq_rgb=True, sq_y=False, ssim3d=True, ssim_y=False, taps=False):
     """refid_score_u8 (csrc/score.hip) on the current stream: two uint8 CUDA tensors (..., H, W, 3) of one shape -> an int64
     CUDA tensor (4, nf) of 8-byte words, row 0 the integer squared errors, rows 1..3 the bits of the float64 sums sq_y,

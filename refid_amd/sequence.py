@@ -316,14 +316,22 @@ class _SequenceRunner:
 
     niqe_scores = None
     scores = None
+    video_paths = None
 
     def run(self, frames, events, pairs, out_dir=None, names=None, keep=False, bgr=False, niqe=None, png_filter="none",
-            png_deflate="host", gt=None, score=None):
+            png_deflate="host", gt=None, score=None, video=None, video_fps=30, video_quality=90, video_subsampling="420",
+            video_keys=None, jpeg_pitch=None):
         from . import niqe as niqe_mod
-        from .validation import FrameWriter, check_png_deflate, check_png_filter
+        from .validation import FrameWriter, VideoWriter, check_png_deflate, check_png_filter, check_video_options
         what = type(self).__name__
         png_filter = check_png_filter(png_filter, f"{what}.run: png_filter")
         png_deflate = check_png_deflate(png_deflate, f"{what}.run: png_deflate")
+        if video is not None:
+            check_video_options(video_fps, video_quality, video_subsampling, jpeg_pitch, f"{what}.run")
+            sharp = self.assembler.layout == "sharp"
+            if video_keys and not sharp:
+                raise RefidHipError(f"{what}.run: video_keys needs sharp key frames (layout 'sharp'), not {self.assembler.layout!r}")
+            video_keys = sharp if video_keys is None else bool(video_keys)
         pairs = list(pairs)
         if not pairs:
             raise RefidHipError(f"{what}.run: no pairs")
@@ -365,6 +373,10 @@ class _SequenceRunner:
 
         was_training = self.net.training
         writer = FrameWriter(self.device, png_filter=png_filter, png_deflate=png_deflate) if out_dir is not None else None
+        vwriter = None
+        if video is not None:
+            vwriter = VideoWriter(self.device, video, video_fps, video_quality, video_subsampling, jpeg_pitch)
+        self.video_paths = None
         kept = []
         self.net.eval()
         try:
@@ -382,6 +394,8 @@ class _SequenceRunner:
                     if writer is not None:
                         paths = [p for i in range(len(chunk)) for p in self._paths(out_dir, names[base + i], u8[i])]
                         writer.dump([(u8.view(-1, H, W, 3), paths)])
+                    if vwriter is not None:
+                        vwriter.add(self._video_frames(u8, pairs, base, len(chunk), video_keys).view(-1, H, W, 3))
                     if niqe is not None:
                         sums = niqe_mod.moments(u8.view(-1, H, W, 3), niqe)
                         if sums_pin is None:
@@ -411,8 +425,13 @@ class _SequenceRunner:
         finally:
             self.net.train(was_training)
             cur.wait_stream(side)
-            if writer is not None:
-                writer.close()
+            try:
+                if writer is not None:
+                    writer.close()
+            finally:
+                if vwriter is not None:
+                    vwriter.close()
+                    self.video_paths = vwriter.paths
         if niqe is not None:
             cur.synchronize()                  # the last sums have arrived
             scores = niqe_mod.finish(sums_pin.numpy(), niqe)
@@ -426,6 +445,21 @@ class _SequenceRunner:
             self.scores = [(names[i // each], i % each, Scores(*(None if col is None else col[i] for col in sc)))
                            for i in range(scored)]
         return torch.cat(kept, dim=0).cpu().numpy() if keep else None
+
+    def _video_frames(self, u8, pairs, base, count, keys):
+        """The frames of a minibatch as they enter the video: the outputs in order; with ``keys`` pair k's left key frame
+        (resident, RGB) in front of its outputs, and its right key frame behind them unless the next pair starts on it."""
+        if not keys:
+            return u8
+        resident = self.assembler.frames
+        key = lambda i: resident[i:i + 1].flip(-1) if self.assembler.bgr else resident[i:i + 1]      # noqa: E731
+        parts = []
+        for i in range(count):
+            p = pairs[base + i]
+            parts += [key(p[0]), u8[i].reshape(-1, *u8.shape[-3:])]
+            if base + i + 1 >= len(pairs) or pairs[base + i + 1][0] != p[1]:
+                parts.append(key(p[1]))
+        return torch.cat(parts, dim=0)
 
 
 class SequenceInterpolator(_SequenceRunner):
@@ -446,7 +480,8 @@ class SequenceInterpolator(_SequenceRunner):
         self.stream = torch.cuda.Stream(device=self.device)
 
     def run(self, frames, events, pairs, out_dir=None, names=None, keep=False, bgr=False, niqe=None, png_filter="none",
-            png_deflate="host", gt=None, score=None):
+            png_deflate="host", gt=None, score=None, video=None, video_fps=30, video_quality=90, video_subsampling="420",
+            video_keys=None, jpeg_pitch=None):
         """``frames`` uint8 (N, H, W, 3), ``events`` float32 (E, 4), ``pairs`` from ``make_pairs``.  With ``out_dir`` frame f
         of pair k goes to ``{out_dir}/{names[k]}_{f:02d}.png`` (default name: the left key frame's index, six digits, as
         the validation dumps are named).  ``keep=True`` returns the uint8 frames (P, T, H, W, 3) on the host, else None.
@@ -454,8 +489,16 @@ class SequenceInterpolator(_SequenceRunner):
         'adaptive' (``validation.FrameWriter``): the same pixels in smaller files.  ``png_deflate``: 'host' or 'device'
         (the PNGs' zlib streams come from the GPU, ``ops.png_deflate``): the same pixels again.  ``gt`` / ``score``: ground
         truth to score the outputs against (``_SequenceRunner``): a directory of ``{names[k]}_{f:02d}.png`` or the uint8
-        frames; ``scores`` then holds (name, f, ``score.Scores``) per output frame."""
-        return super().run(frames, events, pairs, out_dir, names, keep, bgr, niqe, png_filter, png_deflate, gt, score)
+        frames; ``scores`` then holds (name, f, ``score.Scores``) per output frame.
+        ``video``: a path; the output frames then also go, in output order, into one Motion-JPEG AVI file there
+        (``validation.VideoWriter``: baseline JPEG frames from the GPU, csrc/jpeg.hip; ``video_paths`` lists the file and
+        its parts) -- independent of ``out_dir``: either, both or neither.  ``video_fps``, ``video_quality`` 1 .. 100,
+        ``video_subsampling`` '420' or '444', ``jpeg_pitch`` as ``VideoWriter`` takes it.  ``video_keys``: the resident key
+        frames enter the video too (default: yes for layout 'sharp', no otherwise; True elsewhere raises) -- pair k's left
+        key frame in front of its outputs, its right key frame behind them when the next pair does not start on it or
+        there is none -- so that a run of consecutive pairs is a gap-free slow-motion clip."""
+        return super().run(frames, events, pairs, out_dir, names, keep, bgr, niqe, png_filter, png_deflate, gt, score, video,
+                           video_fps, video_quality, video_subsampling, video_keys, jpeg_pitch)
 
     def _forward(self, batch):
         return self.net(x=batch["lq"], event=batch["voxel"])
@@ -490,13 +533,16 @@ class SequenceDeblurrer(_SequenceRunner):
         self.stream = torch.cuda.Stream(device=self.device)
 
     def run(self, frames, events, items, out_dir=None, names=None, keep=False, bgr=False, niqe=None, png_filter="none",
-            png_deflate="host", gt=None, score=None):
+            png_deflate="host", gt=None, score=None, video=None, video_fps=30, video_quality=90, video_subsampling="420",
+            jpeg_pitch=None):
         """``frames`` uint8 (N, H, W, 3), ``events`` float32 (E, 4), ``items`` from ``make_pairs(t, *frame_windows(...))``.
         With ``out_dir`` item k goes to ``{out_dir}/{names[k]}.png`` (default name: the frame index, six digits).
         ``keep=True`` returns the uint8 frames (P, H, W, 3) on the host, else None.
         ``niqe``: a ``NiqeModel``; ``niqe_scores`` then holds (name, 0, score) per output frame.  ``png_filter``: as for
-        ``SequenceInterpolator.run``.  ``gt`` / ``score``: as there, the directory holding ``{names[k]}.png``."""
-        return super().run(frames, events, items, out_dir, names, keep, bgr, niqe, png_filter, png_deflate, gt, score)
+        ``SequenceInterpolator.run``.  ``gt`` / ``score``: as there, the directory holding ``{names[k]}.png``.  ``video`` and
+        its options: as there, the deblurred frames in order (no key frames)."""
+        return super().run(frames, events, items, out_dir, names, keep, bgr, niqe, png_filter, png_deflate, gt, score, video,
+                           video_fps, video_quality, video_subsampling, None, jpeg_pitch)
 
     def _forward(self, batch):
         if self.crop_size is None:
