@@ -152,7 +152,11 @@ typedef struct refid_conv_desc {
     int wino_tile;                              /* algo 5: 0 = the library chooses between the 64- and the 32-output-channel
                                                    workgroup tile; 1 = the 64-channel tile wherever cout > 32; 4 = the
                                                    32-channel tile everywhere (an A/B switch: measured 9-35 % slower on the
-                                                   64-channel layers).  Same results whichever runs.  (2 / 3 selected tiles
+                                                   64-channel layers); 5 = the library's choice of tile as under 0, but a
+                                                   plan of exactly two K ranges (split_k) runs as two launch rows + the
+                                                   finishing pass through `ws` instead of as the two four-wave groups of one
+                                                   512-thread workgroup per tile (the routing before that form existed: an
+                                                   A/B switch).  Same results whichever runs.  (2 / 3 selected tiles
                                                    that were removed with ABI 9 -- a persistent and a wide one, both measured
                                                    slower -- and are ignored.)                                          */
     const refid_pw_extras* pw;                  /* algo 3 only: fusions around the pointwise conv, or NULL               */

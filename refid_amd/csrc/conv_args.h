@@ -49,6 +49,9 @@ int refid_launch_wino3x3(const ConvKArgs& a, float* ws, size_t ws_bytes, int spl
 // conv_wino6.hip: Winograd F(2x2,3x3) with six bf16 products per fp32 product (algo 5)
 bool refid_wino6_eligible(const ConvKArgs& a);
 size_t refid_wino6_workspace_bytes(const ConvKArgs& a, int split_mode);
+// the plan of a call, for host checks (tools/probes/wino6_route_host_check.cpp): K ranges | 32-channel column tiles per wave << 8 |
+// K groups per workgroup << 16 (2 = the in-group split: both K ranges in one launch, no workspace, no finishing pass)
+int refid_wino6_route(const ConvKArgs& a, int split_mode, int tile_hint);
 // terms: 0 / 6 = six bf16 products (three planes per operand), 3 = three fp16 products (two planes, scaled operands),
 //        1 = one fp16 product (one plane, the same scaling)
 int refid_launch_wino6(const ConvKArgs& a, float* ws, size_t ws_bytes, int split_mode, int tile_hint, int terms, hipStream_t st);

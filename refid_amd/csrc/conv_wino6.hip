@@ -49,6 +49,8 @@
 //     16-byte buffer load, a wave reads 1 KB contiguous; fragments of column j+1 are requested before column j's MFMAs
 //     (two register sets), never through LDS.
 //   * the raw halo of chunk c+2 is requested at the top of chunk c (global -> VGPR -> LDS, double buffered).
+//   * split-K (small grids): K ranges over grid.y into partial outputs + wino_splitk_finish_kernel -- except for exactly TWO
+//     ranges, which run as the two four-wave groups of one 512-thread workgroup (template parameter KG = 2, below).
 #include "common.h"
 #include "conv_args.h"
 #include "conv_epilogue.h"
@@ -83,20 +85,29 @@ constexpr int F16_E0 = F16_TGT + 1;     // initial (biased) reference exponent: 
 //         split feeds 6 instead of 12 MFMAs, so this form is vector-issue bound -- and still well ahead of 64 fp32 MFMAs.
 // F16: the three-fp16-product form (two planes per operand, online power-of-two scaling: see the top of the file)
 // ONE (with F16): its one-product form -- one fp16 plane per operand, no residual split
-template <int NT, bool F16, bool ONE = false>
-__global__ __launch_bounds__(256, NT == 2 ? 2 : 3) void conv_wino6_kernel(const ConvKArgs a) {
+// KG = 2: in-group split-K (a plan with exactly two K ranges).  One workgroup of 512 threads per output tile; waves 0-3 reduce
+//         the K range blockIdx.y = 0 of the grid split would, waves 4-7 the range of blockIdx.y = 1, each group on its own raw halo
+//         buffers and its own exchange region (2 x lds_bytes: one workgroup per CU with the LDS two have under the grid split).  The
+//         epilogue adds the two groups' output tiles in the finishing kernel's order and applies the fused epilogue itself: no
+//         partial outputs, no finishing launch, the grid split's bits.
+template <int NT, bool F16, bool ONE = false, int KG = 1>
+__global__ __launch_bounds__(256 * KG, NT == 2 ? 2 : 3) void conv_wino6_kernel(const ConvKArgs a) {
     constexpr int BN = 32 * NT;
+    static_assert(KG == 1 || KG == 2, "K groups per workgroup");
     static_assert(F16 || !ONE, "the one-product form is an fp16 form");
     constexpr int NPL = ONE ? 1 : (F16 ? 2 : 3);            // planes per operand
     constexpr int NPR = ONE ? 1 : ((REFID_WINO6_ABLATE == 14 || REFID_WINO6_ABLATE == 15) ? 3 : (F16 ? 3 : 6));   // products kept
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    f32x4* sR = reinterpret_cast<f32x4*>(smem);            // two raw halo buffers
+    // K group of this wave (wave-uniform: kept scalar) and the thread's index within its group
+    const int grp = KG == 2 ? __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 8) : 0;
+    f32x4* sR = reinterpret_cast<f32x4*>(smem + grp * lds_bytes(NT));   // two raw halo buffers (per group)
 
-    const int tid = threadIdx.x;
+    const int tid = KG == 2 ? (threadIdx.x & 255) : threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
     const int li = lane & 31, kh = lane >> 5;
     const int ti = wave;                                   // transform row i owned by this wave (xi = 4i .. 4i+3)
-    if (REFID_WINO6_ABLATE == 20 && a.N > 0) return;       // (every workgroup leaves at once, registers / LDS as the product: dispatch only)
+    // (every workgroup leaves at once, registers / LDS as the product: dispatch only; 22 / 23: of half the grid, see the launcher)
+    if ((REFID_WINO6_ABLATE == 20 || REFID_WINO6_ABLATE == 22 || REFID_WINO6_ABLATE == 23) && a.N > 0) return;
     if (REFID_WINO6_ABLATE == 21 && a.N > 0) { __syncthreads(); if (tid == 12345) a.out[0] = 1.f; return; }   // + one barrier
 
 #if defined(REFID_WINO6_ABLATE) && (REFID_WINO6_ABLATE == 9 || REFID_WINO6_ABLATE == 11)
@@ -152,7 +163,7 @@ __global__ __launch_bounds__(256, NT == 2 ? 2 : 3) void conv_wino6_kernel(const 
     }
     // split-K (small grids only): this workgroup reduces chunks [kc0, kc1) and writes a raw partial output
     const int kper = (a.nchunks + a.ksplit - 1) / a.ksplit;
-    const int kc0 = blockIdx.y * kper, kc1 = min(a.nchunks, kc0 + kper);
+    const int kc0 = (KG == 2 ? grp : (int)blockIdx.y) * kper, kc1 = min(a.nchunks, kc0 + kper);
 
     f32x4 rr[R_ITEMS];
     // chunks past kc1 are requested with out-of-range offsets (zeros, no memory traffic): no branches around loads,
@@ -165,7 +176,8 @@ __global__ __launch_bounds__(256, NT == 2 ? 2 : 3) void conv_wino6_kernel(const 
     // instruction count, no bandwidth), 13 = half the U loads (column tile 1 reuses tile 0's fragments), 14 = three products on
     // two planes (the MFMA / U-byte count of a two-plane fp16 form), 15 = 14 without the split; fp16 form (WINO6_TERMS=3):
     // 16 = no max / rescale / scale, 17 = a one-instruction max, 18 = no split, 19 = the prologue's halo loads from a cache-resident
-    // tile, 20 = every workgroup returns at once (dispatch cost of the grid), 21 = 20 + one barrier.  Never in the product.
+    // tile, 20 = every workgroup returns at once (dispatch cost of the grid), 21 = 20 + one barrier, 22 = 20 with half the
+    // workgroups, 23 = 20 with half the workgroups of 512 threads.  Never in the product.
     auto load_raw = [&](int ch, f32x4 (&dst)[R_ITEMS]) {
         const int c0 = (REFID_WINO6_ABLATE == 5 ? 0 : ch) * KC;   // chunk-uniform source: Ca % 16 == 0 for two sources
         const bool fromA = c0 < a.Ca;
@@ -329,13 +341,15 @@ __global__ __launch_bounds__(256, NT == 2 ? 2 : 3) void conv_wino6_kernel(const 
 
     if (REFID_WINO6_ABLATE != 3 && REFID_WINO6_ABLATE != 10)
         for (int ch = kc0; ch < kc1; ++ch) phase(ch);
+    if constexpr (KG == 2)                                 // the group with the shorter K range keeps the workgroup's barrier count
+        for (int i = max(kc1 - kc0, 0); i < kper; ++i) __syncthreads();
 
     // ---- output transform (as conv_wino.hip) -----------------------------------------------------------------
     // lane: tile li, channels (r&3)+8(r>>2)+4kh of a 32-channel tile;  acc[j][t] = M[i][j]
     //   R_i[b] = sum_j M[i][j] A[j][b] :  b=0: M0+M1+M2   b=1: M1-M2-M3          (in registers)
     //   Y[a][b] = sum_i A^T[a][i] R_i[b]:  a=0: R0+R1+R2   a=1: R1-R2-R3          (across the 4 waves, through LDS)
     constexpr int XL = 66;
-    f32x4* xch = reinterpret_cast<f32x4*>(smem);
+    f32x4* xch = reinterpret_cast<f32x4*>(smem + grp * lds_bytes(NT));
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll
@@ -360,13 +374,18 @@ __global__ __launch_bounds__(256, NT == 2 ? 2 : 3) void conv_wino6_kernel(const 
     // one 64-bit base per tensor and thread plus workgroup-uniform steps (a generic (n, oy, ox) -> offset product per item
     // was 160 quarter-rate integer multiplies per tile -- as much vector-issue time as the K loop at 64 input channels).
     constexpr int QUADS = BN / 4, PPT = 256 / QUADS, CPR = TW / PPT;        // 16 / 16 / 2   or   8 / 32 / 1
-    constexpr int NIT = TH * CPR;                                           // 8 or 4
+    // KG = 2: the 512 threads share the tile's items -- group g takes output rows 2g, 2g + 1 (the Winograd tile row g) of BOTH
+    // groups' exchange regions.
+    constexpr int NIT = TH * CPR / KG;                                      // 8 or 4 (KG = 2: 4 or 2)
     static_assert(TW == 32 && (NT == 1 || NT == 2) && PPT * CPR == TW, "epilogue item mapping");
     constexpr int TI_STRIDE = 2 * NT * 4 * XL;             // exchange slots between transform rows i and i + 1
+    constexpr bool INGROUP = KG == 2;
+    const bool part = !INGROUP && a.ksplit > 1;            // this launch writes a raw partial output (grid split)
+    const int row0 = INGROUP ? 2 * grp : 0;                // first output row of this thread's items
     const int p0 = tid / QUADS, c = (tid % QUADS) * 4;
     const int j0 = n0 + c;
     const int nt = c >> 5, rq = (c & 31) >> 3, ckh = (c & 7) >> 2;
-    const long long opb = (long long)(n * a.Ho + oy0) * a.Wo + ox0 + p0;
+    const long long opb = (long long)(n * a.Ho + oy0 + row0) * a.Wo + ox0 + p0;
     const bool jok = j0 < a.Cout;
     const bool vec = a.vecOK && (j0 + 3 < a.Cout);
     bool cok[CPR];
@@ -374,13 +393,13 @@ __global__ __launch_bounds__(256, NT == 2 ? 2 : 3) void conv_wino6_kernel(const 
     for (int q2 = 0; q2 < CPR; ++q2) cok[q2] = ox0 + q2 * PPT + p0 < a.Wo;
     // out (or this K range's partial output), residual, mask and the second output out2 = out + add2 (a skip sum leaves with the
     // tile; the finishing pass writes it under split-K): the same item addressing for all of them
-    const EpiSteps epi(a, a.out + (a.ksplit > 1 ? blockIdx.y * a.wsStride : 0), opb, j0, a.Wo, PPT, a.ksplit == 1);
-    const bool pre = REFID_WINO6_ABLATE != 4 && REFID_WINO6_ABLATE != 10 && vec && a.ksplit == 1 && (a.res != nullptr || a.mask != nullptr);
+    const EpiSteps epi(a, a.out + (part ? blockIdx.y * a.wsStride : 0), opb, j0, a.Wo, PPT, !part);
+    const bool pre = REFID_WINO6_ABLATE != 4 && REFID_WINO6_ABLATE != 10 && vec && !part && (a.res != nullptr || a.mask != nullptr);
     f32x4 pres[NIT], pmask[NIT];
     if (pre) {
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
-            const bool ok = (oy0 + it / CPR < a.Ho) && cok[it % CPR];
+            const bool ok = (oy0 + row0 + it / CPR < a.Ho) && cok[it % CPR];
             pres[it] = f32x4{0.f, 0.f, 0.f, 0.f};
             pmask[it] = f32x4{1.f, 1.f, 1.f, 1.f};
             if (ok && a.res) pres[it] = epi_load4(epi.at(EPI_RES, it / CPR, it % CPR));
@@ -388,23 +407,30 @@ __global__ __launch_bounds__(256, NT == 2 ? 2 : 3) void conv_wino6_kernel(const 
         }
     }
     f32x4 bv = {0.f, 0.f, 0.f, 0.f};                        // the same four output channels for all of a thread's items
-    if (a.ksplit == 1 && jok) bv = epi_bias4(a, a.coBase + j0, j0, vec);
+    if (!part && jok) bv = epi_bias4(a, a.coBase + j0, j0, vec);
     __syncthreads();
 
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
         const int row = it / CPR, colb = it % CPR;
         const int col = colb * PPT + p0;
-        const int oa = row & 1, tile = ((row & 3) >> 1) * 16 + (col >> 1), ob = col & 1;
-        if (oy0 + row >= a.Ho || !cok[colb] || !jok) continue;
-        const f32x4* xp = xch + (((oa * 2 + ob) * NT + nt) * 4 + rq) * XL + ckh * 33 + tile;   // row i0 = oa
+        const int oa = row & 1, tile = (((row0 + row) & 3) >> 1) * 16 + (col >> 1), ob = col & 1;
+        if (oy0 + row0 + row >= a.Ho || !cok[colb] || !jok) continue;
+        const int xo = (((oa * 2 + ob) * NT + nt) * 4 + rq) * XL + ckh * 33 + tile;            // row i0 = oa
+        const f32x4* xp = (INGROUP ? reinterpret_cast<const f32x4*>(smem) : xch) + xo;         // (in-group split: K group 0's region)
         const float sg = oa ? -1.f : 1.f;                   // a=0: R0+R1+R2 ; a=1: R1-R2-R3
         f32x4 v = xp[0] + (xp[TI_STRIDE] + xp[2 * TI_STRIDE]) * sg;
-        if (a.ksplit > 1) {                                 // raw partial sums; the finishing pass applies the epilogue
+        if (part) {                                         // raw partial sums; the finishing pass applies the epilogue
             *reinterpret_cast<f32x4*>(epi.at(EPI_OUT, row, colb)) = v;
             continue;
         }
-        v += bv;
+        if constexpr (INGROUP) {
+            // the finishing kernel's arithmetic (conv_wino.hip): partial 0 + partial 1, and no zero bias quad on the 16-byte path
+            const f32x4* xq = reinterpret_cast<const f32x4*>(smem + lds_bytes(NT)) + xo;
+            v += xq[0] + (xq[TI_STRIDE] + xq[2 * TI_STRIDE]) * sg;
+            if (!vec || a.bias) v += bv;
+        } else
+            v += bv;
         epi_pre(a, v);
         if (REFID_WINO6_ABLATE == 4 || REFID_WINO6_ABLATE == 10) {
             if (v[0] == 12345.678f) epi.at(EPI_OUT, row, colb)[0] = v[1];
@@ -414,11 +440,15 @@ __global__ __launch_bounds__(256, NT == 2 ? 2 : 3) void conv_wino6_kernel(const 
     }
 }
 
-struct Wino6Plan { int ks; int nt; dim3 grid; };
+// kg: K groups per workgroup -- 2 = the in-group split (ks == 2 in one launch of 512-thread workgroups, no workspace)
+struct Wino6Plan { int ks; int nt; dim3 grid; int kg; };
+constexpr int HINT_PARENT = 5;           // refid_conv_desc.wino_tile 5: the routing before the in-group split (A/B switch)
 
 // same small-grid policy as the fp32 tile (conv_wino.hip::wino_plan), in chunks of 16 channels
 Wino6Plan wino6_plan(ConvKArgs& a, int split_mode, int tile_hint = 0) {
     Wino6Plan p;
+    const bool parent = tile_hint == HINT_PARENT;          // the library's choice, minus the in-group split
+    if (parent) tile_hint = 0;
     // (tile_hint 4, an experiment switch: the 32-channel form for every layer -- three instead of two workgroups per CU,
     //  twice the V transforms / splits per product)
     p.nt = (a.Cout > 32 && tile_hint != 4) ? 2 : 1;
@@ -443,25 +473,45 @@ Wino6Plan wino6_plan(ConvKArgs& a, int split_mode, int tile_hint = 0) {
     p.grid = dim3(round_up(a.tilesX * a.tilesY * a.N, 8) * a.ncot);
     const int nwg = (split_mode == 2) ? (int)p.grid.x : a.tilesX * a.tilesY * a.ncot * 8;   // "sample": as if N = 8
     p.ks = split_mode ? refid_splitk_count(nwg, a.nchunks, 256, 8, 4) : 1;
+    // Exactly two K ranges: both run as the two four-wave groups of one workgroup (as many waves per CU as the split grid had) and
+    // meet in LDS -- no partial outputs, no finishing launch, the same bits.  Other counts keep the grid split and its bits.
+    p.kg = (p.ks == 2 && !parent) ? 2 : 1;
     return p;
 }
 
-template <int NT, bool F16, bool ONE = false>
+template <int NT, bool F16, bool ONE = false, int KG = 1>
 int launch_wino6_t(const ConvKArgs& a, dim3 grid, hipStream_t st, const char* what) {
     static std::atomic<unsigned long long> done{0};
-    if (int rc = refid_lds_attr_once(done, &conv_wino6_kernel<NT, F16, ONE>, lds_bytes(NT), "conv_wino6")) return rc;
-    hipLaunchKernelGGL((conv_wino6_kernel<NT, F16, ONE>), grid, dim3(256), lds_bytes(NT), st, a);
+#if REFID_WINO6_ABLATE == 22 || REFID_WINO6_ABLATE == 23
+    // dispatch only, HALF as many workgroups: 22 = of 256 threads, 23 = of 512 threads with the in-group form's registers and LDS
+    // (is the dispatch cost of a grid per workgroup or per wave?)
+    constexpr int G = REFID_WINO6_ABLATE == 23 ? 2 : KG;
+    constexpr auto kernel = &conv_wino6_kernel<NT, F16, ONE, G>;
+    static std::atomic<unsigned long long> doneh{0};
+    if (int rc = refid_lds_attr_once(doneh, kernel, G * lds_bytes(NT), "conv_wino6")) return rc;
+    hipLaunchKernelGGL(kernel, dim3((grid.x + 1) / 2, grid.y), dim3(256 * G), G * lds_bytes(NT), st, a);
+#else
+    constexpr auto kernel = &conv_wino6_kernel<NT, F16, ONE, KG>;
+    if (int rc = refid_lds_attr_once(done, kernel, KG * lds_bytes(NT), "conv_wino6")) return rc;
+    hipLaunchKernelGGL(kernel, grid, dim3(256 * KG), KG * lds_bytes(NT), st, a);
+#endif
     REFID_LAUNCH_CHECK(what);
     return 0;
 }
 
-template <int NT>
+template <int NT, int KG = 1>
 int launch_wino6(const ConvKArgs& a, int terms, dim3 grid, hipStream_t st, const char* what) {
-    if (terms == 1) return launch_wino6_t<NT, true, true>(a, grid, st, what);
-    return terms == 3 ? launch_wino6_t<NT, true>(a, grid, st, what) : launch_wino6_t<NT, false>(a, grid, st, what);
+    if (terms == 1) return launch_wino6_t<NT, true, true, KG>(a, grid, st, what);
+    return terms == 3 ? launch_wino6_t<NT, true, false, KG>(a, grid, st, what) : launch_wino6_t<NT, false, false, KG>(a, grid, st, what);
 }
 
 }  // namespace
+
+int refid_wino6_route(const ConvKArgs& ka, int split_mode, int tile_hint) {
+    ConvKArgs a = ka;
+    const Wino6Plan p = wino6_plan(a, split_mode, tile_hint);
+    return p.ks | p.nt << 8 | p.kg << 16;
+}
 
 bool refid_wino6_eligible(const ConvKArgs& a) {
     const long long lim = 0x7fffffffLL;
@@ -474,6 +524,7 @@ bool refid_wino6_eligible(const ConvKArgs& a) {
 
 size_t refid_wino6_workspace_bytes(const ConvKArgs& ka, int split_mode) {
     size_t need = 0;
+    // (the in-group split needs none, but wino_tile 5 -- the same plan on the grid split -- does: the parent's byte counts stand)
     for (int hint : {0, 1, 4}) {                           // any tile form may be asked for (wino_tile): the largest need
         ConvKArgs a = ka;
         const Wino6Plan p = wino6_plan(a, split_mode, hint);
@@ -496,6 +547,10 @@ int refid_launch_wino6(const ConvKArgs& ka, float* ws, size_t ws_bytes, int spli
     //  and was removed in round 6: DESIGN.md section 7)
     const Wino6Plan pl = wino6_plan(a, ws ? split_mode : 0, tile_hint);
     if (pl.ks == 1) return pl.nt == 2 ? launch_wino6<2>(a, terms, pl.grid, st, "conv_wino6") : launch_wino6<1>(a, terms, pl.grid, st, "conv_wino6/32");
+    if (pl.kg == 2) {                                      // in-group split: the epilogue runs in the tile, the workspace stays untouched
+        a.ksplit = 2;
+        return pl.nt == 2 ? launch_wino6<2, 2>(a, terms, pl.grid, st, "conv_wino6/ingroup") : launch_wino6<1, 2>(a, terms, pl.grid, st, "conv_wino6/32/ingroup");
+    }
     const dim3 grid(pl.grid.x, pl.ks);
     return refid_launch_splitk("conv_wino6", a, pl.ks, (long long)a.N * a.Ho * a.Wo, ws, ws_bytes, [&](const ConvKArgs& p) {
         return pl.nt == 2 ? launch_wino6<2>(p, terms, grid, st, "conv_wino6/splitk") : launch_wino6<1>(p, terms, grid, st, "conv_wino6/32/splitk");

@@ -21,7 +21,8 @@ ROLE_FWD, ROLE_DGRAD, ROLE_CONVT, ROLE_CONVT_DGRAD, ROLE_DOWN_DGRAD, ROLE_WINO_F
 WINO_SPLIT = {"0": 0, "s": 1}.get(os.environ.get("REFID_SPLITK", os.environ.get("REFID_WINO_SPLITK", "auto"))[:1], 2)
 
 # Winograd x six / x three tile selection (refid_conv_desc.wino_tile): 0 = by problem size, 1 = the 64-channel tile wherever
-# cout > 32, 4 = the 32-channel tile everywhere (A/B switches)
+# cout > 32, 4 = the 32-channel tile everywhere, 5 = as 0 with two K ranges on the grid split + finishing pass instead of inside
+# one workgroup (A/B switches)
 WINO_TILE = int(os.environ.get("REFID_WINO_TILE", "0"))
 
 # bench.py's roofline leg: when PROFILE is a list, conv2d()/conv2d_wgrad() bracket each launch with

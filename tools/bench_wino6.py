@@ -2,7 +2,14 @@
 """fp32 Winograd tile (algo 1) vs Winograd x six bf16 products (algo 5) vs Winograd x three fp16 products (algo 5, terms 3) vs
 Winograd x ONE fp16 product (algo 5, terms 1: compute_dtype 'fp16') vs the bf16 one-product direct tile (algo 4, terms 1:
 compute_dtype 'bf16'; single-source layers only, as in the engine) at the config-2 shapes (B=8): time and -- on a small crop --
-the largest deviation of each from the float64 convolution."""
+the largest deviation of each from the float64 convolution.
+
+  python tools/bench_wino6.py               the table above
+  python tools/bench_wino6.py ab [B ...]    the routing before the in-group split-K (wino_tile 5: two launch rows + finishing pass)
+                                            and the library's choice (wino_tile 0) on the three-fp16-product form, ALTERNATING in
+                                            one process: ROUNDS (5) timings per layer and form, median and min..max, results
+                                            compared bit for bit.  Layers: the 32-channel shapes and the bottleneck conv, whose plan
+                                            has two K ranges at B=8; at the batch sizes given (default 8 1 2) every split layer."""
 import os
 import sys
 
@@ -60,7 +67,52 @@ def one(name, H, Ca, Cb, Co, res=False, mask=False):
           f"x3 {e3:.1e}  x1 {eh:.1e}", flush=True)
 
 
+AB_SHAPES = [   # name, H, Ca, Cb, Co, res + mask
+    ("D2 res 32->32 @256", 256, 32, 0, 32, False), ("D2 res dgrad 32->32 +res+mask", 256, 32, 0, 32, True),
+    ("L0 first dgrad 64->32 @256", 256, 64, 0, 32, False), ("D2 main.0 64->32 +res+mask", 256, 32, 32, 32, True),
+    ("bottleneck 256->256 @32", 32, 256, 0, 256, False), ("bottleneck dgrad +res+mask", 32, 256, 0, 256, True),
+    ("L2 res 256->256 @64", 64, 256, 0, 256, False), ("L2 main.0 512->256 @64", 64, 256, 256, 256, False),
+    ("L1 res 128->128 @128", 128, 128, 0, 128, False),
+]
+
+
+def run_ab(batches):
+    import statistics
+    rounds = int(os.environ.get("ROUNDS", 5))
+    print(f"# x3 fp16, rounds={rounds}: us per call, median (min..max); grid = wino_tile 5 (grid split + finishing pass), "
+          f"group = wino_tile 0 (in-group split where the plan has two K ranges); ws = the grid form wrote the workspace")
+    for nb in batches:
+        for name, H, Ca, Cb, Co, rm in AB_SHAPES:
+            torch.manual_seed(1)
+            Ci = Ca + Cb
+            a = torch.randn(nb, H, H, Ca, device="cuda")
+            b = torch.randn(nb, H, H, Cb, device="cuda") if Cb else None
+            w = torch.randn(Co, Ci, 3, 3, device="cuda") * (1.0 / (Ci * 9) ** 0.5)
+            r = torch.randn(nb, H, H, Co, device="cuda") if rm else None
+            m = torch.randn(nb, H, H, Co, device="cuda") if rm else None
+            kw = dict(kh=3, kw=3, pad=1, cout=Co, cout_pad=-(-Co // 64) * 64, in_b=b, bias=torch.randn(Co, device="cuda"),
+                      slope_pre=0.1, res=r, mask=m, slope_mask=0.2 if rm else 1.0, algo=5, terms=3)
+            w3 = ops.pack_conv_weights_wino6(w, ops.ROLE_WINO_FWD, Co, Ci, f16=True)
+            outs = {t: torch.empty(nb, H, H, Co, device="cuda") for t in (5, 0)}
+            times = {5: [], 0: []}
+            ws = ops._workspace(64 << 20, a.device, "conv")
+            ws.fill_(-12345.0)
+            for _ in range(rounds):
+                for t in (5, 0):
+                    ops.WINO_TILE = t
+                    times[t].append(timeit(lambda: ops.conv2d(a, w3, outs[t], **kw), iters=20) * 1e6)
+            split = not bool((ws == -12345.0).all())
+            ops.WINO_TILE = 0
+            m5, m0 = statistics.median(times[5]), statistics.median(times[0])
+            print(f"B={nb} {name:30s} grid {m5:7.1f} ({min(times[5]):7.1f}..{max(times[5]):7.1f})  group {m0:7.1f} "
+                  f"({min(times[0]):7.1f}..{max(times[0]):7.1f})  group/grid {m0 / m5:5.3f}  ws {'yes' if split else 'no '}  "
+                  f"bits {'equal' if torch.equal(outs[5], outs[0]) else 'DIFFER'}", flush=True)
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "ab":
+        run_ab([int(v) for v in sys.argv[2:]] or [8, 1, 2])
+        sys.exit(0)
     one("L0 first dgrad 64->32.. skip", 256, 64, 0, 64)
     one("L0 main.0 128->64 @256", 256, 64, 64, 64)
     one("L0 res 64->64 @256", 256, 64, 0, 64)
@@ -80,3 +132,4 @@ if __name__ == "__main__":
     one("D2 res 32->32 @256 +res", 256, 32, 0, 32, res=True)
     one("D2 res dgrad +res +mask", 256, 32, 0, 32, res=True, mask=True)
     one("L0 first dgrad 64->32 @256", 256, 64, 0, 32)
+    one("L0 first dgrad 64->32 +res +mask", 256, 64, 0, 32, res=True, mask=True)

@@ -32,8 +32,9 @@ def norm(name):
 def algo_key(k):
     """rocprof kernel name -> name used by refid_amd.ops.PROFILE (tools/profile_step.py)."""
     if k.startswith("conv_wino6_kernel"):
-        # <NT, F16, ONE>: ops.PROFILE names "<NT>" / "<NT, true>" / "<NT, true, fp16x1>"
-        m = re.match(r"conv_wino6_kernel<(\d+)(?:, (true|false))?(?:, (true|false))?>", k)
+        # <NT, F16, ONE, KG>: ops.PROFILE names "<NT>" / "<NT, true>" / "<NT, true, fp16x1>" (KG = 2, the in-group split-K
+        # form, is priced with the tile it is a form of)
+        m = re.match(r"conv_wino6_kernel<(\d+)(?:, (true|false))?(?:, (true|false))?(?:, \d+)?>", k)
         if not m: return "conv_wino6_kernel<2>"
         if m.group(3) == "true": return f"conv_wino6_kernel<{m.group(1)}, true, fp16x1>"
         return f"conv_wino6_kernel<{m.group(1)}, true>" if m.group(2) == "true" else f"conv_wino6_kernel<{m.group(1)}>"
