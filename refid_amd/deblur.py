@@ -15,7 +15,7 @@ the output frames) scores every output frame against ground truth while it is on
 import sys
 
 from .interpolate import load_frames, load_frames_resident, png_deflate_setting, png_filter_setting, write_niqe  # noqa: F401  (for other callers)
-from .interpolate import load_inputs, load_network, parser, run_and_report, video_settings
+from .interpolate import load_inputs, load_network, parsed_opt, parser, run_and_report, video_settings
 
 
 def settings(args):
@@ -23,8 +23,7 @@ def settings(args):
     the explicit arguments."""
     net, ckpt, bins, mb, crop = None, None, None, None, None
     if args.opt:
-        from .options import parse
-        opt = parse(args.opt, is_train=False)
+        opt = parsed_opt(args)
         net = dict(opt["network_g"])
         ckpt = opt.get("path", {}).get("pretrain_network_g")
         bins = opt.get("datasets", {}).get("test", {}).get("num_bins")

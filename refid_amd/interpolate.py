@@ -72,12 +72,19 @@ def write_niqe(out_dir, files, scores):
     return mean
 
 
+def parsed_opt(args):
+    """The options of ``--opt``, parsed once per ``args`` however many settings are read from them; {} without ``--opt``."""
+    if getattr(args, "parsed_opt", None) is None:
+        from .options import parse
+        args.parsed_opt = parse(args.opt, is_train=False) if args.opt else {}
+    return args.parsed_opt
+
+
 def settings(args):
     """(network options, checkpoint path or None, m, n, layout) from --opt, overridden by the explicit arguments."""
     net, ckpt, m, n, layout = None, None, 1, None, None
     if args.opt:
-        from .options import parse
-        opt = parse(args.opt, is_train=False)
+        opt = parsed_opt(args)
         net = dict(opt["network_g"])
         ckpt = opt.get("path", {}).get("pretrain_network_g")
         ds = opt.get("datasets", {}).get("test", {})
@@ -94,37 +101,29 @@ def settings(args):
     return net, ckpt, int(m), int(n), layout
 
 
+def _val_setting(args, flag, key, check):
+    """The command line's ``flag`` (an attribute of ``args``), else ``val.<key>`` of ``--opt`` through ``check``, whose default
+    stands for an absent key or no ``--opt``; a bad value in the file exits with ``check``'s message."""
+    from ._lib import RefidHipError
+    if getattr(args, flag) is not None:
+        return getattr(args, flag)
+    try:
+        return check((parsed_opt(args).get("val") or {}).get(key), f"--opt: val.{key}")
+    except RefidHipError as ex:
+        raise SystemExit(str(ex))
+
+
 def png_filter_setting(args):
     """``--png-filter``, else ``val.png_filter`` of ``--opt``, else 'none' (what ``settings`` leaves out: it is the same
     for both command lines)."""
-    from ._lib import RefidHipError
     from .validation import check_png_filter
-    if args.png_filter is not None:
-        return args.png_filter
-    if args.opt:
-        from .options import parse
-        val = parse(args.opt, is_train=False).get("val") or {}
-        try:
-            return check_png_filter(val.get("png_filter"), "--opt: val.png_filter")
-        except RefidHipError as ex:
-            raise SystemExit(str(ex))
-    return "none"
+    return _val_setting(args, "png_filter", "png_filter", check_png_filter)
 
 
 def png_deflate_setting(args):
     """``--png-deflate``, else ``val.png_deflate`` of ``--opt``, else 'host'; as ``png_filter_setting``."""
-    from ._lib import RefidHipError
     from .validation import check_png_deflate
-    if args.png_deflate is not None:
-        return args.png_deflate
-    if args.opt:
-        from .options import parse
-        val = parse(args.opt, is_train=False).get("val") or {}
-        try:
-            return check_png_deflate(val.get("png_deflate"), "--opt: val.png_deflate")
-        except RefidHipError as ex:
-            raise SystemExit(str(ex))
-    return "host"
+    return _val_setting(args, "png_deflate", "png_deflate", check_png_deflate)
 
 
 def parser(prog, doc, opt_help, frames_help, stamps_help):

@@ -11,13 +11,14 @@ and the events of its exposure per item (``frame_windows``, ``SequenceAssembler(
 Window search stays on the host: the host loaded the events, so ``np.searchsorted`` over the same float32 timestamp
 column the kernel reads costs nothing and needs no synchronisation."""
 import collections
+import contextlib
 import ctypes as C
 import os
 
 import numpy as np
 import torch
 
-from . import _lib, metrics
+from . import _lib, metrics, niqe, score, validation
 from ._lib import RefidHipError
 from .data import GeometryCache, layout_shapes
 
@@ -296,6 +297,125 @@ class SequenceAssembler:
         return {"lq": lq, "voxel": voxel}
 
 
+class _Sink:
+    """One output of a runner's uint8 frames (``_SequenceRunner.run`` lists them).  ``add(u8, base, count)``: once per minibatch,
+    the frames (count, [T,] H, W, 3) of items base .. base + count - 1; it only queues work on the current stream.  ``close()``:
+    in the ``finally`` behind the loop.  ``finish()``: after a loop that did not fail; it may synchronise and sets the result."""
+
+    def __init__(self, runner, names):
+        self.runner, self.names, self.what = runner, names, type(runner).__name__
+
+    def paths(self, root, u8, base, count):
+        return [p for i in range(count) for p in self.runner._paths(root, self.names[base + i], u8[i])]
+
+    def close(self):
+        pass
+
+    def finish(self):
+        pass
+
+
+def _flat(u8):
+    return u8.view(-1, *u8.shape[-3:])
+
+
+class _PngSink(_Sink):
+    def __init__(self, runner, names, out_dir, png_filter, png_deflate):
+        super().__init__(runner, names)
+        self.out_dir, self.writer = out_dir, validation.FrameWriter(runner.device, png_filter=png_filter, png_deflate=png_deflate)
+
+    def add(self, u8, base, count):
+        self.writer.dump([(_flat(u8), self.paths(self.out_dir, u8, base, count))])
+
+    def close(self):
+        self.writer.close()
+
+
+class _VideoSink(_Sink):
+    def __init__(self, runner, names, pairs, keys, path, fps, quality, subsampling, jpeg_pitch):
+        super().__init__(runner, names)
+        self.pairs, self.keys = pairs, keys
+        self.writer = validation.VideoWriter(runner.device, path, fps, quality, subsampling, jpeg_pitch)
+
+    def add(self, u8, base, count):
+        """The frames of a minibatch as they enter the video: the outputs in order; with ``keys`` pair k's left key frame
+        (resident, RGB) in front of its outputs, and its right key frame behind them unless the next pair starts on it."""
+        if self.keys:
+            asm, pairs, parts = self.runner.assembler, self.pairs, []
+            key = lambda i: asm.frames[i:i + 1].flip(-1) if asm.bgr else asm.frames[i:i + 1]      # noqa: E731
+            for i in range(count):
+                p = pairs[base + i]
+                parts += [key(p[0]), u8[i].reshape(-1, *u8.shape[-3:])]
+                if base + i + 1 >= len(pairs) or pairs[base + i + 1][0] != p[1]:
+                    parts.append(key(p[1]))
+            u8 = torch.cat(parts, dim=0)
+        self.writer.add(_flat(u8))
+
+    def close(self):
+        self.writer.close()
+        self.runner.video_paths = self.writer.paths
+
+
+class _NiqeSink(_Sink):
+    def __init__(self, runner, names, model):
+        super().__init__(runner, names)
+        niqe.cropped_size(runner.assembler.height, runner.assembler.width)        # a frame without one 96x96 block raises here
+        self.model, self.sums_pin, self.per_item = model, None, 0                 # pinned, sized at the first minibatch
+
+    def add(self, u8, base, count):
+        sums = niqe.moments(_flat(u8), self.model)
+        if self.sums_pin is None:
+            self.per_item = sums.shape[0] // count
+            self.sums_pin = torch.empty((len(self.names) * self.per_item,) + tuple(sums.shape[1:]), dtype=sums.dtype).pin_memory()
+        self.sums_pin[base * self.per_item:][:sums.shape[0]].copy_(sums, non_blocking=True)
+
+    def finish(self):
+        torch.cuda.current_stream(self.runner.device).synchronize()               # the last sums have arrived
+        scores = niqe.finish(self.sums_pin.numpy(), self.model)
+        self.runner.niqe_scores = [(self.names[i // self.per_item], i % self.per_item, sc) for i, sc in enumerate(scores)]
+
+
+class _ScoreSink(_Sink):
+    def __init__(self, runner, names, gt, scorer):
+        super().__init__(runner, names)
+        self.scorer, self.scored = score.FrameScorer() if scorer is None else scorer, 0
+        self.gt_dir = os.fspath(gt) if isinstance(gt, (str, os.PathLike)) else None
+        self.gt_all = None
+        if self.gt_dir is None:                # the frames themselves, uploaded once; a directory's PNGs are decoded per minibatch
+            H, W = runner.assembler.height, runner.assembler.width
+            gt = torch.as_tensor(gt) if not torch.is_tensor(gt) else gt
+            if gt.dtype != torch.uint8 or gt.dim() != 4 or tuple(gt.shape[1:]) != (H, W, 3):
+                raise RefidHipError(f"{self.what}.run: gt must be a directory or uint8 (frames, {H}, {W}, 3), got {gt.dtype} "
+                                    f"{tuple(gt.shape)}")
+            self.gt_all = gt.contiguous().to(runner.device, non_blocking=True)
+
+    def add(self, u8, base, count):
+        flat = _flat(u8)
+        if self.gt_dir is not None:
+            gpaths = self.paths(self.gt_dir, u8, base, count)
+            for p in gpaths:
+                if not os.path.isfile(p):
+                    raise RefidHipError(f"{self.what}.run: no ground truth {p}")
+            g = load_png_frames(gpaths, device=self.runner.device, frames_per_launch=len(gpaths))
+            if g.shape != flat.shape:
+                raise RefidHipError(f"{self.what}.run: the ground truth {gpaths[0]} is {g.shape[1]}x{g.shape[2]}, the "
+                                    f"output {flat.shape[1]}x{flat.shape[2]}")
+        else:
+            g = self.gt_all[self.scored:self.scored + flat.shape[0]]
+            if g.shape[0] != flat.shape[0]:
+                raise RefidHipError(f"{self.what}.run: gt holds {self.gt_all.shape[0]} frames, fewer than the outputs")
+        self.scorer.add(flat, g)
+        self.scored += flat.shape[0]
+
+    def finish(self):
+        if self.gt_all is not None and self.scored != self.gt_all.shape[0]:
+            raise RefidHipError(f"{self.what}.run: gt holds {self.gt_all.shape[0]} frames for {self.scored} outputs")
+        sc = self.scorer.finish()               # the one synchronisation, after the loop
+        each = self.scored // len(self.names)
+        self.runner.scores = [(self.names[i // each], i % each, score.Scores(*(None if col is None else col[i] for col in sc)))
+                              for i in range(self.scored)]
+
+
 class _SequenceRunner:
     """What ``SequenceInterpolator`` and ``SequenceDeblurrer`` share: upload the sequence once, assemble minibatch k+1 on a
     side stream while minibatch k runs, crop back to (H, W), quantise with ``metrics.val_tail`` and hand the uint8 frames to
@@ -314,20 +434,17 @@ class _SequenceRunner:
     ``FrameScorer()``: PSNR and the 3-D SSIM, uncropped.  ``scores`` then holds ``(name, frame index, score.Scores)`` per
     frame, a ``Scores`` field being None for what was not asked for (``scores`` is None without ``gt``)."""
 
-    niqe_scores = None
-    scores = None
-    video_paths = None
+    niqe_scores = scores = video_paths = None
 
     def run(self, frames, events, pairs, out_dir=None, names=None, keep=False, bgr=False, niqe=None, png_filter="none",
             png_deflate="host", gt=None, score=None, video=None, video_fps=30, video_quality=90, video_subsampling="420",
             video_keys=None, jpeg_pitch=None):
-        from . import niqe as niqe_mod
-        from .validation import FrameWriter, VideoWriter, check_png_deflate, check_png_filter, check_video_options
         what = type(self).__name__
-        png_filter = check_png_filter(png_filter, f"{what}.run: png_filter")
-        png_deflate = check_png_deflate(png_deflate, f"{what}.run: png_deflate")
+        self.niqe_scores = self.scores = self.video_paths = None
+        png_filter = validation.check_png_filter(png_filter, f"{what}.run: png_filter")
+        png_deflate = validation.check_png_deflate(png_deflate, f"{what}.run: png_deflate")
         if video is not None:
-            check_video_options(video_fps, video_quality, video_subsampling, jpeg_pitch, f"{what}.run")
+            validation.check_video_options(video_fps, video_quality, video_subsampling, jpeg_pitch, f"{what}.run")
             sharp = self.assembler.layout == "sharp"
             if video_keys and not sharp:
                 raise RefidHipError(f"{what}.run: video_keys needs sharp key frames (layout 'sharp'), not {self.assembler.layout!r}")
@@ -343,25 +460,13 @@ class _SequenceRunner:
         cur = torch.cuda.current_stream(self.device)
         asm.load(frames, events, bgr=bgr)
         side.wait_stream(cur)                 # the upload was issued on the current stream
-        H, W = asm.height, asm.width
-        self.niqe_scores = None
-        if niqe is not None:
-            niqe_mod.cropped_size(H, W)        # a frame without one 96x96 block raises here, before any work
-        sums_pin, per_item = None, 0           # pinned (all frames, 2, blocks, 5, 5) float64, allocated at the first minibatch
-        self.scores = None
-        scorer, gt_dir, gt_all, scored = None, None, None, 0
-        if gt is not None:
-            from .score import FrameScorer
-            scorer = FrameScorer() if score is None else score
-            if isinstance(gt, (str, os.PathLike)):
-                gt_dir = os.fspath(gt)
-            else:
-                gt_all = torch.as_tensor(gt) if not torch.is_tensor(gt) else gt
-                if gt_all.dtype != torch.uint8 or gt_all.dim() != 4 or tuple(gt_all.shape[1:]) != (H, W, 3):
-                    raise RefidHipError(f"{what}.run: gt must be a directory or uint8 (frames, {H}, {W}, 3), got {gt_all.dtype} "
-                                        f"{tuple(gt_all.shape)}")
-                gt_all = gt_all.contiguous().to(self.device, non_blocking=True)
-        elif score is not None:
+        sinks = [None if out_dir is None else _PngSink(self, names, out_dir, png_filter, png_deflate),
+                 None if video is None else _VideoSink(self, names, pairs, video_keys, video, video_fps, video_quality,
+                                                       video_subsampling, jpeg_pitch),
+                 None if niqe is None else _NiqeSink(self, names, niqe),
+                 None if gt is None else _ScoreSink(self, names, gt, score)]
+        sinks = [s for s in sinks if s is not None]         # those asked for, in the order their work is queued per minibatch
+        if gt is None and score is not None:
             raise RefidHipError(f"{what}.run: score= needs gt=")
         chunks = [pairs[i:i + self.max_minibatch] for i in range(0, len(pairs), self.max_minibatch)]
 
@@ -372,11 +477,6 @@ class _SequenceRunner:
                 return asm.assemble(chunks[k])
 
         was_training = self.net.training
-        writer = FrameWriter(self.device, png_filter=png_filter, png_deflate=png_deflate) if out_dir is not None else None
-        vwriter = None
-        if video is not None:
-            vwriter = VideoWriter(self.device, video, video_fps, video_quality, video_subsampling, jpeg_pitch)
-        self.video_paths = None
         kept = []
         self.net.eval()
         try:
@@ -389,77 +489,20 @@ class _SequenceRunner:
                         v.record_stream(cur)
                     nxt = preload(k + 1)
                     out = self._forward(batch)
-                    u8 = metrics.val_tail(out[..., :H, :W], bgr=False).pred_u8       # (P, [T,] H, W, 3)
-                    base = k * self.max_minibatch
-                    if writer is not None:
-                        paths = [p for i in range(len(chunk)) for p in self._paths(out_dir, names[base + i], u8[i])]
-                        writer.dump([(u8.view(-1, H, W, 3), paths)])
-                    if vwriter is not None:
-                        vwriter.add(self._video_frames(u8, pairs, base, len(chunk), video_keys).view(-1, H, W, 3))
-                    if niqe is not None:
-                        sums = niqe_mod.moments(u8.view(-1, H, W, 3), niqe)
-                        if sums_pin is None:
-                            per_item = sums.shape[0] // len(chunk)
-                            sums_pin = torch.empty((len(pairs) * per_item,) + tuple(sums.shape[1:]), dtype=sums.dtype).pin_memory()
-                        at = k * self.max_minibatch * per_item
-                        sums_pin[at:at + sums.shape[0]].copy_(sums, non_blocking=True)
-                    if scorer is not None:
-                        flat = u8.view(-1, H, W, 3)
-                        if gt_dir is not None:
-                            gpaths = [p for i in range(len(chunk)) for p in self._paths(gt_dir, names[base + i], u8[i])]
-                            for p in gpaths:
-                                if not os.path.isfile(p):
-                                    raise RefidHipError(f"{what}.run: no ground truth {p}")
-                            g = load_png_frames(gpaths, device=self.device, frames_per_launch=len(gpaths))
-                            if g.shape != flat.shape:
-                                raise RefidHipError(f"{what}.run: the ground truth {gpaths[0]} is {g.shape[1]}x{g.shape[2]}, the "
-                                                    f"output {H}x{W}")
-                        else:
-                            g = gt_all[scored:scored + flat.shape[0]]
-                            if g.shape[0] != flat.shape[0]:
-                                raise RefidHipError(f"{what}.run: gt holds {gt_all.shape[0]} frames, fewer than the outputs")
-                        scorer.add(flat, g)
-                        scored += flat.shape[0]
+                    u8 = metrics.val_tail(out[..., :asm.height, :asm.width], bgr=False).pred_u8       # (P, [T,] H, W, 3)
+                    for sink in sinks:
+                        sink.add(u8, k * self.max_minibatch, len(chunk))
                     if keep:
                         kept.append(u8)
         finally:
             self.net.train(was_training)
             cur.wait_stream(side)
-            try:
-                if writer is not None:
-                    writer.close()
-            finally:
-                if vwriter is not None:
-                    vwriter.close()
-                    self.video_paths = vwriter.paths
-        if niqe is not None:
-            cur.synchronize()                  # the last sums have arrived
-            scores = niqe_mod.finish(sums_pin.numpy(), niqe)
-            self.niqe_scores = [(names[i // per_item], i % per_item, sc) for i, sc in enumerate(scores)]
-        if scorer is not None:
-            from .score import Scores
-            if gt_all is not None and scored != gt_all.shape[0]:
-                raise RefidHipError(f"{what}.run: gt holds {gt_all.shape[0]} frames for {scored} outputs")
-            sc = scorer.finish()                # the one synchronisation, after the loop
-            each = scored // len(pairs)
-            self.scores = [(names[i // each], i % each, Scores(*(None if col is None else col[i] for col in sc)))
-                           for i in range(scored)]
+            with contextlib.ExitStack() as closing:        # (last in, first out) in the sinks' order, each even if another raises
+                for sink in reversed(sinks):
+                    closing.callback(sink.close)
+        for sink in sinks:
+            sink.finish()
         return torch.cat(kept, dim=0).cpu().numpy() if keep else None
-
-    def _video_frames(self, u8, pairs, base, count, keys):
-        """The frames of a minibatch as they enter the video: the outputs in order; with ``keys`` pair k's left key frame
-        (resident, RGB) in front of its outputs, and its right key frame behind them unless the next pair starts on it."""
-        if not keys:
-            return u8
-        resident = self.assembler.frames
-        key = lambda i: resident[i:i + 1].flip(-1) if self.assembler.bgr else resident[i:i + 1]      # noqa: E731
-        parts = []
-        for i in range(count):
-            p = pairs[base + i]
-            parts += [key(p[0]), u8[i].reshape(-1, *u8.shape[-3:])]
-            if base + i + 1 >= len(pairs) or pairs[base + i + 1][0] != p[1]:
-                parts.append(key(p[1]))
-        return torch.cat(parts, dim=0)
 
 
 class SequenceInterpolator(_SequenceRunner):
@@ -497,8 +540,10 @@ class SequenceInterpolator(_SequenceRunner):
         frames enter the video too (default: yes for layout 'sharp', no otherwise; True elsewhere raises) -- pair k's left
         key frame in front of its outputs, its right key frame behind them when the next pair does not start on it or
         there is none -- so that a run of consecutive pairs is a gap-free slow-motion clip."""
-        return super().run(frames, events, pairs, out_dir, names, keep, bgr, niqe, png_filter, png_deflate, gt, score, video,
-                           video_fps, video_quality, video_subsampling, video_keys, jpeg_pitch)
+        return super().run(frames, events, pairs, out_dir=out_dir, names=names, keep=keep, bgr=bgr, niqe=niqe,
+                           png_filter=png_filter, png_deflate=png_deflate, gt=gt, score=score, video=video, video_fps=video_fps,
+                           video_quality=video_quality, video_subsampling=video_subsampling, video_keys=video_keys,
+                           jpeg_pitch=jpeg_pitch)
 
     def _forward(self, batch):
         return self.net(x=batch["lq"], event=batch["voxel"])
@@ -541,8 +586,9 @@ class SequenceDeblurrer(_SequenceRunner):
         ``niqe``: a ``NiqeModel``; ``niqe_scores`` then holds (name, 0, score) per output frame.  ``png_filter``: as for
         ``SequenceInterpolator.run``.  ``gt`` / ``score``: as there, the directory holding ``{names[k]}.png``.  ``video`` and
         its options: as there, the deblurred frames in order (no key frames)."""
-        return super().run(frames, events, items, out_dir, names, keep, bgr, niqe, png_filter, png_deflate, gt, score, video,
-                           video_fps, video_quality, video_subsampling, None, jpeg_pitch)
+        return super().run(frames, events, items, out_dir=out_dir, names=names, keep=keep, bgr=bgr, niqe=niqe,
+                           png_filter=png_filter, png_deflate=png_deflate, gt=gt, score=score, video=video, video_fps=video_fps,
+                           video_quality=video_quality, video_subsampling=video_subsampling, jpeg_pitch=jpeg_pitch)
 
     def _forward(self, batch):
         if self.crop_size is None:

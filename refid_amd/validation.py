@@ -32,20 +32,22 @@ PNG_FILTERS = ("none", "adaptive")
 PNG_DEFLATES = ("host", "device")
 
 
+def _check_choice(value, choices, where):
+    """``value`` (None, an absent key: the first choice) if it is one of ``choices``; anything else raises, naming ``where``."""
+    value = choices[0] if value is None else value
+    if value not in choices:
+        raise _lib.RefidHipError(f"{where}: {value!r} is not one of {', '.join(choices)}")
+    return value
+
+
 def check_png_filter(value, where="png_filter"):
     """'none' (or None: an absent key) / 'adaptive'; anything else raises, naming ``where``."""
-    value = "none" if value is None else value
-    if value not in PNG_FILTERS:
-        raise _lib.RefidHipError(f"{where}: {value!r} is not one of {', '.join(PNG_FILTERS)}")
-    return value
+    return _check_choice(value, PNG_FILTERS, where)
 
 
 def check_png_deflate(value, where="png_deflate"):
     """'host' (or None: an absent key) / 'device'; anything else raises, naming ``where``."""
-    value = "host" if value is None else value
-    if value not in PNG_DEFLATES:
-        raise _lib.RefidHipError(f"{where}: {value!r} is not one of {', '.join(PNG_DEFLATES)}")
-    return value
+    return _check_choice(value, PNG_DEFLATES, where)
 
 
 JPEG_SUBSAMPLINGS = ("420", "444")
@@ -68,89 +70,59 @@ def check_video_options(fps=30, quality=90, subsampling="420", jpeg_pitch=None, 
     return fps, quality, subsampling, jpeg_pitch
 
 
-class FrameWriter:
-    WORKERS = 4              # encoding is zlib (releases the GIL); never sized from the machine's core count
-    QUEUE = 32               # jobs submitted and not finished; `dump` blocks beyond that
+class _PinnedRelay:
+    """What ``FrameWriter`` and ``VideoWriter`` share: a side stream, two pinned host buffers ("slots") that take turns, the
+    event behind a slot's copies, and a thread pool whose jobs read a slot once that event has completed.  Per transfer the
+    owner calls ``claim()``, launches its device work on the current stream, ``send()``s the results and ``submit()``s the jobs
+    that read them, in this order: the overlap rests on it ("Frame outputs")."""
 
-    def __init__(self, device, level=1, png_filter="none", png_deflate="host"):
-        self.level = level
-        self.png_filter = check_png_filter(png_filter, "FrameWriter: png_filter")
-        self.png_deflate = check_png_deflate(png_deflate, "FrameWriter: png_deflate")
+    def __init__(self, device, workers, queue, thread_name_prefix):
         self.stream = torch.cuda.Stream(device)
         self.slots = [dict(buf=None, jobs=[]), dict(buf=None, jobs=[])]
         self.turn = 0
-        self.pool = ThreadPoolExecutor(max_workers=self.WORKERS, thread_name_prefix="refid-png")
-        self.room = threading.BoundedSemaphore(self.QUEUE)
+        self.pool = ThreadPoolExecutor(max_workers=workers, thread_name_prefix=thread_name_prefix)
+        self.room = threading.BoundedSemaphore(queue)   # jobs submitted and not finished; `submit` blocks beyond that
 
-    def dump(self, batches):
-        """batches: [(uint8 device tensor (N, H, W, 3), [N paths])] of ONE item; returns at once."""
-        slot = self.slots[self.turn]
+    def claim(self):
+        """Takes the next slot and waits for the jobs of its previous transfer: its buffer may then be overwritten."""
+        self.slot = self.slots[self.turn]
         self.turn ^= 1
-        self._drain(slot)                                   # its previous item is written: the buffer may be overwritten
-        # (tensor, paths, width, (lens, height)): the width marks rows the device has filtered, the last entry zlib streams it
-        # has deflated as well; both launched here on the current stream
-        if self.png_deflate == "device":
-            batches = [self._deflated(t, paths, self.png_filter) for t, paths in batches]
-        else:
-            batches = [self._filtered(t, paths) if self.png_filter == "adaptive" else (t, paths, None, None) for t, paths in batches]
-        total = sum(t.numel() + (0 if deflated is None else 4 * deflated[0].numel() + 4) for t, _, _, deflated in batches)
+        self._drain(self.slot)
+
+    def send(self, groups):
+        """groups: [[device tensor, ...], ...], all of them one transfer into the claimed slot.  Every tensor is copied,
+        non-blocking, on the side stream -- which first waits for the current stream -- to the next multiple of its element
+        size (int32 lengths behind uint8 payload: the next multiple of 4); one event is recorded behind the copies.  Returns
+        the pinned views in the same nesting; only a job given to ``submit`` may read them."""
+        slot, off, views = self.slot, 0, []
+        total = sum((t.numel() + 1) * t.element_size() for group in groups for t in group)       # with room to align each
         if slot["buf"] is None or slot["buf"].numel() < total:
             slot["buf"] = torch.empty(total, dtype=torch.uint8).pin_memory()
         self.stream.wait_stream(torch.cuda.current_stream())
-        views, off = [], 0
         with torch.cuda.stream(self.stream):
-            for t, paths, width, deflated in batches:
-                dst = slot["buf"][off:off + t.numel()].view(t.shape)
-                dst.copy_(t, non_blocking=True)
-                t.record_stream(self.stream)                # the allocator must not hand t's block out before the copy ran
-                off += t.numel()
-                sizes = None
-                if deflated is not None:                    # the streams' lengths, behind them at the next multiple of 4
-                    lens, height = deflated
-                    off = (off + 3) & ~3
-                    pinned = slot["buf"][off:off + 4 * lens.numel()].view(torch.int32)
-                    pinned.copy_(lens, non_blocking=True)
-                    lens.record_stream(self.stream)
-                    off += 4 * lens.numel()
-                    sizes = (pinned.numpy(), height)
-                views.append((dst.numpy(), paths, width, sizes))
-            done = torch.cuda.Event()
-            done.record(self.stream)
-        for frames, paths, width, sizes in views:
-            for i, path in enumerate(paths):
-                self.room.acquire()
-                stream = None if sizes is None else (sizes[0][i:i + 1], sizes[1])
-                slot["jobs"].append(self.pool.submit(self._job, done, frames[i], path, width, stream))
+            for group in groups:
+                views.append([])
+                for t in group:
+                    size = t.element_size()
+                    off = -(-off // size) * size
+                    dst = slot["buf"][off:off + t.numel() * size].view(t.dtype).view(t.shape)
+                    dst.copy_(t, non_blocking=True)
+                    t.record_stream(self.stream)            # the allocator must not hand t's block out before the copy ran
+                    views[-1].append(dst)
+                    off += t.numel() * size
+            self.done = torch.cuda.Event()
+            self.done.record(self.stream)
+        return views
 
-    @staticmethod
-    def _filtered(t, paths):
-        """(filtered rows (N, H, 1 + 3W) of t, paths, W), launched on the current stream; frames wider than the kernel
-        takes stay as they are (filter 0 on the host)."""
-        from . import ops
-        if t.dim() != 4 or t.shape[-1] != 3 or t.shape[2] > _lib.PNG_FILTER_MAX_WIDTH:
-            return t, paths, None, None
-        return ops.png_filter(t.contiguous(), "adaptive"), paths, int(t.shape[2]), None
+    def submit(self, job, *args):
+        """Runs ``job(*args)`` on the pool once the copies of the last ``send`` have completed; blocks while the queue is full."""
+        self.room.acquire()
+        self.slot["jobs"].append(self.pool.submit(self._run, self.done, job, args))
 
-    @staticmethod
-    def _deflated(t, paths, png_filter):
-        """(zlib streams (N, pitch) of t's rows, paths, W, (lens (N,), H)), launched on the current stream: the rows are
-        filter 0 or adaptive.  Frames the filter kernel does not take keep the host route."""
-        from . import ops
-        if t.dim() != 4 or t.shape[-1] != 3 or t.shape[2] > _lib.PNG_FILTER_MAX_WIDTH:
-            return t, paths, None, None
-        rows = ops.png_filter(t.contiguous(), "adaptive" if png_filter == "adaptive" else 0)
-        out, lens = ops.png_deflate(rows)
-        return out, paths, int(t.shape[2]), (lens, int(t.shape[1]))
-
-    def _job(self, done, frame, path, width=None, stream=None):
+    def _run(self, done, job, args):
         try:
             done.synchronize()                              # nothing reads the pinned buffer before its copy has completed
-            if stream is not None:                          # a zlib stream of the device: its length came with the copy
-                write_png_stream(path, frame[:int(stream[0][0])], width, stream[1])
-            elif width is None:
-                write_png(path, frame, self.level)
-            else:                                           # rows the device has filtered
-                write_png_rows(path, frame, width, frame.shape[0], self.level)
+            job(*args)
         finally:
             self.room.release()
 
@@ -167,12 +139,58 @@ class FrameWriter:
             raise err
 
     def close(self):
-        """Joins the pool: every file exists when this returns; a worker's exception is raised here."""
+        """Joins the pool: every job has run when this returns; the first job's exception is raised here."""
         try:
             for slot in self.slots:
                 self._drain(slot)
         finally:
             self.pool.shutdown(wait=True, cancel_futures=True)
+
+
+class FrameWriter:
+    WORKERS = 4              # encoding is zlib (releases the GIL); never sized from the machine's core count
+    QUEUE = 32               # jobs submitted and not finished; `dump` blocks beyond that
+
+    def __init__(self, device, level=1, png_filter="none", png_deflate="host"):
+        self.level = level
+        self.png_filter = check_png_filter(png_filter, "FrameWriter: png_filter")
+        self.png_deflate = check_png_deflate(png_deflate, "FrameWriter: png_deflate")
+        self.relay = _PinnedRelay(device, self.WORKERS, self.QUEUE, "refid-png")
+
+    def dump(self, batches):
+        """batches: [(uint8 device tensor (N, H, W, 3), [N paths])] of ONE item; returns at once."""
+        self.relay.claim()                                  # the slot's previous item is written
+        routed = [self._route(t, paths) for t, paths in batches]        # the device's share, launched on the current stream
+        for (_, paths, width, height), (payload, *lens) in zip(routed, self.relay.send([r[0] for r in routed])):
+            payload, lens = payload.numpy(), lens[0].numpy() if lens else None
+            for i, path in enumerate(paths):
+                self.relay.submit(self._write, payload[i], path, width, None if lens is None else lens[i:i + 1], height)
+
+    def _route(self, t, paths):
+        """([what travels], paths, W, H): the frames themselves (W and H None: the host does everything); with
+        ``png_filter='adaptive'`` their filtered rows (N, H, 1 + 3W) (H None); with ``png_deflate='device'`` the zlib streams
+        (N, pitch) of the rows -- filter 0 or adaptive -- and their lengths (N,).  Frames the filter kernel does not take keep
+        the host route."""
+        from . import ops
+        deflate, fits = self.png_deflate == "device", t.dim() == 4 and t.shape[-1] == 3 and t.shape[2] <= _lib.PNG_FILTER_MAX_WIDTH
+        if not fits or not (deflate or self.png_filter == "adaptive"):
+            return [t], paths, None, None
+        rows = ops.png_filter(t.contiguous(), "adaptive" if self.png_filter == "adaptive" else 0)
+        if not deflate:
+            return [rows], paths, int(t.shape[2]), None
+        return list(ops.png_deflate(rows)), paths, int(t.shape[2]), int(t.shape[1])
+
+    def _write(self, frame, path, width, length, height):
+        if length is not None:                              # a zlib stream of the device: its length came with the copy
+            write_png_stream(path, frame[:int(length[0])], width, height)
+        elif width is None:
+            write_png(path, frame, self.level)
+        else:                                               # rows the device has filtered
+            write_png_rows(path, frame, width, frame.shape[0], self.level)
+
+    def close(self):
+        """Joins the pool: every file exists when this returns; a worker's exception is raised here."""
+        self.relay.close()
 
 
 class VideoWriter:
@@ -186,11 +204,7 @@ class VideoWriter:
     def __init__(self, device, path, fps, quality=90, subsampling="420", jpeg_pitch=None, max_bytes=None):
         self.fps, self.quality, self.subsampling, self.jpeg_pitch = check_video_options(fps, quality, subsampling, jpeg_pitch)
         self.path, self.max_bytes = str(path), max_bytes
-        self.stream = torch.cuda.Stream(device)
-        self.slots = [dict(buf=None, jobs=[]), dict(buf=None, jobs=[])]
-        self.turn = 0
-        self.pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="refid-avi")      # one worker: submission order
-        self.room = threading.BoundedSemaphore(self.QUEUE)
+        self.relay = _PinnedRelay(device, 1, self.QUEUE, "refid-avi")                       # one worker: submission order
         self.avi, self.frames, self.paths, self.failed = None, 0, [], None
 
     def add(self, frames_u8):
@@ -208,34 +222,16 @@ class VideoWriter:
             self.size = tuple(t.shape[1:])
         elif tuple(t.shape[1:]) != self.size:
             raise _lib.RefidHipError(f"VideoWriter: frames of {tuple(t.shape[1:])} in a video of {self.size}")
-        slot = self.slots[self.turn]
-        self.turn ^= 1
-        self._drain(slot)                                   # its previous batch is appended: the buffer may be overwritten
+        self.relay.claim()                                  # the slot's previous batch is appended
         out, lens = ops.jpeg_encode(t, self.quality, self.subsampling, pitch=self.jpeg_pitch)      # on the current stream
-        n, pitch = int(out.shape[0]), int(out.shape[1])
-        at = (out.numel() + 3) & ~3                         # the lengths, behind the files at the next multiple of 4
-        total = at + 4 * n
-        if slot["buf"] is None or slot["buf"].numel() < total:
-            slot["buf"] = torch.empty(total, dtype=torch.uint8).pin_memory()
-        self.stream.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(self.stream):
-            files = slot["buf"][:out.numel()].view(n, pitch)
-            files.copy_(out, non_blocking=True)
-            out.record_stream(self.stream)                  # the allocator must not hand the block out before the copy ran
-            sizes = slot["buf"][at:total].view(torch.int32)
-            sizes.copy_(lens, non_blocking=True)
-            lens.record_stream(self.stream)
-            done = torch.cuda.Event()
-            done.record(self.stream)
-        self.room.acquire()
-        slot["jobs"].append(self.pool.submit(self._job, done, files.numpy(), sizes.numpy(), self.frames, pitch))
-        self.frames += n
+        (files, sizes), = self.relay.send([[out, lens]])    # the whole pitch and the lengths: nothing waits for a length
+        self.relay.submit(self._append, files.numpy(), sizes.numpy(), self.frames, int(out.shape[1]))
+        self.frames += int(out.shape[0])
 
-    def _job(self, done, files, sizes, first, pitch):
+    def _append(self, files, sizes, first, pitch):
+        if self.failed is not None:                         # an earlier batch failed: the order is lost, append nothing more
+            return
         try:
-            if self.failed is not None:                     # an earlier batch failed: the order is lost, append nothing more
-                return
-            done.synchronize()                              # nothing reads the pinned buffer before its copy has completed
             for i in range(files.shape[0]):
                 size = int(sizes[i])
                 if size < 0:
@@ -245,18 +241,12 @@ class VideoWriter:
         except BaseException as ex:                         # noqa: BLE001
             self.failed = ex
             raise
-        finally:
-            self.room.release()
-
-    _drain = staticmethod(FrameWriter._drain)
 
     def close(self):
         """Joins the worker and finishes the container: the files are complete when this returns; a worker's exception is
         raised here (the container is still closed, with the frames in front of the failure)."""
         try:
-            for slot in self.slots:
-                self._drain(slot)
+            self.relay.close()
         finally:
-            self.pool.shutdown(wait=True, cancel_futures=True)
             if self.avi is not None:
                 self.paths = self.avi.close()
