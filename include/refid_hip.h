@@ -957,6 +957,80 @@ size_t refid_jpeg_header_bytes(void);
 size_t refid_jpeg_bound(int32_t height, int32_t width, int32_t subsampling, int32_t restart_mcus);
 size_t refid_jpeg_work_bytes(int32_t n_frames, int32_t height, int32_t width, int32_t subsampling, int32_t restart_mcus);
 
+/* ----------------------------------------------------------------------------------
+ * Baseline JPEG decode (csrc/jpeg_entropy.h on the host, csrc/jpeg_decode.hip on the device): JPEG key frames and the
+ * frames of a Motion-JPEG AVI -> (n_frames, height, width, 3) uint8 RGB.  The serial entropy stage runs on the host
+ * (refid_jpeg_probe, refid_jpeg_entropy_decode: no GPU call, no allocation that outlives the call, safe from several threads
+ * at once); dequantisation, IDCT, chroma upsampling and colour conversion run on the device (refid_jpeg_decode).  The
+ * pixels are what libjpeg(-turbo) gives with its defaults (islow IDCT, fancy upsampling, table-based YCbCr -> RGB), which
+ * is what PIL returns: integers only, compared byte for byte.  tests/jpeg_decode_ref.py restates all of it.
+ *
+ * Accepted files: SOF0, 8 bit, one interleaved scan (Ss 0, Se 63, Ah = Al = 0); 1 component (grey, any sampling factors:
+ * REFID_JPEG_DEC_GREY) or 3 components with chroma 1x1 and luma 1x1 (REFID_JPEG_DEC_444), 2x1 (.._422) or 2x2 (.._420); any
+ * DQT (8-bit tables) and DHT, in any number of segments, a later one replacing an earlier one; DRI of any value, RSTn
+ * checked modulo 8; APPn, COM and other segments without meaning here are skipped; 0xFF fill bytes in front of a marker.
+ * The Annex K Huffman tables K.3 .. K.6 stand in slots 0 (luminance) and 1 (chrominance) until a DHT replaces them, so a
+ * file without DHT decodes, as Motion-JPEG cameras write them.  Refused, each with a message that begins "jpeg_decode:":
+ * progressive, arithmetic, lossless and hierarchical frames, SOF1, a precision other than 8, 2 or 4 or more components,
+ * other samplings, a scan that does not hold all components in frame order, 16-bit quantisation tables, RGB-coded files
+ * (Adobe transform 0, or component ids 'R' 'G' 'B'), a table that is referenced but not defined, a Huffman code that is not
+ * in its table, a DC category above 11, an AC category above 10, a DC value that leaves int16, a zero run past coefficient
+ * 63, entropy data that ends (or meets a marker) before the last MCU -- nothing is padded with zeros --, bytes left over in
+ * front of a restart marker, a wrong RST number, a height or width of 0, and any segment that passes the end of the file.
+ * Neither function reads outside [file, file + len).
+ *
+ * refid_jpeg_probe fills `info`.  blocks[c] = 8x8 blocks of component c's plane padded to whole MCUs: with MCU rows R and
+ * columns C (MCU = 8 h_max x 8 v_max pixels; grey: 8x8), component c holds (R v_c) x (C h_c) blocks.
+ * refid_jpeg_entropy_decode turns a file down unless its header gives exactly *expect, then writes
+ *   coefs  int16 [total_blocks][64]: the components back to back (Y, Cb, Cr), a component's blocks in raster order of its
+ *          padded plane, a block's quantised coefficients in natural (row-major, de-zigzagged) order, DC prediction undone;
+ *   quant  uint16 [components][64]: each component's quantisation table in natural order.
+ * After a refusal the contents of coefs and quant are unspecified (but nothing outside them was written).
+ *
+ * refid_jpeg_decode: coefs (n_frames, total_blocks, 64) and quant (n_frames, components, 64) on the device, as above, one
+ * set per frame (tables may differ from frame to frame) -> frames.  Two launches on `stream`, no allocation, no atomics, no
+ * synchronisation; `work` is refid_jpeg_decode_work_bytes(n_frames, height, width, sampling) bytes of scratch (the
+ * component planes between the launches; 0 from that function = a geometry the entry point turns down).
+ *   1. x = coef * q.  IDCT: libjpeg's jpeg_idct_islow, CONST_BITS 13, PASS1_BITS 2, multipliers 2446 3196 4433 6270 7373
+ *      9633 12299 15137 16069 16819 20995 25172; the column pass descales by 11, the row pass by 18, DESCALE(x, n) =
+ *      (x + (1 << (n-1))) >> n (arithmetic shift); + 128, clamped to 0 .. 255.  All of it in 32-bit two's complement with
+ *      wrap-around (unsigned on the device).  For coefficients an encoder can produce this equals libjpeg.
+ *   2. A component plane is cropped to ceil(H v / v_max) x ceil(W h / h_max); where a neighbour is missing the edge sample
+ *      stands in.  h2v1 (4:2:2), s = the chroma row: out[2i] = (3 s[i] + s[i-1] + 1) >> 2, out[2i+1] = (3 s[i] + s[i+1] + 2)
+ *      >> 2, out[0] = s[0], out[2 last + 1] = s[last].  h2v2 (4:2:0): t = 3 near_row + far_row (far: the row above for the
+ *      upper output row, below for the lower); out[2i] = (3 t[i] + t[i-1] + 8) >> 4, out[2i+1] = (3 t[i] + t[i+1] + 7) >> 4,
+ *      out[0] = (4 t[0] + 8) >> 4, out[2 last + 1] = (4 t[last] + 7) >> 4.  A chroma plane of at most 2 columns is
+ *      replicated instead (as libjpeg does).
+ *   3. F(x) = int(x 65536 + 0.5), cb -= 128, cr -= 128: R = Y + ((F(1.402) cr + 32768) >> 16), B = Y + ((F(1.772) cb + 32768)
+ *      >> 16), G = Y + ((-F(0.34414) cb + 32768 - F(0.71414) cr) >> 16), each clamped; grey: R = G = B = Y.
+ * Only the n_frames * height * width * 3 bytes of `frames` are written (any alignment; rows whose first byte is 4-aligned
+ * are stored as whole dwords, other rows byte by byte); a frame's bytes do not depend on n_frames, on its position or on
+ * the alignment.  height, width 1 .. 65535; n_frames 1 .. 65535; coefs and work aligned to 16 bytes, quant to 2.  A bad
+ * descriptor returns 1 with a message naming the field and launches nothing.
+ * ---------------------------------------------------------------------------------- */
+#define REFID_JPEG_DEC_GREY 0
+#define REFID_JPEG_DEC_444 1
+#define REFID_JPEG_DEC_422 2
+#define REFID_JPEG_DEC_420 3
+typedef struct refid_jpeg_info {
+    int32_t height, width, components, sampling;
+    int32_t blocks[3];                          /* per component (0 for the components a grey file lacks)          */
+    int32_t total_blocks, restart_interval;     /* restart_interval in MCUs, 0 = none                              */
+} refid_jpeg_info;
+int refid_jpeg_probe(const uint8_t* file, size_t len, refid_jpeg_info* info);
+int refid_jpeg_entropy_decode(const uint8_t* file, size_t len, const refid_jpeg_info* expect, int16_t* coefs, uint16_t* quant);
+typedef struct refid_jpeg_decode_desc {
+    const int16_t* coefs;                       /* device: n_frames * total_blocks * 64                            */
+    const uint16_t* quant;                      /* device: n_frames * components * 64                              */
+    uint8_t* frames;                            /* device: n_frames * height * width * 3 bytes, RGB                */
+    uint8_t* work;                              /* device: refid_jpeg_decode_work_bytes(...) bytes of scratch      */
+    int32_t n_frames, height, width, sampling;
+} refid_jpeg_decode_desc;
+int refid_jpeg_decode(const refid_jpeg_decode_desc* d, void* stream);
+size_t refid_jpeg_decode_work_bytes(int32_t n_frames, int32_t height, int32_t width, int32_t sampling);
+/* blocks of one frame: fills blocks[3], returns their sum (0 for a geometry that is turned down) */
+int32_t refid_jpeg_decode_blocks(int32_t height, int32_t width, int32_t sampling, int32_t* blocks);
+
 #ifdef __cplusplus
 }
 #endif

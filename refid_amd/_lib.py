@@ -180,6 +180,22 @@ class JpegDesc(C.Structure):
     ]
 
 
+class JpegInfo(C.Structure):
+    """refid_jpeg_info: what refid_jpeg_probe reads from a file's header and refid_jpeg_entropy_decode expects of it."""
+    _fields_ = [
+        ("height", C.c_int32), ("width", C.c_int32), ("components", C.c_int32), ("sampling", C.c_int32),
+        ("blocks", C.c_int32 * 3), ("total_blocks", C.c_int32), ("restart_interval", C.c_int32),
+    ]
+
+
+class JpegDecodeDesc(C.Structure):
+    """refid_jpeg_decode_desc: the coefficients and tables of n_frames JPEG files of one geometry -> uint8 (n_frames, height, width, 3)."""
+    _fields_ = [
+        ("coefs", C.c_void_p), ("quant", C.c_void_p), ("frames", C.c_void_p), ("work", C.c_void_p),
+        ("n_frames", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("sampling", C.c_int32),
+    ]
+
+
 LAYOUT_BLUR, LAYOUT_SHARP = 0, 1                # == REFID_LAYOUT_* in include/refid_hip.h
 ASSEMBLE_ZERO, ASSEMBLE_SCATTER, ASSEMBLE_FINISH, ASSEMBLE_FRAMES, ASSEMBLE_ALL = 1, 2, 4, 8, 15
 ASSEMBLE_STATS = 16                              # refid_assemble_single only: voxel_norm's statistics, between scatter and finish
@@ -196,6 +212,7 @@ PNG_DEFLATE_RECORD = 1088          # == REFID_PNG_DEFLATE_RECORD in include/refi
 JPEG_444, JPEG_420 = 0, 1          # == REFID_JPEG_444 / REFID_JPEG_420 in include/refid_hip.h
 JPEG_HEADER_BYTES = 625            # == REFID_JPEG_HEADER_BYTES in include/refid_hip.h
 JPEG_BLOCK_BITS = 1660             # == REFID_JPEG_BLOCK_BITS in include/refid_hip.h
+JPEG_DEC_GREY, JPEG_DEC_444, JPEG_DEC_422, JPEG_DEC_420 = 0, 1, 2, 3    # == REFID_JPEG_DEC_* in include/refid_hip.h
 ABI_VERSION = 9          # == REFID_ABI_VERSION in include/refid_hip.h
 _lib = None
 
@@ -221,6 +238,8 @@ def lib():
         raise RefidHipError(
             f"{LIB_PATH} not found: the HIP extension is required (no CPU/eager fallback). "
             "Run `python -m refid_amd.build`.")
+    import torch  # noqa: F401  first: the library then binds the HIP runtime torch ships.  Loaded before torch it pulls in the
+    #                             system's, torch brings its own, and of two runtimes in one process the second finds no device
     L = C.CDLL(LIB_PATH)
     L.refid_last_error.restype = C.c_char_p
     L.refid_abi_version.restype = C.c_int
@@ -337,6 +356,13 @@ def _bind_extra(L):
     L.refid_jpeg_bound.restype = C.c_size_t
     L.refid_jpeg_work_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     L.refid_jpeg_work_bytes.restype = C.c_size_t
+    L.refid_jpeg_probe.argtypes = [vp, C.c_size_t, C.POINTER(JpegInfo)]
+    L.refid_jpeg_entropy_decode.argtypes = [vp, C.c_size_t, C.POINTER(JpegInfo), vp, vp]
+    L.refid_jpeg_decode.argtypes = [C.POINTER(JpegDecodeDesc), vp]
+    L.refid_jpeg_decode_work_bytes.argtypes = [C.c_int32] * 4
+    L.refid_jpeg_decode_work_bytes.restype = C.c_size_t
+    L.refid_jpeg_decode_blocks.argtypes = [C.c_int32] * 3 + [C.POINTER(C.c_int32)]
+    L.refid_jpeg_decode_blocks.restype = C.c_int32
     L.refid_score_u8_parts.argtypes = [i, i, i, i]
     L.refid_score_u8_parts.restype = ll
     L.refid_score_u8.argtypes = [vp, vp, i, i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp]

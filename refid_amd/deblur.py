@@ -6,7 +6,8 @@
 ``--opt`` supplies ``network_g``, ``path.pretrain_network_g``, ``datasets.test.num_bins``, ``val.max_minibatch`` and, when
 ``val.grids`` is set, ``val.crop_size`` (tiled inference); or give ``--checkpoint`` with ``--num-bins``: the network is then
 ``SingleMultiConnectEVHINet`` with its defaults and ``ev_chn = num_bins``.  ``--frames`` is a directory of 8-bit PNGs
-(sorted by name) or a ``.npy`` stack (N, H, W, 3) uint8 RGB; ``--stamps`` a text file with the exposure ``start end`` of
+(sorted by name), a ``.npy`` stack (N, H, W, 3) uint8 RGB, or -- decoded on the GPU -- a directory of baseline JPEGs or a
+Motion-JPEG ``.avi``; ``--stamps`` a text file with the exposure ``start end`` of
 every frame per line, in the events' clock.  Frame k is written to ``{out}/{k:06d}.png``.  ``--niqe PARAMS.npz`` (the
 reference's ``niqe_pris_params.npz``) also scores every output frame with NIQE: ``{out}/niqe.txt`` holds one ``file score``
 line per frame and a last ``mean`` line over the finite scores, which is printed too.  ``--gt DIR`` (sharp PNGs named as
@@ -46,7 +47,7 @@ def settings(args):
 
 def main(argv=None):
     ap = parser("python -m refid_amd.deblur", __doc__, "a test YAML: network_g, path.pretrain_network_g, datasets.test.num_bins, val.*",
-                "directory of blurry PNG frames, or a .npy stack (N, H, W, 3) uint8 RGB",
+                "directory of blurry PNG or JPEG frames, a Motion-JPEG .avi, or a .npy stack (N, H, W, 3) uint8 RGB",
                 "the exposure 'start end' of every frame, one frame per line")
     ap.add_argument("--num-bins", type=int, help="voxel bins per frame (the network's ev_chn)")
     ap.add_argument("--max-minibatch", type=int, help="frames (with --crop-size: tiles) per network call; default 1")

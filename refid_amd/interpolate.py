@@ -5,8 +5,9 @@
 
 ``--opt`` supplies ``network_g``, ``path.pretrain_network_g`` and ``datasets.test.num_*`` (the layout follows the model
 type: the ``*Sharp*`` classes take sharp key frames); or give ``--checkpoint`` with ``--n`` / ``--m`` / ``--layout`` and the
-released network size.  ``--frames`` is a directory of 8-bit PNGs (sorted by name) or a ``.npy`` stack (N, H, W, 3) uint8
-RGB; ``--stamps`` a text file with one key-frame timestamp per line (sharp layout) or an exposure ``start end`` per line
+released network size.  ``--frames`` is a directory of 8-bit PNGs (sorted by name), a ``.npy`` stack (N, H, W, 3) uint8
+RGB, or -- decoded on the GPU -- a directory of baseline JPEGs (``*.jpg`` / ``*.jpeg``) or a Motion-JPEG ``.avi`` such as
+``--video`` writes; ``--stamps`` a text file with one key-frame timestamp per line (sharp layout) or an exposure ``start end`` per line
 (blur layout), in the events' clock.  Frame f of pair k is written to ``{out}/{k:06d}_{f:02d}.png``.  ``--niqe PARAMS.npz``
 (the reference's ``niqe_pris_params.npz``) also scores every output frame with NIQE: ``{out}/niqe.txt`` holds one
 ``file score`` line per frame and a last ``mean`` line over the finite scores, which is printed too.  ``--gt DIR`` (PNGs
@@ -42,11 +43,30 @@ def load_frames(path):
     return stack
 
 
+def _jpeg_input(path):
+    """True for what only the JPEG route reads: a Motion-JPEG ``.avi`` file, or a directory that holds ``*.jpg`` / ``*.jpeg``."""
+    if os.path.isdir(path):
+        return bool(glob.glob(os.path.join(path, "*.jpg")) or glob.glob(os.path.join(path, "*.jpeg")))
+    return str(path).lower().endswith(".avi")
+
+
 def load_frames_resident(path):
     """``--frames`` of the command lines: a directory of PNGs is inflated by a thread pool and unfiltered on the GPU
     (``sequence.load_png_frames``, csrc/png.hip) into the resident uint8 (N, H, W, 3) tensor the runners take, the same bytes
-    ``load_frames`` gives; a ``.npy`` stack, or a machine without a GPU, goes through ``load_frames``."""
+    ``load_frames`` gives; a ``.npy`` stack, or a machine without a GPU, goes through ``load_frames``.  A directory of JPEGs
+    or a Motion-JPEG ``.avi`` goes through ``sequence.load_key_frames`` (host entropy decode, csrc/jpeg_decode.hip); there is
+    no host JPEG decoder, so these need the GPU."""
     import torch
+    if _jpeg_input(path):
+        if not torch.cuda.is_available():
+            raise SystemExit("--frames: JPEG key frames need the GPU (a directory of *.jpg / *.jpeg or a Motion-JPEG .avi is decoded by "
+                             "csrc/jpeg_decode.hip; without a GPU give PNGs or a .npy stack)")
+        from . import sequence
+        from ._lib import RefidHipError
+        try:
+            return sequence.load_key_frames(path)
+        except RefidHipError as e:
+            raise SystemExit(f"--frames: {e}")
     if not (os.path.isdir(path) and torch.cuda.is_available()):
         return load_frames(path)
     from . import sequence
@@ -244,7 +264,7 @@ def run_and_report(runner, args, frames, events, items, niqe_model, noun, file_n
 
 def main(argv=None):
     ap = parser("python -m refid_amd.interpolate", __doc__, "a test YAML: network_g, path.pretrain_network_g, datasets.test.num_*",
-                "directory of PNG key frames, or a .npy stack (N, H, W, 3) uint8 RGB",
+                "directory of PNG or JPEG key frames, a Motion-JPEG .avi, or a .npy stack (N, H, W, 3) uint8 RGB",
                 "key-frame timestamps, one per line ('start end' per line for blur)")
     ap.add_argument("--n", type=int, help="frames to interpolate between two key frames")
     ap.add_argument("--m", type=int, help="frames to recover from each blurry key frame (blur layout)")

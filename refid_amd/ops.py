@@ -1220,6 +1220,55 @@ def jpeg_encode(frames_u8, quality=90, subsampling="420", restart_mcus=None, pit
     return out, lens
 
 
+JPEG_DECODE_SAMPLINGS = {"grey": _lib.JPEG_DEC_GREY, "444": _lib.JPEG_DEC_444, "422": _lib.JPEG_DEC_422, "420": _lib.JPEG_DEC_420}
+
+
+def jpeg_decode_blocks(h, w, sampling):
+    """(blocks per component [3], their sum) of a frame: the first dimension of one frame's ``coefs`` (host only, no GPU)."""
+    if sampling not in JPEG_DECODE_SAMPLINGS:
+        raise _lib.RefidHipError(f"jpeg_decode: sampling {sampling!r} is not one of {sorted(JPEG_DECODE_SAMPLINGS)}")
+    blocks = (C.c_int32 * 3)()
+    total = lib().refid_jpeg_decode_blocks(int(h), int(w), JPEG_DECODE_SAMPLINGS[sampling], blocks) if max(int(h), int(w)) < 2 ** 31 else 0
+    if total <= 0:
+        raise _lib.RefidHipError(f"jpeg_decode: height {h} and width {w} must be 1 .. 65535")
+    return list(blocks), total
+
+
+def jpeg_decode(coefs, quant, n, h, w, sampling, out=None):
+    """refid_jpeg_decode (csrc/jpeg_decode.hip) on the current stream: the quantised coefficients ``coefs`` int16
+    (n, total_blocks, 64) and tables ``quant`` uint16 or int16 (n, components, 64) of ``n`` JPEG files of one (h, w, sampling)
+    -- what ``jpeg.entropy_decode`` writes, on the device -> uint8 (n, h, w, 3) RGB, a grey file replicated to three
+    channels.  ``sampling``: 'grey', '444', '422' or '420'.  ``out``: a contiguous uint8 (n, h, w, 3) view to write into
+    (any alignment; nothing outside it is written).  The scratch between the two launches is allocated here.  Does not
+    synchronise."""
+    n, h, w = int(n), int(h), int(w)
+    if n < 1:
+        raise _lib.RefidHipError(f"jpeg_decode: n={n} must be positive")
+    blocks, total = jpeg_decode_blocks(h, w, sampling)
+    comps = 1 if sampling == "grey" else 3
+    if not isinstance(coefs, torch.Tensor) or not coefs.is_cuda or coefs.dtype != torch.int16 or not coefs.is_contiguous() or \
+            coefs.numel() != n * total * 64:
+        raise _lib.RefidHipError(f"jpeg_decode: coefs must be a contiguous int16 CUDA tensor of {n}*{total}*64 elements (no CPU fallback), got "
+                                 + (f"{coefs.dtype} {tuple(coefs.shape)} on {coefs.device}" if isinstance(coefs, torch.Tensor) else type(coefs).__name__))
+    if not isinstance(quant, torch.Tensor) or quant.device != coefs.device or quant.dtype not in (torch.int16, getattr(torch, "uint16", torch.int16)) or \
+            not quant.is_contiguous() or quant.numel() != n * comps * 64:
+        raise _lib.RefidHipError(f"jpeg_decode: quant must be a contiguous 16-bit tensor of {n}*{comps}*64 elements on {coefs.device}")
+    if out is None:
+        out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=coefs.device)
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != coefs.device or tuple(out.shape) != (n, h, w, 3) or \
+            not out.is_contiguous():
+        raise _lib.RefidHipError(f"jpeg_decode: out must be a contiguous uint8 ({n}, {h}, {w}, 3) tensor on {coefs.device}")
+    L = lib()
+    work_bytes = L.refid_jpeg_decode_work_bytes(n, h, w, JPEG_DECODE_SAMPLINGS[sampling])
+    if not work_bytes:
+        raise _lib.RefidHipError(f"jpeg_decode: {n} frames of {h}x{w} exceed the grid (split the call)")
+    work = torch.empty((work_bytes // 8,), dtype=torch.int64, device=coefs.device)
+    desc = _lib.JpegDecodeDesc(coefs=coefs.data_ptr(), quant=quant.data_ptr(), frames=out.data_ptr(), work=work.data_ptr(), n_frames=n,
+                               height=h, width=w, sampling=JPEG_DECODE_SAMPLINGS[sampling])
+    check(L.refid_jpeg_decode(C.byref(desc), _stream()), "refid_jpeg_decode")
+    return out
+
+
 def score_u8(a_u8, b_u8, bgr=False, crop_border=0, sq_rgb=True, sq_y=False, ssim3d=True, ssim_y=False, taps=False):
     """refid_score_u8 (csrc/score.hip) on the current stream: two uint8 CUDA tensors (..., H, W, 3) of one shape -> an int64
     CUDA tensor (4, nf) of 8-byte words, row 0 the integer squared errors, rows 1..3 the bits of the float64 sums sq_y,

@@ -197,6 +197,145 @@ def load_png_frames(paths, device=None, workers=8, frames_per_launch=8):
     return out
 
 
+def _jpeg_sources(sources):
+    """[(name, path or bytes)] of ``load_jpeg_frames``'s ``sources``."""
+    import glob
+    if isinstance(sources, (str, os.PathLike)):
+        if os.path.isdir(sources):
+            sources = sorted(glob.glob(os.path.join(sources, "*.jpg")) + glob.glob(os.path.join(sources, "*.jpeg")))
+        else:
+            sources = [sources]
+    out = []
+    for k, s in enumerate(sources):
+        if isinstance(s, (bytes, bytearray, memoryview)):
+            out.append((f"frame {k} ({len(s)} bytes)", bytes(s)))
+        else:
+            out.append((os.fspath(s), os.fspath(s)))
+    return out
+
+
+def load_jpeg_frames(sources, device=None, workers=8, frames_per_launch=8):
+    """Baseline JPEG key frames of one size -> uint8 (N, H, W, 3) RGB on the device, a grey file replicated to three channels:
+    what ``SequenceAssembler.load`` takes, and byte for byte what libjpeg (PIL) decodes.  ``sources``: paths in order, byte
+    strings in order (the frames of ``video.read_mjpeg_avi``), or a directory (its ``*.jpg`` / ``*.jpeg`` sorted by name).
+    ``workers`` threads (at most ``PNG_WORKERS_MAX``) read the files and undo their Huffman coding (``jpeg.entropy_decode``:
+    the library call releases the GIL) straight into one of two pinned staging buffers of coefficients and tables; every
+    chunk of ``frames_per_launch`` frames is uploaded without blocking and decoded by one ``refid_jpeg_decode``
+    (csrc/jpeg_decode.hip) on the current stream while the pool works on the next chunk.  A staging buffer is written again
+    only after the event behind its last upload has completed.  Files that differ in (H, W, components, sampling):
+    RefidHipError naming the first one; a file the decoder refuses (include/refid_hip.h lists what): RefidHipError with its
+    name and the library's message.  Does not synchronise at the end."""
+    from concurrent.futures import ThreadPoolExecutor
+    from . import jpeg, ops
+    items = _jpeg_sources(sources)
+    workers, per = int(workers), int(frames_per_launch)
+    if not items:
+        raise RefidHipError("load_jpeg_frames: no files")
+    if not 1 <= workers <= PNG_WORKERS_MAX or per < 1:
+        raise RefidHipError(f"load_jpeg_frames: workers {workers} must be 1..{PNG_WORKERS_MAX} and frames_per_launch {per} >= 1")
+    device = torch.device("cuda" if device is None else device)
+    if device.type != "cuda":
+        raise RefidHipError("load_jpeg_frames: a GPU device is required (the HIP path has no CPU fallback)")
+
+    def read(item):
+        name, src = item
+        if isinstance(src, bytes):
+            return src
+        with open(src, "rb") as f:
+            return f.read()
+
+    def probe(item, data):
+        try:
+            return jpeg.probe(data)
+        except RefidHipError as e:
+            raise RefidHipError(f"load_jpeg_frames: {item[0]}: {e}") from None
+
+    first = probe(items[0], read(items[0]))
+    h, w, comps, sampling, total = first.height, first.width, first.components, first.sampling, first.total_blocks
+    per = min(per, len(items))
+    chunks = [items[i:i + per] for i in range(0, len(items), per)]
+
+    def decode(item, coefs, quant):
+        data = read(item)
+        info = probe(item, data)
+        if info[:4] != first[:4]:
+            raise RefidHipError(f"load_jpeg_frames: {item[0]} is {info.height}x{info.width}, {info.components} components, sampling "
+                                f"{info.sampling}; {items[0][0]} is {h}x{w}, {comps}, {sampling}: the files of a sequence must share "
+                                "(H, W, components, sampling)")
+        try:
+            jpeg.entropy_decode(data, info, coefs, quant)
+        except RefidHipError as e:
+            raise RefidHipError(f"load_jpeg_frames: {item[0]}: {e}") from None
+
+    with ThreadPoolExecutor(max_workers=workers) as pool, torch.cuda.device(device):
+        out = torch.empty((len(items), h, w, 3), dtype=torch.uint8, device=device)
+        staging = [(torch.empty((per, total, 64), dtype=torch.int16).pin_memory(), torch.empty((per, comps, 64), dtype=torch.int16).pin_memory())
+                   for _ in range(min(2, len(chunks)))]
+        copied = [None] * len(staging)                     # the event after the upload that last read each buffer
+        ahead = collections.deque(maxlen=2)                # the chunks being decoded: the one in hand and the next
+
+        def submit(k):
+            if k < len(chunks):
+                if copied[k % 2] is not None:
+                    copied[k % 2].synchronize()
+                coefs, quant = (t.numpy() for t in staging[k % 2])
+                ahead.append([pool.submit(decode, item, coefs[i], quant[i].view(np.uint16)) for i, item in enumerate(chunks[k])])
+
+        submit(0)
+        submit(1)
+        for k, chunk in enumerate(chunks):
+            futures = ahead.popleft()
+            try:
+                for fut in futures:
+                    fut.result()
+            except BaseException:
+                for later in list(ahead) + [futures]:
+                    for f in later:
+                        f.cancel()
+                raise
+            n = len(chunk)
+            coefs_dev = torch.empty((n, total, 64), dtype=torch.int16, device=device)
+            quant_dev = torch.empty((n, comps, 64), dtype=torch.int16, device=device)
+            coefs_dev.copy_(staging[k % 2][0][:n], non_blocking=True)
+            quant_dev.copy_(staging[k % 2][1][:n], non_blocking=True)
+            copied[k % 2] = torch.cuda.Event()
+            copied[k % 2].record()
+            ops.jpeg_decode(coefs_dev, quant_dev, n, h, w, sampling, out=out[k * per:k * per + n])
+            submit(k + 2)
+    return out
+
+
+def load_key_frames(path, device=None, workers=8, frames_per_launch=8):
+    """The key frames of ``path`` -> uint8 (N, H, W, 3) RGB on the device: a directory of PNGs (``load_png_frames``), a
+    directory of JPEGs (``load_jpeg_frames``), or a Motion-JPEG ``*.avi`` (``video.read_mjpeg_avi``, then ``load_jpeg_frames``
+    on its frames; the parts ``stem.part002.avi`` ... of a split video follow in order).  A directory that holds both kinds
+    of file, or neither: RefidHipError."""
+    import glob
+    from . import video
+    path = os.fspath(path)
+    kw = dict(device=device, workers=workers, frames_per_launch=frames_per_launch)
+    if os.path.isdir(path):
+        pngs = sorted(glob.glob(os.path.join(path, "*.png")))
+        jpgs = sorted(glob.glob(os.path.join(path, "*.jpg")) + glob.glob(os.path.join(path, "*.jpeg")))
+        if pngs and jpgs:
+            raise RefidHipError(f"load_key_frames: {path} holds both PNG ({len(pngs)}) and JPEG ({len(jpgs)}) files: keep one kind")
+        if not pngs and not jpgs:
+            raise RefidHipError(f"load_key_frames: no *.png, *.jpg or *.jpeg under {path}")
+        return load_png_frames(pngs, **kw) if pngs else load_jpeg_frames(jpgs, **kw)
+    if path.lower().endswith(".avi"):
+        frames, part = [], 1
+        while part == 1 or os.path.exists(video.part_path(path, part)):
+            try:
+                frames += video.read_mjpeg_avi(video.part_path(path, part))[1]
+            except (OSError, ValueError) as e:
+                raise RefidHipError(f"load_key_frames: {e}") from None
+            part += 1
+        if not frames:
+            raise RefidHipError(f"load_key_frames: {path} holds no frames")
+        return load_jpeg_frames(frames, **kw)
+    raise RefidHipError(f"load_key_frames: {path} is neither a directory of PNG or JPEG files nor an .avi file")
+
+
 def _round_up(v, multiple):
     return (v + multiple - 1) // multiple * multiple
 
