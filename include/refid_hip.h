@@ -1031,6 +1031,88 @@ size_t refid_jpeg_decode_work_bytes(int32_t n_frames, int32_t height, int32_t wi
 /* blocks of one frame: fills blocks[3], returns their sum (0 for a geometry that is turned down) */
 int32_t refid_jpeg_decode_blocks(int32_t height, int32_t width, int32_t sampling, int32_t* blocks);
 
+/* ----------------------------------------------------------------------------------
+ * Simulated events (csrc/event_sim.hip): high-frame-rate uint8 frames -> the float32 (E, 4) rows [t, x, y, p] every event
+ * route takes, by the ESIM contrast-threshold model: a reference level per pixel in log intensity, an event at each
+ * threshold crossing, its time interpolated linearly between the two frames.  Integers only, apart from the three float64
+ * operations of the time stamp; tests/event_sim_ref.py restates all of it and the device is compared bit for bit.
+ *
+ * Inputs: frames uint8 (n_frames, height, width, 3), RGB or (bgr) BGR, n_frames >= 2; stamps float64 [n_frames], strictly
+ * increasing; lut int32 [256]; thresholds c_pos, c_neg int32 in units of 2^-16, each one scalar or a (height, width) map;
+ * state int32 (height, width), read and written.
+ *   Luma   Y8 = (19595 R + 38470 G + 7471 B + 32768) >> 16 (the coefficients of csrc/jpeg.hip).
+ *   Level  a = lut[Y8].  The default table (refid_amd.event_sim.default_lut) is rint(65536 ln(v / 255 + eps)) in float64 on the
+ *          host, eps = 1e-3, v = 0 .. 255; its span lut[255] - lut[0] is 452773.  The table is an argument: no transcendental
+ *          is evaluated on the device, and a caller may pass another monotone mapping.
+ *   State  ref = the level of the pixel's last event.  RESET sets ref = lut[Y8(frame 0)].  At every frame boundary
+ *          a - c_pos < ref < a + c_neg holds and is expected of a `state` that is passed in; rows from a state that breaks it
+ *          are unspecified (but bounded and inside their slots, see the cap).
+ *   Interval k, frame k to frame k + 1, per pixel, a = lut[Y8_k], b = lut[Y8_{k+1}], j = 0:
+ *          b > a: while ref + c_pos <= b: ref += c_pos, emit p = +1 with num = ref - a, den = b - a, ++j;
+ *          b < a: while ref - c_neg >= b: ref -= c_neg, emit p = -1 with num = a - ref, den = a - b, ++j;
+ *          b == a: nothing.   tick = (num 2^20) / den by 64-bit integer floor division, in (0, 2^20].
+ *   Time   t = fl32(t_k + (t_{k+1} - t_k) * (double(tick) 2^-20)): three float64 operations, each rounded once, no contraction.
+ *   Row    [t, x, y, p] float32, p = 1.0 or -1.0.
+ *   Order  ascending in (k, tick, y width + x, j); t is then non-decreasing in float32.  An event with tick = 2^20 carries
+ *          t_{k+1}: under a half-open window [t_k, t_{k+1}) it belongs to the next window.
+ *   Cap    at most REFID_EVENT_SIM_CAP (255) events per pixel and interval.  The entry turns down thresholds that could exceed
+ *          it, (lut_max - lut_min) / c_min + 1 > 255 (refid_event_sim_min_threshold gives the least threshold a table
+ *          allows: 1776 for the default table), where lut_min, lut_max and, for maps, c_min are the caller's statement about
+ *          device data.  Whatever the data, the device loop ends at 255 events and sets REFID_EVENT_SIM_FLAG_OVERFLOW in the
+ *          flag word; an EMIT lane stores only into its own slots and sets REFID_EVENT_SIM_FLAG_SLOTS when they do not fit
+ *          (the frames changed between the passes, or `ends` is not the prefix sum of `counts`).
+ *
+ * refid_event_sim launches the one kernel `stage` names on `stream`; it allocates nothing and does not synchronise:
+ *   RESET   reads frames (frame 0), lut; writes state.
+ *   COUNT   reads frames, lut, thresholds, state; writes counts[pix] = the pixel's rows over the chunk and ADDS the rows of
+ *           interval k to totals[k] (k < n_frames - 1) and ORs flags into totals[n_frames - 1]: zero `totals` first.
+ *   EMIT    reads the same and `ends` (the inclusive prefix sum of counts, int64), n_rows = ends[last]; writes the pixel's
+ *           rows to rows[ends[pix - 1] .. ends[pix]) in (k, j) order, one 16-byte store each, and the row's key
+ *           k << 54 | tick << 33 | pix << 8 | j to `keys`; writes state; ORs flags into totals[n_frames - 1].
+ *   GATHER  sorted[i] = rows[perm[i]], i < n_rows (perm: the permutation that sorts `keys`; the keys are unique, so it does
+ *           not depend on the sorting algorithm).
+ * Between COUNT and EMIT the caller reads the totals and the flag (one synchronisation).  Turned down with return 1 and a
+ * message that begins "event_sim:" and names the field, before any launch: a null or misaligned pointer (rows and sorted 16
+ * bytes; stamps_dev, totals, ends, keys, perm 8; the int32 arrays 4; frames any), n_frames < 2 or above
+ * REFID_EVENT_SIM_MAX_FRAMES (the key's 9 bits of k), height width above REFID_EVENT_SIM_MAX_PIXELS (its 25 bits of pix),
+ * a scalar threshold or c_min below 1, the cap condition, stamps that are not finite and strictly increasing, n_rows outside
+ * 1 .. 2^31 - 1 (use a smaller chunk).
+ * ---------------------------------------------------------------------------------- */
+#define REFID_EVENT_SIM_RESET 1
+#define REFID_EVENT_SIM_COUNT 2
+#define REFID_EVENT_SIM_EMIT 4
+#define REFID_EVENT_SIM_GATHER 8
+#define REFID_EVENT_SIM_CAP 255
+#define REFID_EVENT_SIM_MAX_FRAMES 512
+#define REFID_EVENT_SIM_MAX_PIXELS 33554432
+#define REFID_EVENT_SIM_FLAG_OVERFLOW 1
+#define REFID_EVENT_SIM_FLAG_SLOTS 2
+typedef struct refid_event_sim_desc {
+    const uint8_t* frames;                      /* device: n_frames * height * width * 3 bytes                      */
+    const double* stamps_host;                  /* host:   n_frames stamps (checked here)                           */
+    const double* stamps_dev;                   /* device: the same stamps (read by EMIT)                           */
+    const int32_t* lut;                         /* device: 256 levels                                               */
+    const int32_t* c_pos_map;                   /* device: (height, width) thresholds, or null: the scalar c_pos    */
+    const int32_t* c_neg_map;                   /* device: (height, width) thresholds, or null: the scalar c_neg    */
+    int32_t* state;                             /* device: (height, width) reference levels                         */
+    int32_t* counts;                            /* device: (height, width) rows per pixel (COUNT writes)            */
+    int64_t* totals;                            /* device: n_frames words: rows per interval, then the flag word    */
+    const int64_t* ends;                        /* device: (height, width) inclusive prefix sum of counts (EMIT)    */
+    float* rows;                                /* device: n_rows * 4, in pixel order (EMIT writes, GATHER reads)   */
+    int64_t* keys;                              /* device: n_rows sort keys (EMIT writes)                           */
+    const int64_t* perm;                        /* device: n_rows indices into rows (GATHER)                        */
+    float* sorted;                              /* device: n_rows * 4, the result (GATHER writes)                   */
+    int64_t n_rows;
+    int32_t n_frames, height, width, bgr;
+    int32_t c_pos, c_neg;                       /* scalar thresholds, units of 2^-16 (used where the map is null)   */
+    int32_t c_min;                              /* the maps' smallest value (read only when a map is given)         */
+    int32_t lut_min, lut_max;                   /* the table's smallest and largest level                           */
+    int32_t stage;                              /* one of REFID_EVENT_SIM_RESET, _COUNT, _EMIT, _GATHER             */
+} refid_event_sim_desc;
+int refid_event_sim(const refid_event_sim_desc* d, void* stream);
+/* the least threshold the cap allows for a table with these extremes (0: lut_max < lut_min, or none fits int32) */
+int32_t refid_event_sim_min_threshold(int32_t lut_min, int32_t lut_max);
+
 #ifdef __cplusplus
 }
 #endif

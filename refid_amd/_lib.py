@@ -196,6 +196,19 @@ class JpegDecodeDesc(C.Structure):
     ]
 
 
+class EventSimDesc(C.Structure):
+    """refid_event_sim_desc: uint8 frames + stamps -> event rows [t, x, y, p] by the ESIM model; ``stage`` names the launch."""
+    _fields_ = [
+        ("frames", C.c_void_p), ("stamps_host", C.c_void_p), ("stamps_dev", C.c_void_p), ("lut", C.c_void_p),
+        ("c_pos_map", C.c_void_p), ("c_neg_map", C.c_void_p), ("state", C.c_void_p), ("counts", C.c_void_p), ("totals", C.c_void_p),
+        ("ends", C.c_void_p), ("rows", C.c_void_p), ("keys", C.c_void_p), ("perm", C.c_void_p), ("sorted", C.c_void_p),
+        ("n_rows", C.c_int64),
+        ("n_frames", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("bgr", C.c_int32),
+        ("c_pos", C.c_int32), ("c_neg", C.c_int32), ("c_min", C.c_int32), ("lut_min", C.c_int32), ("lut_max", C.c_int32),
+        ("stage", C.c_int32),
+    ]
+
+
 LAYOUT_BLUR, LAYOUT_SHARP = 0, 1                # == REFID_LAYOUT_* in include/refid_hip.h
 ASSEMBLE_ZERO, ASSEMBLE_SCATTER, ASSEMBLE_FINISH, ASSEMBLE_FRAMES, ASSEMBLE_ALL = 1, 2, 4, 8, 15
 ASSEMBLE_STATS = 16                              # refid_assemble_single only: voxel_norm's statistics, between scatter and finish
@@ -213,6 +226,11 @@ JPEG_444, JPEG_420 = 0, 1          # == REFID_JPEG_444 / REFID_JPEG_420 in inclu
 JPEG_HEADER_BYTES = 625            # == REFID_JPEG_HEADER_BYTES in include/refid_hip.h
 JPEG_BLOCK_BITS = 1660             # == REFID_JPEG_BLOCK_BITS in include/refid_hip.h
 JPEG_DEC_GREY, JPEG_DEC_444, JPEG_DEC_422, JPEG_DEC_420 = 0, 1, 2, 3    # == REFID_JPEG_DEC_* in include/refid_hip.h
+EVENT_SIM_RESET, EVENT_SIM_COUNT, EVENT_SIM_EMIT, EVENT_SIM_GATHER = 1, 2, 4, 8    # == REFID_EVENT_SIM_* in include/refid_hip.h
+EVENT_SIM_CAP = 255                # == REFID_EVENT_SIM_CAP in include/refid_hip.h
+EVENT_SIM_MAX_FRAMES = 512         # == REFID_EVENT_SIM_MAX_FRAMES in include/refid_hip.h
+EVENT_SIM_MAX_PIXELS = 1 << 25     # == REFID_EVENT_SIM_MAX_PIXELS in include/refid_hip.h
+EVENT_SIM_FLAG_OVERFLOW, EVENT_SIM_FLAG_SLOTS = 1, 2    # == REFID_EVENT_SIM_FLAG_* in include/refid_hip.h
 ABI_VERSION = 9          # == REFID_ABI_VERSION in include/refid_hip.h
 _lib = None
 
@@ -363,6 +381,9 @@ def _bind_extra(L):
     L.refid_jpeg_decode_work_bytes.restype = C.c_size_t
     L.refid_jpeg_decode_blocks.argtypes = [C.c_int32] * 3 + [C.POINTER(C.c_int32)]
     L.refid_jpeg_decode_blocks.restype = C.c_int32
+    L.refid_event_sim.argtypes = [C.POINTER(EventSimDesc), vp]
+    L.refid_event_sim_min_threshold.argtypes = [C.c_int32, C.c_int32]
+    L.refid_event_sim_min_threshold.restype = C.c_int32
     L.refid_score_u8_parts.argtypes = [i, i, i, i]
     L.refid_score_u8_parts.restype = ll
     L.refid_score_u8.argtypes = [vp, vp, i, i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp]

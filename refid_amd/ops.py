@@ -2,12 +2,14 @@
 
 Tensors are NHWC fp32 on the GPU: shape (N, H, W, C) with stride(-1) == 1; the pixel
 pitch may exceed C (channel-slice views of wider buffers).  torch is used here only
-for device memory and streams; all arithmetic happens in librefid_hip.so.
+for device memory and streams; all arithmetic happens in librefid_hip.so (one stated
+exception: ``event_sim`` puts ``torch.cumsum`` and ``torch.sort`` between its launches).
 """
 import collections
 import ctypes as C
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1299,3 +1301,125 @@ def score_u8(a_u8, b_u8, bgr=False, crop_border=0, sq_rgb=True, sq_y=False, ssim
                                ptr(out[0], sq_rgb), ptr(out[1], sq_y), ptr(out[2], ssim3d), ptr(out[3], ssim_y),
                                buf[4 * nf:].data_ptr(), ptr(ya), ptr(ymap), _stream()), "refid_score_u8")
     return (out, [ya, ymap]) if taps else out
+
+
+def _event_sim_threshold(name, c, h, w, device):
+    """(scalar, map tensor or None) of one threshold argument of ``event_sim``."""
+    if torch.is_tensor(c):
+        if not c.is_cuda or c.device != device or c.dtype != torch.int32 or tuple(c.shape) != (h, w) or not c.is_contiguous():
+            raise _lib.RefidHipError(f"event_sim: a {name} map must be a contiguous int32 ({h}, {w}) tensor on {device}, got {c.dtype} "
+                                     f"{tuple(c.shape)} on {c.device}")
+        return 0, c
+    if isinstance(c, bool) or not isinstance(c, (int, np.integer)):
+        raise _lib.RefidHipError(f"event_sim: {name} must be an int in units of 2^-16 or an int32 ({h}, {w}) map, got {type(c).__name__}")
+    if not 1 <= int(c) < 2 ** 31:
+        raise _lib.RefidHipError(f"event_sim: {name} {int(c)} must be 1 .. 2^31 - 1 (units of 2^-16)")
+    return int(c), None
+
+
+def event_sim_reset(frame_u8, lut, state=None, bgr=False):
+    """RESET of refid_event_sim on the current stream: ``state`` int32 (H, W) = lut[Y8(frame)] for a uint8 (H, W, 3) CUDA
+    frame.  Does not synchronise."""
+    if not torch.is_tensor(frame_u8) or not frame_u8.is_cuda or frame_u8.dtype != torch.uint8 or frame_u8.dim() != 3 or \
+            frame_u8.shape[2] != 3 or not frame_u8.is_contiguous() or frame_u8.numel() == 0:
+        raise _lib.RefidHipError("event_sim_reset: the frame must be a contiguous non-empty uint8 (H, W, 3) CUDA tensor (no CPU fallback), got "
+                                 + (f"{frame_u8.dtype} {tuple(frame_u8.shape)} on {frame_u8.device}" if torch.is_tensor(frame_u8)
+                                    else type(frame_u8).__name__))
+    h, w = int(frame_u8.shape[0]), int(frame_u8.shape[1])
+    dev = frame_u8.device
+    if not torch.is_tensor(lut) or lut.device != dev or lut.dtype != torch.int32 or tuple(lut.shape) != (256,) or not lut.is_contiguous():
+        raise _lib.RefidHipError(f"event_sim_reset: lut must be a contiguous int32 (256,) tensor on {dev}")
+    if state is None:
+        state = torch.empty((h, w), dtype=torch.int32, device=dev)
+    elif not torch.is_tensor(state) or state.device != dev or state.dtype != torch.int32 or tuple(state.shape) != (h, w) or \
+            not state.is_contiguous():
+        raise _lib.RefidHipError(f"event_sim_reset: state must be a contiguous int32 ({h}, {w}) tensor on {dev}")
+    desc = _lib.EventSimDesc(frames=frame_u8.data_ptr(), lut=lut.data_ptr(), state=state.data_ptr(), n_frames=1, height=h, width=w,
+                             bgr=int(bool(bgr)), stage=_lib.EVENT_SIM_RESET)
+    check(lib().refid_event_sim(C.byref(desc), _stream()), "refid_event_sim (reset)")
+    return state
+
+
+def event_sim(frames_u8, stamps, state, lut, c_pos, c_neg, bgr=False, lut_range=None, c_min=None):
+    """refid_event_sim (csrc/event_sim.hip) on the current stream: the events of the N - 1 intervals of ``frames_u8`` uint8
+    (N, H, W, 3) on the device (a contiguous view of any alignment), by the ESIM model of include/refid_hip.h ->
+    ``(rows, offsets)``: ``rows`` float32 (E, 4) [t, x, y, p] on the device, ascending in (interval, tick, pixel, j) and so
+    non-decreasing in t; ``offsets`` int64 (N,) on the host, interval k's rows being [offsets[k], offsets[k+1]).  An event
+    exactly at stamps[k+1] (tick 2^20) lies in interval k's rows but, under ``sequence.pair_windows``' half-open rule,
+    in the time window that begins at stamps[k+1].
+
+    ``stamps``: N strictly increasing float64 on the host.  ``state`` int32 (H, W) on the device, the pixels' reference
+    levels: read, and written with the levels after the last frame (``event_sim_reset`` makes the first one).  ``lut``
+    int32 (256,) on the device.  ``c_pos`` / ``c_neg``: an int in units of 2^-16, or an int32 (H, W) map on the device.
+    ``lut_range`` = (min, max) of the table and ``c_min`` = the smallest value of the maps, when the caller knows them
+    (``event_sim.EventSimulator`` reduces once at construction); None: reduced here, one more synchronisation each.
+
+    Launches: count, ``torch.cumsum`` over the pixels, ONE synchronisation that reads the per-interval totals, the overflow
+    flag and E, emit, ``torch.sort`` of the unique 64-bit keys, gather.  E = 0 returns an empty (0, 4) tensor after the
+    synchronisation, without an emit launch.  A pixel with more than 255 events in an interval (only maps or tables that
+    belie ``c_min`` / ``lut_range`` get that far) raises RefidHipError and leaves ``state`` as it was; so does E >= 2^31."""
+    if not torch.is_tensor(frames_u8) or not frames_u8.is_cuda or frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or \
+            frames_u8.shape[3] != 3 or not frames_u8.is_contiguous():
+        raise _lib.RefidHipError("event_sim: frames must be a contiguous uint8 (N, H, W, 3) CUDA tensor (no CPU fallback), got "
+                                 + (f"{frames_u8.dtype} {tuple(frames_u8.shape)} on {frames_u8.device}" if torch.is_tensor(frames_u8)
+                                    else type(frames_u8).__name__))
+    n, h, w = (int(v) for v in frames_u8.shape[:3])
+    dev = frames_u8.device
+    if n < 2:
+        raise _lib.RefidHipError(f"event_sim: frames holds N={n} frames, at least 2 are needed")
+    if n > _lib.EVENT_SIM_MAX_FRAMES:
+        raise _lib.RefidHipError(f"event_sim: N={n} frames exceed {_lib.EVENT_SIM_MAX_FRAMES} in one call: use a smaller chunk")
+    if h < 1 or w < 1 or h * w > _lib.EVENT_SIM_MAX_PIXELS:
+        raise _lib.RefidHipError(f"event_sim: height {h} * width {w} must be 1 .. {_lib.EVENT_SIM_MAX_PIXELS} pixels (what the sort key holds)")
+    stamps_host = np.ascontiguousarray(np.asarray(stamps.cpu() if torch.is_tensor(stamps) else stamps, dtype=np.float64).reshape(-1))
+    if stamps_host.shape != (n,):
+        raise _lib.RefidHipError(f"event_sim: {stamps_host.size} stamps for N={n} frames")
+    if not np.all(np.isfinite(stamps_host)) or not np.all(stamps_host[1:] > stamps_host[:-1]):
+        raise _lib.RefidHipError("event_sim: stamps must be finite and strictly increasing")
+    if not torch.is_tensor(state) or state.device != dev or state.dtype != torch.int32 or tuple(state.shape) != (h, w) or not state.is_contiguous():
+        raise _lib.RefidHipError(f"event_sim: state must be a contiguous int32 ({h}, {w}) tensor on {dev}")
+    if not torch.is_tensor(lut) or lut.device != dev or lut.dtype != torch.int32 or tuple(lut.shape) != (256,) or not lut.is_contiguous():
+        raise _lib.RefidHipError(f"event_sim: lut must be a contiguous int32 (256,) tensor on {dev}")
+    cp, cp_map = _event_sim_threshold("c_pos", c_pos, h, w, dev)
+    cn, cn_map = _event_sim_threshold("c_neg", c_neg, h, w, dev)
+    if lut_range is None:
+        host = lut.cpu()
+        lut_range = (int(host.min()), int(host.max()))
+    maps = [m for m in (cp_map, cn_map) if m is not None]
+    if maps and c_min is None:
+        c_min = min(int(m.min()) for m in maps)
+    c_min = int(c_min) if maps else 0
+    L = lib()
+    stamps_dev = torch.from_numpy(stamps_host).to(dev)
+    counts = torch.empty((h * w,), dtype=torch.int32, device=dev)
+    totals = torch.zeros((n + 1,), dtype=torch.int64, device=dev)          # rows per interval, the flag word, then E
+    ptr = lambda t: t.data_ptr() if t is not None else None               # noqa: E731
+    desc = _lib.EventSimDesc(frames=frames_u8.data_ptr(), stamps_host=stamps_host.ctypes.data, stamps_dev=stamps_dev.data_ptr(),
+                             lut=lut.data_ptr(), c_pos_map=ptr(cp_map), c_neg_map=ptr(cn_map), state=state.data_ptr(),
+                             counts=counts.data_ptr(), totals=totals.data_ptr(), n_frames=n, height=h, width=w, bgr=int(bool(bgr)),
+                             c_pos=cp, c_neg=cn, c_min=c_min, lut_min=lut_range[0], lut_max=lut_range[1], stage=_lib.EVENT_SIM_COUNT)
+    check(L.refid_event_sim(C.byref(desc), _stream()), "refid_event_sim (count)")
+    ends = torch.cumsum(counts, 0, dtype=torch.int64)
+    totals[n:].copy_(ends[-1:])
+    host = totals.cpu()                                                     # the call's one synchronisation
+    per_interval, flag, total = host[:n - 1].numpy(), int(host[n - 1]), int(host[n])
+    offsets = np.zeros((n,), dtype=np.int64)
+    np.cumsum(per_interval, out=offsets[1:])
+    if flag & _lib.EVENT_SIM_FLAG_OVERFLOW:
+        raise _lib.RefidHipError(f"event_sim: overflow: a pixel has more than {_lib.EVENT_SIM_CAP} events in one interval (a threshold or a "
+                                 f"table entry lies outside what c_min / lut_range state); state is unchanged")
+    if total != int(offsets[-1]):
+        raise _lib.RefidHipError(f"event_sim: the per-pixel rows sum to {total}, the per-interval rows to {int(offsets[-1])}")
+    if total >= 2 ** 31:
+        raise _lib.RefidHipError(f"event_sim: E={total} rows in one call reach 2^31: use a smaller chunk")
+    if total == 0:
+        return torch.empty((0, 4), dtype=torch.float32, device=dev), offsets
+    rows = torch.empty((total, 4), dtype=torch.float32, device=dev)
+    keys = torch.empty((total,), dtype=torch.int64, device=dev)
+    desc.ends, desc.rows, desc.keys, desc.n_rows, desc.stage = ends.data_ptr(), rows.data_ptr(), keys.data_ptr(), total, _lib.EVENT_SIM_EMIT
+    check(L.refid_event_sim(C.byref(desc), _stream()), "refid_event_sim (emit)")
+    perm = torch.sort(keys)[1]
+    out = torch.empty_like(rows)
+    desc.perm, desc.sorted, desc.stage = perm.data_ptr(), out.data_ptr(), _lib.EVENT_SIM_GATHER
+    check(L.refid_event_sim(C.byref(desc), _stream()), "refid_event_sim (gather)")
+    return out, offsets
