@@ -14,6 +14,7 @@
 // the pixel rows of a wave -> the four waves in order through LDS -> one partial row per workgroup in the
 // caller's scratch -> a second tiny kernel adds the rows in a fixed order.  No floating-point atomics.
 #include "common.h"
+#include "workgroup.h"
 #include <vector>
 #include <cstring>
 
@@ -47,8 +48,7 @@ __global__ __launch_bounds__(256) void rows_sum_kernel(const float* __restrict__
     if (i >= ncols) return;
     float a = 0.f;
     for (int b = lane; b < nrows; b += 64) a += parts[(long long)b * ncols + i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+    a = refid_wave_sum(a);
     if (lane == 0) {
         float* d = i < n_a ? dst_a + i : dst_b + (i - n_a);
         *d = accumulate ? *d + a : a;
@@ -81,8 +81,7 @@ __global__ __launch_bounds__(256) void rows_sum_batch_kernel(const RowsBatch b) 
         const int nrows = b.job[j].nrows;
         float a = 0.f;
         for (int r = lane; r < nrows; r += 64) a += parts[(long long)r * g.ncols + i];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+        a = refid_wave_sum(a);
         tot += a;
     }
     if (lane == 0) *d = tot;
@@ -381,8 +380,7 @@ __global__ __launch_bounds__(256) void se_fwd_kernel(const float* __restrict__ p
     for (int j = wave; j < Ch; j += 4) {
         float a = 0.f;
         for (int c = lane; c < C; c += 64) a += W1[j * C + c] * sm[c];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+        a = refid_wave_sum(a);
         if (lane == 0) {
             a += b1[j];
             a = a > 0.f ? a : 0.f;
@@ -393,8 +391,7 @@ __global__ __launch_bounds__(256) void se_fwd_kernel(const float* __restrict__ p
     for (int c = wave; c < C; c += 4) {
         float a = 0.f;
         for (int j = lane; j < Ch; j += 64) a += W2[c * Ch + j] * sz[j];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+        a = refid_wave_sum(a);
         if (lane == 0) s[n * C + c] = 1.f / (1.f + __expf(-(a + b2[c])));
     }
 }
@@ -592,8 +589,7 @@ __global__ __launch_bounds__(64) void fold_back_kernel(const float* __restrict__
         a += W[(long long)r * K + k] * gf;
         G[(long long)r * K + k] += sc * gf;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+    a = refid_wave_sum(a);
     if (threadIdx.x == 0) {
         dscale[r] += a + b[r] * gbf[r];
         gb[r] += sc * gbf[r];

@@ -19,6 +19,7 @@
 // occupancy is bounded by the grid, not by registers or LDS (3 KiB).  The time goes to the frames' bytes (read once per
 // pass) and, where events are dense, to the 64-bit division per event and the scattered 16-byte row stores.
 #include "common.h"
+#include "workgroup.h"
 
 namespace {
 
@@ -121,9 +122,7 @@ __global__ __launch_bounds__(ESIM_THREADS) void esim_walk(const EsimArgs p) {
             }
         }
         if (!EMIT) {
-            unsigned sum = cnt;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+            const unsigned sum = refid_wave_sum(cnt);
             if ((tid & 63) == 0 && sum) atomicAdd(&s_rows[k], sum);
         }
         total += cnt;

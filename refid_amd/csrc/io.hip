@@ -8,6 +8,7 @@
 // callers that want a full grid; the training path does not need it any more: sample.hip voxelises the float32 event
 // rows of the datasets inside the crop with integer (bit-reproducible) sums while it assembles the batch.
 #include "common.h"
+#include "workgroup.h"
 #include "ssim3d_tile.h"
 
 namespace {
@@ -48,11 +49,8 @@ __global__ __launch_bounds__(256) void sqerr_u8_kernel(const float* __restrict__
         const float d = quant255(pa[i]) - quant255(pb[i]);
         acc += (double)(d * d);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) sq[f * gridDim.x + blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];   // partial [frame][chunk]
+    const double t = refid_block_sum<double, 4>(acc, sh);
+    if (threadIdx.x == 0) sq[f * gridDim.x + blockIdx.x] = t;   // partial [frame][chunk]
 }
 
 // acc[c][i0+y][j0+x] += tile[c][y][x] ; cnt[i0+y][j0+x] += 1     (one tile)
@@ -127,15 +125,6 @@ __device__ __forceinline__ void val_store_row(unsigned char* __restrict__ dst, c
     else if (j == 13) { for (int k = head + 4 * nd; k < nv; ++k) dst[k] = src[k]; }
 }
 
-// Sum over the workgroup of per-thread integer squared errors (each <= 3 * 255^2); thread 0 returns the total.
-__device__ __forceinline__ unsigned long long val_block_sum(unsigned v, unsigned* sh) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (unsigned long long)sh[0] + sh[1] + sh[2] + sh[3];
-}
-
 template <bool SSIM>
 __global__ __launch_bounds__(256) void val_tail_kernel(const float* __restrict__ a, const float* __restrict__ b, int H, int W,
                                                       int tiles_x, int tiles_y, int bgr, const SsimConst k,
@@ -191,7 +180,7 @@ __global__ __launch_bounds__(256) void val_tail_kernel(const float* __restrict__
                 d2 += (unsigned)(d * d);
             }
         }
-        const unsigned long long s = val_block_sum(d2, sqred);
+        const unsigned long long s = refid_block_sum<unsigned long long, 4>(d2, sqred);     // (each d2 <= 3 * 255^2)
         if (threadIdx.x == 0) sq_parts[blockIdx.x] = s;
     }
     if constexpr (SSIM) {
@@ -209,11 +198,8 @@ __global__ __launch_bounds__(256) void sum_rows_u64_kernel(const unsigned long l
     const unsigned long long* p = part + (long long)blockIdx.x * n;
     unsigned long long acc = 0;
     for (int i = threadIdx.x; i < n; i += 256) acc += p[i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) out[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
+    const unsigned long long t = refid_block_sum<unsigned long long, 4>(acc, sh);
+    if (threadIdx.x == 0) out[blockIdx.x] = t;
 }
 
 int nb(long long n) { long long b = (n + 255) / 256; return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b)); }

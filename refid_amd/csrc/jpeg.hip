@@ -8,17 +8,20 @@
 //     its block's pixels (clamped coordinates: the replicated edge), averages chroma, runs the two integer DCT passes in
 //     registers, quantises and leaves the 64 zig-zag coefficients in LDS.  The DC predictor is the DC of the lane 1, 3 or
 //     6 places before (the last eight of a pass are carried to the next).  A first walk over the coefficients adds up the
-//     block's bits, a workgroup prefix sum gives its bit position, a second walk ORs the codes into an LDS image of the
-//     segment's words (LDS integer or: order-free; bits are MSB first, so a word is byte-swapped when it leaves).  The
-//     image's complete words go to the segment's room in `work` as aligned dword stores, counted for FF bytes on the way;
-//     the incomplete word opens the next pass.  The segment's record gets its length before and after stuffing.
-//   jpeg_offsets_kernel  one workgroup per frame.  Exclusive sum of the stuffed lengths (+2 for each RSTm) into the records,
-//     then, if the file fits the pitch, the header (a kernel argument, built on the host), EOI and lens; else lens = -need.
+//     block's bits, a workgroup prefix sum gives its bit position, a second walk puts the codes MSB first into the LDS
+//     image of bit_image.h (writer, retire step and their barrier contract are stated there).  The sink byte-swaps a
+//     complete word, counts its FF bytes and parks it in the segment's room in `work` (aligned dword stores).  The
+//     segment's record gets its length before and after stuffing.
+//   jpeg_offsets_kernel  one workgroup per frame.  Exclusive sum of the stuffed lengths (+2 for each RSTm) into the records
+//     (the chunk walk of bit_image.h), then, if the file fits the pitch, the header (a kernel argument, built on the
+//     host), EOI and lens; else lens = -need.
 //   jpeg_place_kernel    one workgroup per segment.  RSTm, then the parked bytes with 00 after every FF: a lane takes 16
 //     consecutive bytes, a workgroup prefix sum of 1 + (byte == FF) gives its place, bytes are stored one by one (out has
 //     no alignment).  No global atomics, no read-modify-write of a global word; nothing outside the segment's bytes is
 //     written.
+// The scan is that of workgroup.h.
 #include "common.h"
+#include "bit_image.h"
 #include "jpeg_tables.h"
 #include <initializer_list>
 
@@ -90,39 +93,7 @@ struct JpegGeom {
 struct JpegQuant { uint8_t q[2][64]; };                        // zig-zag order, as in DQT
 struct JpegHeader { uint8_t b[(REFID_JPEG_HEADER_BYTES + 3) / 4 * 4]; };
 
-// exclusive prefix sum over the workgroup of NW waves in thread order; *total = the sum
-template <int NW>
-__device__ __forceinline__ unsigned jpeg_block_scan(unsigned v, unsigned* red, unsigned* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned up = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += up;
-    }
-    __syncthreads();                                           // (red may still be read from the call before)
-    if (lane == 63) red[wave] = inc;
-    __syncthreads();
-    unsigned before = 0, sum = 0;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) before += w < wave ? red[w] : 0u, sum += red[w];
-    *total = sum;
-    return before + inc - v;
-}
-
-// the low n bits of v (n <= 26) go to the stream at `word`, of which `filled` (< 32) bits are taken; acc holds them MSB first
-struct JpegPut {
-    unsigned long long acc;
-    unsigned filled, word;
-};
-__device__ __forceinline__ void jpeg_put(JpegPut& p, unsigned* image, unsigned v, unsigned n) {
-    p.acc |= (unsigned long long)v << (64u - p.filled - n);
-    p.filled += n;
-    if (p.filled >= 32u) {
-        atomicOr(&image[p.word], (unsigned)(p.acc >> 32));
-        p.acc <<= 32, p.filled -= 32u, ++p.word;
-    }
-}
+constexpr RefidBitOrder JPEG_ORDER = REFID_BITS_MSB_FIRST;     // T.81: the most significant bit of a code comes first
 
 __device__ __forceinline__ unsigned jpeg_category(int v) { return 32u - (unsigned)__clz(v < 0 ? -v : v); }    // (__clz(0) = 32)
 __device__ __forceinline__ unsigned jpeg_ff_bytes(unsigned v) {
@@ -241,41 +212,35 @@ __global__ __launch_bounds__(JPEG_BLOCKS) void jpeg_code_kernel(const uint8_t* _
             if (run) bits += eob >> 16;
         }
         unsigned total = 0;
-        const unsigned at = cursor + jpeg_block_scan<JPEG_BLOCKS / 64>(bits, red, &total) - 32u * (unsigned)w0;    // bit position in the image
+        const unsigned at = cursor + refid_block_scan<JPEG_BLOCKS / 64>(bits, red, &total) - 32u * (unsigned)w0;    // bit position in the image
         if (tid >= JPEG_BLOCKS - 8) dcs[tid - (JPEG_BLOCKS - 8)] = dcs[8 + tid];       // (dcs[0..8) was last read before the scan's barriers)
         if (active) {
-            JpegPut p = {0ull, at & 31u, at >> 5};
+            RefidBitWriter<JPEG_ORDER> p(at);                  // (a code and its value bits: at most 16 + 11 bits a put)
             const unsigned e = hdc[tbl][dc_cat];
-            jpeg_put(p, image, ((e & 0xffffu) << dc_cat) | ((unsigned)(diff < 0 ? diff - 1 : diff) & ((1u << dc_cat) - 1u)), (e >> 16) + dc_cat);
+            p.put(image, ((e & 0xffffu) << dc_cat) | ((unsigned)(diff < 0 ? diff - 1 : diff) & ((1u << dc_cat) - 1u)), (e >> 16) + dc_cat);
             unsigned run = 0;
             for (int k = 1; k < 64; ++k) {
                 const int v = coef[k][tid];
                 if (v == 0) {
                     ++run;
                 } else {
-                    for (; run > 15u; run -= 16u) jpeg_put(p, image, zrl & 0xffffu, zrl >> 16);
+                    for (; run > 15u; run -= 16u) p.put(image, zrl & 0xffffu, zrl >> 16);
                     const unsigned cat = jpeg_category(v);
                     const unsigned c = hac[tbl][(run << 4) | cat];
-                    jpeg_put(p, image, ((c & 0xffffu) << cat) | ((unsigned)(v < 0 ? v - 1 : v) & ((1u << cat) - 1u)), (c >> 16) + cat);
+                    p.put(image, ((c & 0xffffu) << cat) | ((unsigned)(v < 0 ? v - 1 : v) & ((1u << cat) - 1u)), (c >> 16) + cat);
                     run = 0;
                 }
             }
-            if (run) jpeg_put(p, image, eob & 0xffffu, eob >> 16);
-            if (p.filled) atomicOr(&image[p.word], (unsigned)(p.acc >> 32));
+            if (run) p.put(image, eob & 0xffffu, eob >> 16);
+            p.flush(image);
         }
         cursor += total;
         __syncthreads();                                       // the pass's bits are in the image
-        // the complete words leave; the incomplete one opens the next image
-        const int n_full = (int)(cursor >> 5) - w0;
-        const unsigned carry = image[n_full];
-        for (int i = tid; i < n_full; i += JPEG_BLOCKS) {
-            const unsigned v = image[i];
+        // the complete words leave; the incomplete one opens the next image (the barrier at the top of the pass closes it)
+        refid_bits_retire<JPEG_BLOCKS>(image, cursor, w0, [&ff, parked](int w, unsigned v) {
             ff += jpeg_ff_bytes(v);
-            parked[w0 + i] = __builtin_bswap32(v);
-        }
-        __syncthreads();
-        for (int i = tid; i <= n_full; i += JPEG_BLOCKS) image[i] = i == 0 ? carry : 0u;
-        w0 += n_full;
+            parked[w] = __builtin_bswap32(v);
+        });
     }
     __syncthreads();
     // padding to a byte with 1-bits; the last, incomplete word: only its bytes below the segment's end count
@@ -290,7 +255,7 @@ __global__ __launch_bounds__(JPEG_BLOCKS) void jpeg_code_kernel(const uint8_t* _
         for (unsigned k = 0; k < n; ++k) ff += ((v >> (24u - 8u * k)) & 0xffu) == 0xffu;
     }
     unsigned ff_total = 0;
-    jpeg_block_scan<JPEG_BLOCKS / 64>(ff, red, &ff_total);
+    refid_block_scan<JPEG_BLOCKS / 64>(ff, red, &ff_total);
     if (tid == 0) {
         rec[JPEG_REC_RAW] = end_bytes;
         rec[JPEG_REC_STUFFED] = end_bytes + ff_total;
@@ -302,20 +267,17 @@ __global__ __launch_bounds__(JPEG_THREADS) void jpeg_offsets_kernel(uint8_t* __r
     __shared__ unsigned red[JPEG_THREADS / 64];
     const int tid = threadIdx.x, f = blockIdx.x;
     unsigned* rec = work + (long long)f * g.segs * JPEG_REC;
-    const int per = (g.segs + JPEG_THREADS - 1) / JPEG_THREADS;
-    const int lo = min(tid * per, g.segs), hi = min(lo + per, g.segs);        // (tid * per < 2^31: per <= 2^23)
-    unsigned bytes = 0;                                        // (the sum is below the bound, which fits int32)
-    for (int j = lo; j < hi; ++j) bytes += rec[(long long)j * JPEG_REC + JPEG_REC_STUFFED] + (j ? 2u : 0u);
-    unsigned total = 0;
-    unsigned off = REFID_JPEG_HEADER_BYTES + jpeg_block_scan<JPEG_THREADS / 64>(bytes, red, &total);
-    total += REFID_JPEG_HEADER_BYTES + 2;
-    const bool fits = total <= (unsigned)g.out_pitch;
-    for (int j = lo; j < hi; ++j) {
-        unsigned* r = rec + (long long)j * JPEG_REC;
-        r[JPEG_REC_OFF] = off;                                 // where its RSTm (segment 0: its first byte) goes
-        r[JPEG_REC_FITS] = fits ? 1u : 0u;
-        off += r[JPEG_REC_STUFFED] + (j ? 2u : 0u);
-    }
+    // a segment's bytes in the file: stuffed, and RSTm in front of all but the first (the sum is below the bound, which fits int32)
+    const unsigned need = REFID_JPEG_HEADER_BYTES + 2;         // around the segments: the header and EOI
+    const unsigned pitch = (unsigned)g.out_pitch;
+    const unsigned total = need + refid_chunk_offsets<JPEG_THREADS>(
+        g.segs, red, [rec](int j) { return rec[(long long)j * JPEG_REC + JPEG_REC_STUFFED] + (j ? 2u : 0u); },
+        [rec, need, pitch](int j, unsigned off, unsigned sum) {
+            unsigned* r = rec + (long long)j * JPEG_REC;
+            r[JPEG_REC_OFF] = REFID_JPEG_HEADER_BYTES + off;   // where its RSTm (segment 0: its first byte) goes
+            r[JPEG_REC_FITS] = need + sum <= pitch ? 1u : 0u;
+        });
+    const bool fits = total <= pitch;
     if (fits) {
         uint8_t* o = out + (long long)f * g.out_pitch;
         for (int i = tid; i < REFID_JPEG_HEADER_BYTES; i += JPEG_THREADS) o[i] = header.b[i];
@@ -350,7 +312,7 @@ __global__ __launch_bounds__(JPEG_THREADS) void jpeg_place_kernel(uint8_t* __res
 #pragma unroll
         for (int k = 0; k < JPEG_PER_THREAD; ++k) n += k < mine ? 1u + (((d[k >> 2] >> (8 * (k & 3))) & 0xffu) == 0xffu) : 0u;
         unsigned total = 0;
-        unsigned at = cursor + jpeg_block_scan<JPEG_THREADS / 64>(n, red, &total);
+        unsigned at = cursor + refid_block_scan<JPEG_THREADS / 64>(n, red, &total);
 #pragma unroll
         for (int k = 0; k < JPEG_PER_THREAD; ++k) {
             if (k < mine) {

@@ -127,6 +127,7 @@ __global__ __launch_bounds__(NQ_THREADS) void niqe_moments_kernel(const unsigned
         double e[5] = {(double)cnt[m][0], (double)cnt[m][1], acc[m][0], acc[m][1], acc[m][2]};
 #pragma unroll
         for (int q = 0; q < 5; ++q) {
+            // (offsets 1, 2, .. 32: the other way round than refid_wave_sum of workgroup.h, and pinned to its reference in this order)
 #pragma unroll
             for (int o = 1; o < 64; o <<= 1) e[q] = e[q] + __shfl_xor(e[q], o, 64);
             if (lane == 0) red[wave * NQ_ENTRIES + m * 5 + q] = e[q];

@@ -10,17 +10,19 @@
 //     then ONE lane walks the two-queue merge, the depths and zlib's length repair in LDS (2*257 nodes per 1..64 KiB of
 //     data), and all lanes deal the lengths out, number the canonical codes and add up the segment's bits.  The block's
 //     record in `work` gets the segment length, stored / dynamic, A, B and the 257 (bit-reversed code, length) pairs.
-//   png_deflate_offsets_kernel one workgroup per stream.  Exclusive sum of the segment lengths into the records (fixed
-//     chunks per thread, integer), the Adler sums combined in block order, then 78 01, the terminator, the Adler-32 and lens.
-//   png_deflate_pack_kernel    one workgroup per block.  The bit stream is put together in an LDS image of the ALIGNED
-//     global words it lands in (bit 0 of the image is the first bit of the word that holds the segment's first byte), 4096
-//     input bytes per pass: a thread takes 16 consecutive bytes, a workgroup prefix sum of their code lengths gives its bit
-//     position, its bits are OR-ed into the image (LDS integer or: order-free), the image's complete words leave as aligned
-//     dword stores and the incomplete last word opens the next pass.  The first and the last word of a segment may share
-//     their word with the neighbouring segment: the bytes of such a word that belong to this segment are stored one by
-//     one, by the lane that holds the word.  No global atomics, no read-modify-write of a global word; nothing outside
-//     the segment's bytes is written.  Stored segments are copied byte by byte.
+//   png_deflate_offsets_kernel one workgroup per stream.  Exclusive sum of the segment lengths into the records (the chunk
+//     walk of bit_image.h), the Adler sums combined in block order, then 78 01, the terminator, the Adler-32 and lens.
+//   png_deflate_pack_kernel    one workgroup per block.  The bit stream is put together LSB first in the LDS image of
+//     bit_image.h (writer, retire step and their barrier contract are stated there), which here stands for the ALIGNED
+//     global words the segment lands in (bit 0 of the image is the first bit of the word that holds the segment's first
+//     byte), 4096 input bytes per pass, 16 consecutive bytes per thread.  The sink stores complete words as aligned
+//     dwords.  The first and the last word of a segment may share their word with the neighbouring segment: the bytes of
+//     such a word that belong to this segment are stored one by one, by the lane that holds the word.  No global
+//     atomics, no read-modify-write of a global word; nothing outside the segment's bytes is written.  Stored segments
+//     are copied byte by byte.
+// The workgroup sums and the scan are those of workgroup.h.
 #include "common.h"
+#include "bit_image.h"
 
 namespace {
 
@@ -44,46 +46,8 @@ __device__ __forceinline__ bool pngd_fixed_bit(int i) {
     return i == 2 || (i >= 13 && i < 17) || (i >= 17 + 9 && (i - 17) % 3 == 2);
 }
 
-// ORs the low bits of v into the image at bit `pos` (v has at most 32 significant bits)
-__device__ __forceinline__ void pngd_put(unsigned* image, unsigned pos, unsigned v) {
-    const unsigned long long x = (unsigned long long)v << (pos & 31u);
-    if ((unsigned)x) atomicOr(&image[pos >> 5], (unsigned)x);
-    if ((unsigned)(x >> 32)) atomicOr(&image[(pos >> 5) + 1], (unsigned)(x >> 32));
-}
-
-__device__ __forceinline__ unsigned pngd_wave_sum(unsigned v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// sum over the workgroup; `red` holds one word per wave; every thread gets the total
-__device__ __forceinline__ unsigned pngd_block_sum(unsigned v, unsigned* red) {
-    v = pngd_wave_sum(v);
-    __syncthreads();                                           // (red may still be read from the call before)
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
-}
-
-// exclusive prefix sum over the workgroup in thread order; *total = the sum
-__device__ __forceinline__ unsigned pngd_block_scan(unsigned v, unsigned* red, unsigned* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned up = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += up;
-    }
-    __syncthreads();
-    if (lane == 63) red[wave] = inc;
-    __syncthreads();
-    unsigned before = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) before += w < wave ? red[w] : 0u;
-    *total = red[0] + red[1] + red[2] + red[3];
-    return before + inc - v;
-}
+constexpr int PNGD_WAVES = PNGD_THREADS / 64;
+constexpr RefidBitOrder PNGD_ORDER = REFID_BITS_LSB_FIRST;     // deflate packs codes from bit 0 of a byte up
 
 __global__ __launch_bounds__(PNGD_THREADS) void png_deflate_code_kernel(const uint8_t* __restrict__ src, unsigned* __restrict__ work,
                                                                         int n_blocks, int stream_bytes, int block_bytes) {
@@ -93,7 +57,7 @@ __global__ __launch_bounds__(PNGD_THREADS) void png_deflate_code_kernel(const ui
     __shared__ unsigned short parent[2 * PNGD_SYMS];
     __shared__ unsigned char depth[2 * PNGD_SYMS];
     __shared__ unsigned count[PNGD_MAX_BITS + 1], next_code[PNGD_MAX_BITS + 1];
-    __shared__ unsigned red[4];
+    __shared__ unsigned red[PNGD_WAVES];
     const int tid = threadIdx.x, wave = tid >> 6;
     const int s = blockIdx.x / n_blocks, b = blockIdx.x % n_blocks;
     const int start = b * block_bytes;                         // (< stream_bytes < 2^31)
@@ -132,8 +96,11 @@ __global__ __launch_bounds__(PNGD_THREADS) void png_deflate_code_kernel(const ui
         s1 += d;
         s2 += (unsigned long long)(unsigned)(len - i) * d;
     }
-    const unsigned sum_a = pngd_block_sum(s1, red);            // <= 65535 * 255; (the barrier inside also closes the histogram)
-    const unsigned sum_b = pngd_block_sum((unsigned)(s2 % PNGD_ADLER), red);           // 256 terms below 65521
+    // the three sums of this kernel share `red`: the barrier in front of each keeps its store behind the reads of the one before
+    __syncthreads();
+    const unsigned sum_a = refid_block_sum<unsigned, PNGD_WAVES>(s1, red);             // <= 65535 * 255; (its barrier also closes the histogram)
+    __syncthreads();
+    const unsigned sum_b = refid_block_sum<unsigned, PNGD_WAVES>((unsigned)(s2 % PNGD_ADLER), red);      // 256 terms below 65521
 
     // frequencies and sort keys; end-of-block (256) occurs once
     {
@@ -219,7 +186,8 @@ __global__ __launch_bounds__(PNGD_THREADS) void png_deflate_code_kernel(const ui
         rec[PNGD_REC_CODES + sym] = entry;
         body += freq[sym] * l;                                 // <= 65536 * 15 over the workgroup
     }
-    body = pngd_block_sum(body, red);
+    __syncthreads();
+    body = refid_block_sum<unsigned, PNGD_WAVES>(body, red);
     if (tid == 0) {
         const unsigned bits = PNGD_HEADER_BITS + body + 3;
         const unsigned dynamic = (bits + 7) / 8 + 4;
@@ -234,32 +202,27 @@ __global__ __launch_bounds__(PNGD_THREADS) void png_deflate_code_kernel(const ui
 __global__ __launch_bounds__(PNGD_THREADS) void png_deflate_offsets_kernel(uint8_t* __restrict__ out, unsigned* __restrict__ lens_out,
                                                                            unsigned* __restrict__ work, int n_blocks, int stream_bytes,
                                                                            int block_bytes, int out_pitch) {
-    __shared__ unsigned red[4];
+    __shared__ unsigned red[PNGD_WAVES];
     __shared__ unsigned part_a[PNGD_THREADS], part_b[PNGD_THREADS], part_l[PNGD_THREADS];
     const int tid = threadIdx.x, s = blockIdx.x;
     unsigned* rec = work + (long long)s * n_blocks * PNGD_REC;
-    const int per = (n_blocks + PNGD_THREADS - 1) / PNGD_THREADS;
-    const int lo = min(tid * per, n_blocks), hi = min(lo + per, n_blocks);      // (tid * per < 2^31: per <= 2^23)
-    // a thread's blocks lo .. hi-1: their segment bytes, and their Adler sums combined in order:
+    // a thread's blocks lo .. hi-1 (the chunk the walk below gives it too): their Adler sums combined in order:
     // (A1, B1, L1) then (A2, B2, L2) = (A1 + A2, B1 + L2 A1 + B2, L1 + L2)
-    unsigned bytes = 0;
+    int lo, hi;
+    refid_chunk<PNGD_THREADS>(n_blocks, &lo, &hi);
     unsigned long long a = 0, bsum = 0, l = 0;
     for (int j = lo; j < hi; ++j) {
         const unsigned* r = rec + (long long)j * PNGD_REC;
-        bytes += r[PNGD_REC_SEG];
         const unsigned long long l2 = (unsigned)(j == n_blocks - 1 ? stream_bytes - j * block_bytes : block_bytes);
         bsum = (bsum + l2 * a + r[PNGD_REC_B]) % PNGD_ADLER;
         a = (a + r[PNGD_REC_A]) % PNGD_ADLER;
         l = (l + l2) % PNGD_ADLER;
     }
     part_a[tid] = (unsigned)a, part_b[tid] = (unsigned)bsum, part_l[tid] = (unsigned)l;
-    unsigned total = 0;
-    unsigned off = 2 + pngd_block_scan(bytes, red, &total);    // (its barriers also publish the parts)
-    for (int j = lo; j < hi; ++j) {
-        unsigned* r = rec + (long long)j * PNGD_REC;
-        r[PNGD_REC_OFF] = off;
-        off += r[PNGD_REC_SEG];
-    }
+    // the segments laid end to end behind 78 01; (the scan's barriers also publish the parts)
+    const unsigned total = refid_chunk_offsets<PNGD_THREADS>(
+        n_blocks, red, [rec](int j) { return rec[(long long)j * PNGD_REC + PNGD_REC_SEG]; },
+        [rec](int j, unsigned off, unsigned) { rec[(long long)j * PNGD_REC + PNGD_REC_OFF] = 2 + off; });
     if (tid == 0) {
         unsigned long long ta = 0, tb = 0, tl = 0;
         for (int t = 0; t < PNGD_THREADS; ++t) {
@@ -277,11 +240,13 @@ __global__ __launch_bounds__(PNGD_THREADS) void png_deflate_offsets_kernel(uint8
     }
 }
 
-// the image's words [0, n) are the aligned global words w0 .. w0+n-1 counted from `base`; the segment owns bytes [lo, hi) from base
-__device__ __forceinline__ void pngd_flush(const unsigned* image, int n, int w0, uint8_t* base, int lo, int hi) {
-    for (int i = threadIdx.x; i < n; i += PNGD_THREADS) {
-        const int byte0 = 4 * (w0 + i);
-        const unsigned v = image[i];
+// where the image's words go: word w of the stream is the aligned global word w counted from `base`; the segment owns
+// bytes [lo, hi) from base
+struct PngdFlush {
+    uint8_t* base;
+    int lo, hi;
+    __device__ __forceinline__ void operator()(int w, unsigned v) const {
+        const int byte0 = 4 * w;
         if (byte0 >= lo && byte0 + 4 <= hi) {
             *reinterpret_cast<unsigned*>(base + byte0) = v;
         } else {
@@ -290,14 +255,14 @@ __device__ __forceinline__ void pngd_flush(const unsigned* image, int n, int w0,
                 if (byte0 + k >= lo && byte0 + k < hi) base[byte0 + k] = (uint8_t)(v >> (8 * k));
         }
     }
-}
+};
 
 __global__ __launch_bounds__(PNGD_THREADS) void png_deflate_pack_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ out,
                                                                         const unsigned* __restrict__ work, int n_blocks, int stream_bytes,
                                                                         int block_bytes, int out_pitch) {
     __shared__ unsigned table[PNGD_SYMS + 1];
     __shared__ unsigned image[PNGD_IMAGE];
-    __shared__ unsigned red[4];
+    __shared__ unsigned red[PNGD_WAVES];
     const int tid = threadIdx.x;
     const int s = blockIdx.x / n_blocks, b = blockIdx.x % n_blocks;
     const int start = b * block_bytes;
@@ -316,7 +281,7 @@ __global__ __launch_bounds__(PNGD_THREADS) void png_deflate_pack_kernel(const ui
     }
 
     const int lo = (int)((unsigned long long)o & 3), hi = lo + seg;       // the segment's bytes, counted from the aligned word
-    uint8_t* base = o - lo;
+    const PngdFlush flush = {o - lo, lo, hi};
     for (int i = tid; i < PNGD_SYMS + 1; i += PNGD_THREADS) table[i] = i < PNGD_SYMS ? rec[PNGD_REC_CODES + i] : 0u;     // (257: the distance length)
     for (int i = tid; i < PNGD_IMAGE; i += PNGD_THREADS) image[i] = 0;
     __syncthreads();
@@ -324,23 +289,17 @@ __global__ __launch_bounds__(PNGD_THREADS) void png_deflate_pack_kernel(const ui
     // the header
     unsigned cursor = 8u * lo;                                 // bit position of the next bit, counted from base
     int w0 = 0;                                                // the global word that image[0] stands for
-    if (tid < PNGD_FIXED_BITS && pngd_fixed_bit(tid)) pngd_put(image, cursor + tid, 1u);
+    if (tid < PNGD_FIXED_BITS && pngd_fixed_bit(tid)) refid_bits_put_at<PNGD_ORDER>(image, cursor + tid, 1u, 1u);
     for (int i = tid; i < PNGD_SYMS + 1; i += PNGD_THREADS) {
         const unsigned l = table[i] >> 16;
-        pngd_put(image, cursor + PNGD_FIXED_BITS + 4 * i, ((l & 1) << 3) | ((l & 2) << 1) | ((l & 4) >> 1) | ((l & 8) >> 3));
+        refid_bits_put_at<PNGD_ORDER>(image, cursor + PNGD_FIXED_BITS + 4 * i, ((l & 1) << 3) | ((l & 2) << 1) | ((l & 4) >> 1) | ((l & 8) >> 3), 4u);
     }
     cursor += PNGD_HEADER_BITS;
 
     const int passes = (len + PNGD_PASS - 1) / PNGD_PASS;
     for (int pass = 0; pass <= passes; ++pass) {
         __syncthreads();                                       // the bits put so far are in the image
-        // the complete words leave; the incomplete one opens the next image
-        const int n_full = (int)(cursor >> 5) - w0;
-        const unsigned carry = image[n_full];
-        pngd_flush(image, n_full, w0, base, lo, hi);
-        __syncthreads();
-        for (int i = tid; i < PNGD_IMAGE; i += PNGD_THREADS) image[i] = i == 0 ? carry : 0u;
-        w0 += n_full;
+        refid_bits_retire<PNGD_THREADS>(image, cursor, w0, flush);       // the complete words leave; the incomplete one opens the next image
         __syncthreads();
         if (pass == passes) break;
 
@@ -357,34 +316,27 @@ __global__ __launch_bounds__(PNGD_THREADS) void png_deflate_pack_kernel(const ui
         for (int k = 0; k < PNGD_PER_THREAD; ++k)
             bits += k < mine ? table[(d[k >> 2] >> (8 * (k & 3))) & 0xffu] >> 16 : 0u;
         unsigned total = 0;
-        const unsigned at = cursor + pngd_block_scan(bits, red, &total) - 32u * w0;       // bit position in the image
-        unsigned long long acc = 0;
-        unsigned filled = at & 31u, word = at >> 5;
+        RefidBitWriter<PNGD_ORDER> w(cursor + refid_block_scan<PNGD_WAVES>(bits, red, &total) - 32u * w0);      // bit position in the image
 #pragma unroll
         for (int k = 0; k < PNGD_PER_THREAD; ++k) {
             if (k < mine) {
                 const unsigned e = table[(d[k >> 2] >> (8 * (k & 3))) & 0xffu];
-                acc |= (unsigned long long)(e & 0xffffu) << filled;
-                filled += e >> 16;
-                if (filled >= 32) {
-                    if ((unsigned)acc) atomicOr(&image[word], (unsigned)acc);
-                    acc >>= 32, filled -= 32, ++word;
-                }
+                w.put(image, e & 0xffffu, e >> 16);
             }
         }
-        if ((unsigned)acc) atomicOr(&image[word], (unsigned)acc);
+        w.flush(image);
         cursor += total;
     }
 
     // end-of-block, the empty stored block 000, padding to a byte, 00 00 FF FF
     const unsigned eob = table[256];
-    if (tid == 0) pngd_put(image, cursor - 32u * w0, eob & 0xffffu);
+    if (tid == 0) refid_bits_put_at<PNGD_ORDER>(image, cursor - 32u * w0, eob & 0xffffu, eob >> 16);
     cursor += (eob >> 16) + 3;
     cursor = (cursor + 7u) & ~7u;
-    if (tid == 0) pngd_put(image, cursor + 16 - 32u * w0, 0xffffu);
+    if (tid == 0) refid_bits_put_at<PNGD_ORDER>(image, cursor + 16 - 32u * w0, 0xffffu, 16u);
     cursor += 32;                                              // == 8 * hi
     __syncthreads();
-    pngd_flush(image, (int)((cursor + 31) >> 5) - w0, w0, base, lo, hi);
+    refid_bits_drain<PNGD_THREADS>(image, (int)((cursor + 31) >> 5) - w0, w0, flush);
 }
 
 int pngd_blocks(long long stream_bytes, long long block_bytes) { return (int)((stream_bytes + block_bytes - 1) / block_bytes); }

@@ -24,6 +24,7 @@
 //     [rows, rows + N*H*pitch), and any alignment of `rows` works.
 // Integer arithmetic modulo 256 only: the bytes are defined by the specification, the choice by the sums.
 #include "common.h"
+#include "workgroup.h"
 
 namespace {
 
@@ -96,8 +97,7 @@ __global__ __launch_bounds__(64 * PNGF_WAVES) void png_filter_kernel(const uint8
         }
 #pragma unroll
         for (int t = 0; t < 5; ++t) {
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) sum[t] += __shfl_xor(sum[t], o, 64);
+            sum[t] = refid_wave_sum(sum[t]);
         }
         if (costs && lane < 5) {
             unsigned v = sum[0];

@@ -20,6 +20,7 @@
 // the integer error alone it comes out as in io.hip.  The Y arithmetic is one correctly rounded operation per step:
 // contraction is off inside those bodies.
 #include "common.h"
+#include "workgroup.h"
 #include "ssim3d_tile.h"
 #include "y_plane.h"
 
@@ -76,15 +77,6 @@ __device__ __forceinline__ float score_byte(const unsigned* raw_row, const unsig
     return (float)reinterpret_cast<const unsigned char*>(raw_row)[(int)((unsigned long long)p & 3) + k];
 }
 
-// the integer counterpart of SSIM3D_BLOCK_SUM (each thread's value <= 3 * 255^2); thread 0 uses the result
-__device__ __forceinline__ unsigned long long score_block_sum_u32(unsigned v, unsigned* sh) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (unsigned long long)sh[0] + sh[1] + sh[2] + sh[3];
-}
-
 // ---- colour: sq_rgb and, with S3D, the 3-D SSIM (the halo is staged only then)
 template <bool S3D>
 __global__ __launch_bounds__(256) void score_rgb_kernel(const unsigned char* __restrict__ a, const unsigned char* __restrict__ b,
@@ -122,7 +114,7 @@ __global__ __launch_bounds__(256) void score_rgb_kernel(const unsigned char* __r
                 d2 += (unsigned)(d * d);
             }
         }
-        const unsigned long long s = score_block_sum_u32(d2, sqred);
+        const unsigned long long s = refid_block_sum<unsigned long long, 4>(d2, sqred);     // (each d2 <= 3 * 255^2)
         if (threadIdx.x == 0) sq_parts[blockIdx.x] = s;
     }
     if constexpr (S3D) {

@@ -16,6 +16,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include "workgroup.h"
 
 struct SsimConst { float g[11]; float mc[3][3]; };
 
@@ -61,14 +62,10 @@ constexpr int SSIM_T = 16, SSIM_R = 5, SSIM_HS = SSIM_T + 2 * SSIM_R;          /
         }                                                                                                                   \
     }
 
-// The workgroup's sum of `acc` (one double per thread) as a fixed tree: xor-shuffle inside a wave, then the four waves in
-// order, which thread 0 stores to `dst`.  sred: 4 doubles of LDS that nothing else uses in the kernel.
+// The workgroup's sum of `acc` (one double per thread) in the fixed order of refid_block_sum (workgroup.h), which thread 0
+// stores to `dst`.  sred: 4 doubles of LDS that nothing else uses in the kernel.
 #define SSIM3D_BLOCK_SUM(acc, sred, dst)                                                                                    \
-    _Pragma("unroll")                                                                                                       \
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);                                                         \
-    if ((threadIdx.x & 63) == 0) sred[threadIdx.x >> 6] = acc;                                                              \
-    __syncthreads();                                                                                                        \
-    if (threadIdx.x == 0) dst = sred[0] + sred[1] + sred[2] + sred[3];
+    { const double ssim_sum = refid_block_sum<double, 4>(acc, sred); if (threadIdx.x == 0) dst = ssim_sum; }
 
 static inline SsimConst ssim_const() {
     SsimConst k;

@@ -6,19 +6,14 @@
 // Reference: losses/losses.py:28-30,143-173 (CharbonnierLoss, eps=1e-12, mean);
 // twoImage_event_recurrent_model.py:303-306 (backward, clip_grad_norm_(0.01), AdamW step).
 #include "common.h"
+#include "workgroup.h"
 
 namespace {
 
-__device__ __forceinline__ double block_sum_double(double v, double* sh) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-    if (l == 0) sh[w] = v;
-    __syncthreads();
-    double r = 0.0;
-    if (threadIdx.x == 0) for (int i = 0; i < (int)(blockDim.x >> 6); ++i) r += sh[i];
-    return r;       // valid on thread 0
-}
+// The workgroup sums below (refid_block_sum<double, 4>) add sh[0] + sh[1] + sh[2] + sh[3].  Until they moved to
+// workgroup.h these kernels added 0.0 + sh[0] + ... over blockDim.x / 64 waves: the same bits because every launch here
+// has 256 threads and every thread's term is a sum of non-negative values that starts from +0.0, so no partial is -0.0
+// (the one value that 0.0 + x changes).
 
 // loss_sum[block] = sum sqrt(d^2 + eps) ; grad = d / sqrt(d^2 + eps) * gscale     (d = pred - gt)
 __global__ __launch_bounds__(256) void charbonnier_kernel(const f32x4* __restrict__ pred, const f32x4* __restrict__ gt,
@@ -37,7 +32,7 @@ __global__ __launch_bounds__(256) void charbonnier_kernel(const f32x4* __restric
         }
         if (grad) grad[i] = g;
     }
-    const double t = block_sum_double((double)acc, sh);
+    const double t = refid_block_sum<double, 4>((double)acc, sh);
     if (threadIdx.x == 0) loss_sum[blockIdx.x] = t;        // per-block partial; summed in index order (sum_rows_kernel)
 }
 
@@ -53,7 +48,7 @@ __global__ __launch_bounds__(256) void psnr_sq_kernel(const f32x4* __restrict__ 
         const f32x4 d = pred[base + i] - gt[base + i];
         acc += d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3];
     }
-    const double t = block_sum_double((double)acc, sh);
+    const double t = refid_block_sum<double, 4>((double)acc, sh);
     if (threadIdx.x == 0) sq[(long long)blockIdx.y * gridDim.x + blockIdx.x] = t;     // partial [sample][block]
 }
 
@@ -81,7 +76,7 @@ __global__ __launch_bounds__(256) void sqnorm_kernel(const f32x4* __restrict__ g
         const f32x4 v = g[i];
         acc += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
     }
-    const double t = block_sum_double((double)acc, sh);
+    const double t = refid_block_sum<double, 4>((double)acc, sh);
     if (threadIdx.x == 0) out[blockIdx.x] = t;             // per-block partial (deterministic 2nd stage)
 }
 

@@ -30,6 +30,7 @@ template <> struct VoxelIn<long long> {
 };
 
 // fixed xor tree over the 64 lanes (adjacent pairs first), then the four waves in index order; the total is in thread 0
+// (offsets 1, 2, .. 32: the other way round than refid_block_sum of workgroup.h, and pinned to its reference in this order)
 template <class T>
 __device__ __forceinline__ T vn_block_sum(T v, T* sh) {
 #pragma clang fp contract(off)

@@ -169,6 +169,22 @@ def _inflate(path):
     return w, h, ch, np.frombuffer(raw, dtype=np.uint8).reshape(h, 1 + w * ch)
 
 
+def read_header(path):
+    """(width, height, channels) as ``_inflate`` gives them, from the 33 bytes of the signature and IHDR alone: what
+    ``sequence.load_png_frames`` sizes its staging by before any file is inflated.  A file whose head does not parse that way
+    goes through ``read_filtered``, whose ValueError says what is wrong with it."""
+    with open(path, "rb") as f:
+        head = f.read(33)
+    try:
+        (tag, ihdr), = read_chunks(head)
+        w, h, depth, colour, comp, flt, lace = struct.unpack(">IIBBBBB", ihdr)
+        if tag != b"IHDR" or depth != 8 or colour not in (0, 2) or comp or flt or lace:
+            raise ValueError
+    except (ValueError, struct.error):
+        return read_filtered(path)[:3]
+    return w, h, 3 if colour == 2 else 1
+
+
 def read_png(path):
     """Decodes an 8-bit RGB / grey, non-interlaced PNG (all five filter types) into a uint8 array (H, W, 3) / (H, W)."""
     w, h, ch, rows = _inflate(path)

@@ -118,83 +118,113 @@ def load_event_npz(paths, swap_xy=False):
 PNG_WORKERS_MAX = 16      # the inflate pool never grows with the machine: a shared box shows more CPUs than a job may use
 
 
+def _load_staged(what, items, device, workers, frames_per_launch, plan):
+    """The pipeline under ``load_png_frames`` and ``load_jpeg_frames`` (``what``: the name in the messages).  After the
+    argument checks ``plan(device)`` gives ``(out, shapes, fill, launch)``: the result tensor; per frame the ``(shape,
+    dtype)`` of every staging array; ``fill(item, *views)``, which runs in a worker thread and writes one frame's slices of a
+    pinned staging set (numpy views); ``launch(first, n, host, dev)``, which queues the decode of frames first .. first+n-1
+    on the current stream from the chunk's staging tensors ``host`` and their uploaded copies ``dev``.
+
+    ``workers`` threads (at most ``PNG_WORKERS_MAX``) fill the chunks of ``frames_per_launch`` frames, two chunks ahead of
+    the launches: the one in hand and the next, each in its own staging set (one set when there is one chunk).  A chunk whose
+    workers are done is uploaded without blocking and launched; its set is handed to the workers again only after the
+    event behind that upload has completed.  A worker's exception cancels what has not started and is raised again, the
+    first failing frame's in frame order.  Returns ``out`` without synchronising."""
+    from concurrent.futures import ThreadPoolExecutor
+    workers, per = int(workers), int(frames_per_launch)
+    if not items:
+        raise RefidHipError(f"{what}: no files")
+    if not 1 <= workers <= PNG_WORKERS_MAX or per < 1:
+        raise RefidHipError(f"{what}: workers {workers} must be 1..{PNG_WORKERS_MAX} and frames_per_launch {per} >= 1")
+    device = torch.device("cuda" if device is None else device)
+    if device.type != "cuda":
+        raise RefidHipError(f"{what}: a GPU device is required (the HIP path has no CPU fallback)")
+    out, shapes, fill, launch = plan(device)
+    per = min(per, len(items))
+    chunks = [items[i:i + per] for i in range(0, len(items), per)]
+    with ThreadPoolExecutor(max_workers=workers) as pool, torch.cuda.device(device):
+        staging = [[torch.empty((per, *shape), dtype=dtype).pin_memory() for shape, dtype in shapes]
+                   for _ in range(min(2, len(chunks)))]
+        copied = [None] * len(staging)                     # the event after the upload that last read each set
+        ahead = collections.deque(maxlen=2)                # the chunks being filled: the one in hand and the next
+
+        def submit(k):
+            if k < len(chunks):
+                if copied[k % 2] is not None:
+                    copied[k % 2].synchronize()
+                views = [t.numpy() for t in staging[k % 2]]
+                ahead.append([pool.submit(fill, item, *(v[i] for v in views)) for i, item in enumerate(chunks[k])])
+
+        submit(0)
+        submit(1)
+        for k, chunk in enumerate(chunks):
+            futures = ahead.popleft()
+            try:
+                for fut in futures:
+                    fut.result()
+            except BaseException:
+                for later in list(ahead) + [futures]:
+                    for f in later:
+                        f.cancel()
+                raise
+            n = len(chunk)
+            host = [t[:n] for t in staging[k % 2]]
+            dev = [torch.empty(t.shape, dtype=t.dtype, device=device) for t in host]
+            for d, t in zip(dev, host):
+                d.copy_(t, non_blocking=True)
+            copied[k % 2] = torch.cuda.Event()
+            copied[k % 2].record()
+            launch(k * per, n, host, dev)
+            submit(k + 2)
+    return out
+
+
 def load_png_frames(paths, device=None, workers=8, frames_per_launch=8):
     """8-bit RGB / grey PNG key frames of one size -> uint8 (N, H, W, 3) on the device, a grey file replicated to three
     channels: what ``SequenceAssembler.load`` takes.  ``paths``: the files in order, or a directory (its ``*.png`` sorted
     by name).  The files are read and inflated by ``workers`` threads (``zlib`` releases the GIL; at most
-    ``PNG_WORKERS_MAX``), their filter bytes are checked on the host, and every chunk of ``frames_per_launch`` frames is
-    copied into one of two pinned staging buffers, uploaded without blocking and unfiltered by one ``refid_png_unfilter``
-    launch (csrc/png.hip) on the current stream, while the pool inflates the next chunk.  A staging buffer is written again
-    only after the event behind its last upload has completed.  Files that differ in (H, W, channels): RefidHipError
-    naming the first one; a broken file: ``png.read_png``'s ValueError.  Rows wider than the kernel's line
-    (``_lib.PNG_MAX_ROW_BYTES``) are decoded on the host by ``png.read_png``.  Does not synchronise at the end."""
+    ``PNG_WORKERS_MAX``), which check their filter bytes on the host and copy the rows straight into one of two pinned
+    staging buffers; every chunk of ``frames_per_launch`` frames is uploaded without blocking and unfiltered by one
+    ``refid_png_unfilter`` launch (csrc/png.hip) on the current stream, while the pool inflates the next chunk.  A staging
+    buffer is written again only after the event behind its last upload has completed.  Files that differ in (H, W,
+    channels): RefidHipError naming the first one; a broken file: ``png.read_png``'s ValueError.  Rows wider than the
+    kernel's line (``_lib.PNG_MAX_ROW_BYTES``) are decoded on the host by ``png.read_png``, in the same workers, and only
+    uploaded.  Does not synchronise at the end."""
     import glob
-    from concurrent.futures import ThreadPoolExecutor
     from . import ops, png
     if isinstance(paths, (str, os.PathLike)):
         paths = sorted(glob.glob(os.path.join(paths, "*.png"))) if os.path.isdir(paths) else [paths]
     paths = [os.fspath(p) for p in paths]
-    workers, per = int(workers), int(frames_per_launch)
-    if not paths:
-        raise RefidHipError("load_png_frames: no files")
-    if not 1 <= workers <= PNG_WORKERS_MAX or per < 1:
-        raise RefidHipError(f"load_png_frames: workers {workers} must be 1..{PNG_WORKERS_MAX} and frames_per_launch {per} >= 1")
-    device = torch.device("cuda" if device is None else device)
-    if device.type != "cuda":
-        raise RefidHipError("load_png_frames: a GPU device is required (the HIP path has no CPU fallback)")
-    chunks = [paths[i:i + per] for i in range(0, len(paths), per)]
-    with ThreadPoolExecutor(max_workers=workers) as pool, torch.cuda.device(device):
-        ahead = collections.deque(maxlen=2)                # the chunks being inflated: the one in hand and the next
 
-        def submit(k):
-            if k < len(chunks):
-                ahead.append([pool.submit(png.read_filtered, p) for p in chunks[k]])
-
-        def cancel():
-            for futures in ahead:
-                for f in futures:
-                    f.cancel()
-
-        submit(0)
-        submit(1)
-        w, h, ch, _ = ahead[0][0].result()
-        if w * ch > _lib.PNG_MAX_ROW_BYTES:                # the host route for this file set
-            cancel()
-            imgs = list(pool.map(png.read_png, paths))
-            if len({i.shape for i in imgs}) != 1:
-                first = next(p for p, i in zip(paths, imgs) if i.shape != imgs[0].shape)
-                raise RefidHipError(f"load_png_frames: {first} differs in size from {paths[0]}")
-            imgs = [np.repeat(i[:, :, None], 3, axis=2) if i.ndim == 2 else i for i in imgs]
-            return torch.from_numpy(np.stack(imgs)).to(device)
-        pitch = 1 + w * ch
+    def plan(device):
+        w, h, ch = png.read_header(paths[0])               # (the header alone: no worker waits for a whole file)
         out = torch.empty((len(paths), h, w, 3), dtype=torch.uint8, device=device)
-        staging = [torch.empty((per, h, pitch), dtype=torch.uint8).pin_memory() for _ in range(min(2, len(chunks)))]
-        copied = [None] * len(staging)                     # the event after the upload that last read each buffer
-        for k, chunk in enumerate(chunks):
-            futures = ahead.popleft()
-            submit(k + 2)
-            buf = staging[k % 2]
-            if copied[k % 2] is not None:
-                copied[k % 2].synchronize()
-            for i, (path, fut) in enumerate(zip(chunk, futures)):
-                try:
-                    wi, hi, ci, rows = fut.result()
-                except BaseException:
-                    cancel()
-                    raise
-                if (wi, hi, ci) != (w, h, ch):
-                    cancel()
-                    raise RefidHipError(f"load_png_frames: {path} is {hi}x{wi}x{ci}, {paths[0]} is {h}x{w}x{ch}: the files of a "
-                                        "sequence must share (H, W, channels)")
-                buf[i].numpy()[...] = rows
-            n = len(chunk)
-            bands = png.find_bands(buf[:n, :, 0].numpy())
-            rows_dev = torch.empty((n, h, pitch), dtype=torch.uint8, device=device)
-            rows_dev.copy_(buf[:n], non_blocking=True)
-            copied[k % 2] = torch.cuda.Event()
-            copied[k % 2].record()
-            ops.png_unfilter(rows_dev, n, h, w, ch, out=out[k * per:k * per + n], bands=bands)
-    return out
+        if w * ch > _lib.PNG_MAX_ROW_BYTES:                # the host route for this file set
+            def fill(path, pixels):
+                img = png.read_png(path)
+                if img.shape != ((h, w, 3) if ch == 3 else (h, w)):
+                    raise RefidHipError(f"load_png_frames: {path} differs in size from {paths[0]}")
+                pixels[...] = img if ch == 3 else img[:, :, None]
+
+            def launch(first, n, host, dev):
+                out[first:first + n].copy_(dev[0])
+
+            return out, [((h, w, 3), torch.uint8)], fill, launch
+
+        def fill(path, rows):
+            wi, hi, ci, filtered = png.read_filtered(path)
+            if (wi, hi, ci) != (w, h, ch):
+                raise RefidHipError(f"load_png_frames: {path} is {hi}x{wi}x{ci}, {paths[0]} is {h}x{w}x{ch}: the files of a "
+                                    "sequence must share (H, W, channels)")
+            rows[...] = filtered
+
+        def launch(first, n, host, dev):
+            bands = png.find_bands(host[0][:, :, 0].numpy())
+            ops.png_unfilter(dev[0], n, h, w, ch, out=out[first:first + n], bands=bands)
+
+        return out, [((h, 1 + w * ch), torch.uint8)], fill, launch
+
+    return _load_staged("load_png_frames", paths, device, workers, frames_per_launch, plan)
 
 
 def _jpeg_sources(sources):
@@ -225,17 +255,8 @@ def load_jpeg_frames(sources, device=None, workers=8, frames_per_launch=8):
     only after the event behind its last upload has completed.  Files that differ in (H, W, components, sampling):
     RefidHipError naming the first one; a file the decoder refuses (include/refid_hip.h lists what): RefidHipError with its
     name and the library's message.  Does not synchronise at the end."""
-    from concurrent.futures import ThreadPoolExecutor
     from . import jpeg, ops
     items = _jpeg_sources(sources)
-    workers, per = int(workers), int(frames_per_launch)
-    if not items:
-        raise RefidHipError("load_jpeg_frames: no files")
-    if not 1 <= workers <= PNG_WORKERS_MAX or per < 1:
-        raise RefidHipError(f"load_jpeg_frames: workers {workers} must be 1..{PNG_WORKERS_MAX} and frames_per_launch {per} >= 1")
-    device = torch.device("cuda" if device is None else device)
-    if device.type != "cuda":
-        raise RefidHipError("load_jpeg_frames: a GPU device is required (the HIP path has no CPU fallback)")
 
     def read(item):
         name, src = item
@@ -250,59 +271,29 @@ def load_jpeg_frames(sources, device=None, workers=8, frames_per_launch=8):
         except RefidHipError as e:
             raise RefidHipError(f"load_jpeg_frames: {item[0]}: {e}") from None
 
-    first = probe(items[0], read(items[0]))
-    h, w, comps, sampling, total = first.height, first.width, first.components, first.sampling, first.total_blocks
-    per = min(per, len(items))
-    chunks = [items[i:i + per] for i in range(0, len(items), per)]
-
-    def decode(item, coefs, quant):
-        data = read(item)
-        info = probe(item, data)
-        if info[:4] != first[:4]:
-            raise RefidHipError(f"load_jpeg_frames: {item[0]} is {info.height}x{info.width}, {info.components} components, sampling "
-                                f"{info.sampling}; {items[0][0]} is {h}x{w}, {comps}, {sampling}: the files of a sequence must share "
-                                "(H, W, components, sampling)")
-        try:
-            jpeg.entropy_decode(data, info, coefs, quant)
-        except RefidHipError as e:
-            raise RefidHipError(f"load_jpeg_frames: {item[0]}: {e}") from None
-
-    with ThreadPoolExecutor(max_workers=workers) as pool, torch.cuda.device(device):
+    def plan(device):
+        first = probe(items[0], read(items[0]))
+        h, w, comps, sampling, total = first.height, first.width, first.components, first.sampling, first.total_blocks
         out = torch.empty((len(items), h, w, 3), dtype=torch.uint8, device=device)
-        staging = [(torch.empty((per, total, 64), dtype=torch.int16).pin_memory(), torch.empty((per, comps, 64), dtype=torch.int16).pin_memory())
-                   for _ in range(min(2, len(chunks)))]
-        copied = [None] * len(staging)                     # the event after the upload that last read each buffer
-        ahead = collections.deque(maxlen=2)                # the chunks being decoded: the one in hand and the next
 
-        def submit(k):
-            if k < len(chunks):
-                if copied[k % 2] is not None:
-                    copied[k % 2].synchronize()
-                coefs, quant = (t.numpy() for t in staging[k % 2])
-                ahead.append([pool.submit(decode, item, coefs[i], quant[i].view(np.uint16)) for i, item in enumerate(chunks[k])])
-
-        submit(0)
-        submit(1)
-        for k, chunk in enumerate(chunks):
-            futures = ahead.popleft()
+        def fill(item, coefs, quant):
+            data = read(item)
+            info = probe(item, data)
+            if info[:4] != first[:4]:
+                raise RefidHipError(f"load_jpeg_frames: {item[0]} is {info.height}x{info.width}, {info.components} components, sampling "
+                                    f"{info.sampling}; {items[0][0]} is {h}x{w}, {comps}, {sampling}: the files of a sequence must share "
+                                    "(H, W, components, sampling)")
             try:
-                for fut in futures:
-                    fut.result()
-            except BaseException:
-                for later in list(ahead) + [futures]:
-                    for f in later:
-                        f.cancel()
-                raise
-            n = len(chunk)
-            coefs_dev = torch.empty((n, total, 64), dtype=torch.int16, device=device)
-            quant_dev = torch.empty((n, comps, 64), dtype=torch.int16, device=device)
-            coefs_dev.copy_(staging[k % 2][0][:n], non_blocking=True)
-            quant_dev.copy_(staging[k % 2][1][:n], non_blocking=True)
-            copied[k % 2] = torch.cuda.Event()
-            copied[k % 2].record()
-            ops.jpeg_decode(coefs_dev, quant_dev, n, h, w, sampling, out=out[k * per:k * per + n])
-            submit(k + 2)
-    return out
+                jpeg.entropy_decode(data, info, coefs, quant.view(np.uint16))
+            except RefidHipError as e:
+                raise RefidHipError(f"load_jpeg_frames: {item[0]}: {e}") from None
+
+        def launch(first_frame, n, host, dev):
+            ops.jpeg_decode(dev[0], dev[1], n, h, w, sampling, out=out[first_frame:first_frame + n])
+
+        return out, [((total, 64), torch.int16), ((comps, 64), torch.int16)], fill, launch
+
+    return _load_staged("load_jpeg_frames", items, device, workers, frames_per_launch, plan)
 
 
 def load_key_frames(path, device=None, workers=8, frames_per_launch=8):
@@ -316,7 +307,7 @@ def load_key_frames(path, device=None, workers=8, frames_per_launch=8):
     kw = dict(device=device, workers=workers, frames_per_launch=frames_per_launch)
     if os.path.isdir(path):
         pngs = sorted(glob.glob(os.path.join(path, "*.png")))
-        jpgs = sorted(glob.glob(os.path.join(path, "*.jpg")) + glob.glob(os.path.join(path, "*.jpeg")))
+        jpgs = [name for name, _ in _jpeg_sources(path)]
         if pngs and jpgs:
             raise RefidHipError(f"load_key_frames: {path} holds both PNG ({len(pngs)}) and JPEG ({len(jpgs)}) files: keep one kind")
         if not pngs and not jpgs:
