@@ -1113,6 +1113,44 @@ int refid_event_sim(const refid_event_sim_desc* d, void* stream);
 /* the least threshold the cap allows for a table with these extremes (0: lut_max < lut_min, or none fits int32) */
 int32_t refid_event_sim_min_threshold(int32_t lut_min, int32_t lut_max);
 
+/* ----------------------------------------------------------------------------------
+ * Blur synthesis (csrc/blur_synth.hip): blurry key frames as averages of consecutive frames of a high-frame-rate clip, what
+ * GoPro's blur/ (plain) and blur_gamma/ (response) directories hold.  Integers only; tests/blur_ref.py restates it and the
+ * device is compared bit for bit.
+ *
+ * Inputs: frames uint8 (n_frames, height, width, 3), contiguous, any alignment; windows int32 (n_windows, 2), rows
+ * [first, count] with 1 <= count <= REFID_BLUR_MAX_COUNT and first + count <= n_frames, which may overlap or repeat, on
+ * the host (checked here) and on the device (read by the kernel); to_linear uint32 [256], L, on both sides, or null on both.
+ * Output: out uint8 (n_windows, height, width, 3), any alignment; nothing outside it is written.  Per byte b of a frame
+ * (the channels are independent, so RGB and BGR frames are treated alike):
+ *   plain      out = (sum_j f[first+j][b] + count/2) / count                       integer division: ties round up
+ *   response   v = (sum_j L[f[first+j][b]] + count/2) / count, out = the number of c in 1 .. 255 with thr[c] <= v,
+ *              thr[c] = (L[c-1] + L[c] + 1) >> 1: the code whose level is nearest to the average in linear light.
+ * L must be strictly increasing with L[255] <= 2^24 (a sum of 64 entries then stays below 2^31);
+ * refid_amd.blur_synth.gamma_table(g) is rint(2^24 (c / 255)^g) in float64 on the host.  Since thr[c] <= L[c] < thr[c+1],
+ * a window of identical frames returns that frame exactly, in both modes and for every count.
+ *
+ * One launch for all windows on `stream`; allocates nothing, does not synchronise.  The grid is capped (4096 workgroups
+ * that walk the tiles with a stride; max_groups > 0 lowers or raises the cap, 0 keeps it).  Turned down with return 1 and a
+ * message that begins "blur_synth:" and names the field, before any launch: a null pointer, a table pointer that is not
+ * aligned to 4 bytes, one copy of to_linear without the other, n_windows, height, width or n_frames below 1, a negative
+ * max_groups, a count outside 1 .. 64, a window outside the frames, a table that is not strictly increasing (the first
+ * such index is named) or whose last entry exceeds 2^24, more than 2^40 pixels per frame or 2^31 - 1 tiles (4096 bytes of
+ * one window each) per call.
+ * ---------------------------------------------------------------------------------- */
+#define REFID_BLUR_MAX_COUNT 64
+typedef struct refid_blur_synth_desc {
+    const uint8_t* frames;                      /* device: n_frames * height * width * 3 bytes                      */
+    const int32_t* windows_host;                /* host:   n_windows rows [first, count] (checked here)              */
+    const int32_t* windows;                     /* device: the same rows (read by the kernel)                       */
+    const uint32_t* to_linear_host;             /* host:   256 levels (checked here), or null: plain mode           */
+    const uint32_t* to_linear;                  /* device: the same levels, or null                                 */
+    uint8_t* out;                               /* device: n_windows * height * width * 3 bytes                     */
+    int32_t n_frames, height, width, n_windows;
+    int32_t max_groups;                         /* 0: the default cap of the grid; else the cap, in workgroups      */
+} refid_blur_synth_desc;
+int refid_blur_synth(const refid_blur_synth_desc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

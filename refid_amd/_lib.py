@@ -209,6 +209,15 @@ class EventSimDesc(C.Structure):
     ]
 
 
+class BlurSynthDesc(C.Structure):
+    """refid_blur_synth_desc: uint8 frames + windows [first, count] -> one averaged uint8 frame per window (csrc/blur_synth.hip)."""
+    _fields_ = [
+        ("frames", C.c_void_p), ("windows_host", C.c_void_p), ("windows", C.c_void_p), ("to_linear_host", C.c_void_p),
+        ("to_linear", C.c_void_p), ("out", C.c_void_p),
+        ("n_frames", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("n_windows", C.c_int32), ("max_groups", C.c_int32),
+    ]
+
+
 LAYOUT_BLUR, LAYOUT_SHARP = 0, 1                # == REFID_LAYOUT_* in include/refid_hip.h
 ASSEMBLE_ZERO, ASSEMBLE_SCATTER, ASSEMBLE_FINISH, ASSEMBLE_FRAMES, ASSEMBLE_ALL = 1, 2, 4, 8, 15
 ASSEMBLE_STATS = 16                              # refid_assemble_single only: voxel_norm's statistics, between scatter and finish
@@ -231,6 +240,7 @@ EVENT_SIM_CAP = 255                # == REFID_EVENT_SIM_CAP in include/refid_hip
 EVENT_SIM_MAX_FRAMES = 512         # == REFID_EVENT_SIM_MAX_FRAMES in include/refid_hip.h
 EVENT_SIM_MAX_PIXELS = 1 << 25     # == REFID_EVENT_SIM_MAX_PIXELS in include/refid_hip.h
 EVENT_SIM_FLAG_OVERFLOW, EVENT_SIM_FLAG_SLOTS = 1, 2    # == REFID_EVENT_SIM_FLAG_* in include/refid_hip.h
+BLUR_MAX_COUNT = 64                # == REFID_BLUR_MAX_COUNT in include/refid_hip.h
 ABI_VERSION = 9          # == REFID_ABI_VERSION in include/refid_hip.h
 _lib = None
 
@@ -384,6 +394,7 @@ def _bind_extra(L):
     L.refid_event_sim.argtypes = [C.POINTER(EventSimDesc), vp]
     L.refid_event_sim_min_threshold.argtypes = [C.c_int32, C.c_int32]
     L.refid_event_sim_min_threshold.restype = C.c_int32
+    L.refid_blur_synth.argtypes = [C.POINTER(BlurSynthDesc), vp]
     L.refid_score_u8_parts.argtypes = [i, i, i, i]
     L.refid_score_u8_parts.restype = ll
     L.refid_score_u8.argtypes = [vp, vp, i, i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp]

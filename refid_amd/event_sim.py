@@ -7,8 +7,8 @@ and thresholds in units of 2^-16 from a 256-entry table), so the rows are reprod
 resident, time-sorted float32 (E, 4) tensor [t, x, y, p] that ``SequenceAssembler.load`` takes, and, through
 ``save_event_npz``, the reference's per-interval ``.npz`` files.
 
-Not modelled: a refractory period, leak and shot noise, hot pixels, blur synthesis, frame upsampling before simulation,
-colour or Bayer events.  There is no host fallback."""
+Not modelled: a refractory period, leak and shot noise, hot pixels, frame upsampling before simulation, colour or Bayer
+events (blurry key frames are ``refid_amd.blur_synth``'s).  There is no host fallback."""
 import os
 
 import numpy as np

@@ -1423,3 +1423,51 @@ def event_sim(frames_u8, stamps, state, lut, c_pos, c_neg, bgr=False, lut_range=
     desc.perm, desc.sorted, desc.stage = perm.data_ptr(), out.data_ptr(), _lib.EVENT_SIM_GATHER
     check(L.refid_event_sim(C.byref(desc), _stream()), "refid_event_sim (gather)")
     return out, offsets
+
+
+def blur_synth(frames_u8, windows, to_linear=None, out=None, max_groups=0):
+    """refid_blur_synth (csrc/blur_synth.hip) on the current stream: uint8 CUDA frames (N, H, W, 3), a contiguous view of any
+    alignment, and ``windows`` int32 (K, 2) rows [first, count] on the host (1 <= count <= 64, first + count <= N; they may
+    overlap or repeat) -> uint8 (K, H, W, 3): window k's frames averaged byte by byte, by the integer formulas of
+    include/refid_hip.h ("Blur synthesis").  ``to_linear``: None (plain mode: the codes are averaged) or uint32 (256,) on the
+    host, strictly increasing, at most 2^24 (response mode: the levels are averaged and the nearest code is looked up;
+    ``blur_synth.gamma_table``).  ``out``: a contiguous uint8 tensor of K*H*W*3 elements to write into (any alignment;
+    nothing outside it is written); the result is a view of it.  ``max_groups``: the cap of the grid in workgroups (0: the
+    launcher's own).  One launch; does not synchronise."""
+    f = frames_u8
+    if not isinstance(f, torch.Tensor) or not f.is_cuda or f.dtype != torch.uint8 or f.dim() != 4 or f.shape[-1] != 3 or \
+            f.numel() == 0 or not f.is_contiguous():
+        raise _lib.RefidHipError("blur_synth: frames must be a non-empty contiguous uint8 (N, H, W, 3) CUDA tensor (no CPU fallback), got "
+                                 + (f"{f.dtype} {tuple(f.shape)} on {f.device}" if isinstance(f, torch.Tensor) else type(f).__name__))
+    n, h, w = (int(v) for v in f.shape[:3])
+    try:
+        win = np.asarray(windows.cpu() if torch.is_tensor(windows) else windows)
+    except (TypeError, ValueError):
+        win = np.zeros((0,), dtype=np.float64)
+    if win.ndim != 2 or win.shape[1] != 2 or win.shape[0] < 1 or win.dtype.kind not in "iu":
+        raise _lib.RefidHipError(f"blur_synth: windows must be integer (K, 2) rows [first, count] with K >= 1, got {win.dtype} {tuple(win.shape)}")
+    if int(win.min()) < -2 ** 31 or int(win.max()) >= 2 ** 31:
+        raise _lib.RefidHipError("blur_synth: windows do not fit int32")
+    win = np.ascontiguousarray(win, dtype=np.int32)
+    k = int(win.shape[0])
+    lin = None
+    if to_linear is not None:
+        lin = np.asarray(to_linear.cpu() if torch.is_tensor(to_linear) else to_linear)
+        if lin.shape != (256,) or lin.dtype.kind not in "iu" or int(lin.min()) < 0 or int(lin.max()) >= 2 ** 32:
+            raise _lib.RefidHipError(f"blur_synth: to_linear must be 256 unsigned integers on the host, got {lin.dtype} {tuple(lin.shape)}")
+        lin = np.ascontiguousarray(lin, dtype=np.uint32)
+    if isinstance(max_groups, bool) or not isinstance(max_groups, (int, np.integer)) or not 0 <= int(max_groups) < 2 ** 31:
+        raise _lib.RefidHipError(f"blur_synth: max_groups {max_groups!r} must be an int, 0 (the launcher's cap) .. 2^31 - 1")
+    if out is None:
+        out = torch.empty((k, h, w, 3), dtype=torch.uint8, device=f.device)
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != f.device or out.numel() != k * h * w * 3 or \
+            not out.is_contiguous():
+        raise _lib.RefidHipError(f"blur_synth: out must be a contiguous uint8 tensor of {k}*{h}*{w}*3 elements on {f.device}")
+    win_dev = torch.from_numpy(win).to(f.device)
+    lin_dev = None if lin is None else torch.from_numpy(lin.view(np.int32)).to(f.device)     # (the bits of the uint32)
+    desc = _lib.BlurSynthDesc(frames=f.data_ptr(), windows_host=win.ctypes.data, windows=win_dev.data_ptr(),
+                              to_linear_host=None if lin is None else lin.ctypes.data,
+                              to_linear=None if lin is None else lin_dev.data_ptr(), out=out.data_ptr(),
+                              n_frames=n, height=h, width=w, n_windows=k, max_groups=int(max_groups))
+    check(lib().refid_blur_synth(C.byref(desc), _stream()), "refid_blur_synth")
+    return out.view(k, h, w, 3)

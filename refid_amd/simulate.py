@@ -13,6 +13,22 @@ i + 1 to ``{out}/gt/{i:06d}_{f:02d}.png``, f = 0 .. S - 2, the names ``refid_amd
 second command above then interpolates the key frames from the simulated events and scores the result against the
 held-out frames.  Frames behind the last key frame are simulated but belong to no pair.
 
+    python -m refid_amd.simulate --frames clip240/ --fps 240 --out sim --blur 11 --gap 1
+    python -m refid_amd.interpolate --checkpoint net.pth --layout blur --m 11 --n 1 --frames sim/keys \\
+        --events sim/events/*.npz --stamps sim/key_stamps.txt --gt sim/gt --out sim/out
+    python -m refid_amd.deblur --checkpoint evhinet.pth --num-bins 6 --frames sim/keys --events sim/events/*.npz \\
+        --stamps sim/key_stamps.txt --gt sim/gt_mid --out sim/deblur
+
+``--blur M --gap N`` (instead of ``--split``) writes BLURRY key frames, synthesised on the GPU (``refid_amd.blur_synth``,
+csrc/blur_synth.hip), in the reference's GoPro indexing (basicsr/data/image_npy_dataset.py:75-86): with P = M + N, key i
+is the average of the sharp frames [iP, iP + M), written to ``{out}/keys/{i:06d}.png``; ``{out}/key_stamps.txt`` holds
+``start end`` per line, the stamps of the first and of the last averaged frame; ``{out}/gt/{i:06d}_{f:02d}.png``,
+f = 0 .. 2M + N - 1, are the sharp frames iP + f of pair i, the names ``refid_amd.interpolate --layout blur --m M --n N``
+gives its outputs; for odd M ``{out}/gt_mid/{i:06d}.png`` is the sharp frame iP + M // 2 in the middle of key i's
+exposure, the target of ``refid_amd.deblur --gt``.  ``--blur-gamma G`` (1 .. 3) averages in linear light, (c / 255)^G at
+24 bits, as GoPro's ``blur_gamma`` frames are made; without it the codes are averaged, as in ``blur/``.  The events are
+simulated from the sharp frames either way.
+
 ``--c-pos`` / ``--c-neg`` are the contrast thresholds in natural-log units, ``--sigma-c`` the standard deviation of their
 per-pixel spread (seeded by ``--seed``), ``--eps`` the offset inside the logarithm, ``--chunk`` the frames per device call.
 The simulator runs on the GPU only."""
@@ -68,6 +84,9 @@ def main(argv=None):
     ap.add_argument("--chunk", type=int, default=64, help="frames per device call, 2 .. 512 (default 64)")
     ap.add_argument("--bgr", action="store_true", help="the frames are BGR")
     ap.add_argument("--split", type=int, metavar="S", help="also write every S-th frame as a key frame and the others as ground truth")
+    ap.add_argument("--blur", type=int, metavar="M", help="also write blurry key frames, each the average of M frames, and the sharp frames as ground truth")
+    ap.add_argument("--gap", type=int, metavar="N", help="with --blur: frames between the exposures of two blurry key frames")
+    ap.add_argument("--blur-gamma", type=float, metavar="G", help="with --blur: average in linear light, (c / 255)^G, 1 .. 3 (default: average the codes)")
     args = ap.parse_args(argv)
 
     from . import _lib, event_sim
@@ -86,6 +105,24 @@ def main(argv=None):
         if not np.isfinite(c) or not c < 32768 or event_sim.to_fixed(c) < bound:
             raise SystemExit(f"{flag}: {c} must be at least {bound / event_sim.FIXED_ONE:.4f} ({bound} in units of 2^-16: at most "
                              f"{_lib.EVENT_SIM_CAP} events per pixel between two frames)")
+    if args.blur is not None and args.split is not None:
+        raise SystemExit("--blur and --split exclude each other: blurry or sharp key frames")
+    if args.blur is None:
+        for flag, value in (("--gap", args.gap), ("--blur-gamma", args.blur_gamma)):
+            if value is not None:
+                raise SystemExit(f"{flag}: needs --blur M")
+    else:
+        if args.gap is None:
+            raise SystemExit("--blur: needs --gap N, the frames between two exposures")
+        if not 1 <= args.blur <= _lib.BLUR_MAX_COUNT:
+            raise SystemExit(f"--blur: {args.blur} must be 1 .. {_lib.BLUR_MAX_COUNT} frames per blurry key frame")
+        if not 0 <= args.gap <= 100:
+            raise SystemExit(f"--gap: {args.gap} must be 0 .. 100")
+        if 2 * args.blur + args.gap > 100:
+            raise SystemExit(f"--blur {args.blur} --gap {args.gap}: a pair has 2 M + N = {2 * args.blur + args.gap} ground-truth frames, "
+                             f"100 are the most (two digits in their names)")
+        if args.blur_gamma is not None and not 1.0 <= args.blur_gamma <= 3.0:
+            raise SystemExit(f"--blur-gamma: {args.blur_gamma} must be 1 .. 3")
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("refid_amd.simulate needs the GPU: the event simulator is csrc/event_sim.hip and has no host fallback")
@@ -96,6 +133,8 @@ def main(argv=None):
     n = int(frames.shape[0])
     if n < 2:
         raise SystemExit(f"--frames: {n} frame, at least 2 are needed")
+    if args.blur is not None and n < args.blur:
+        raise SystemExit(f"--frames: {n} frames do not hold one blurry key frame of --blur {args.blur}")
     stamps = _stamps(args, n)
     try:
         sim = event_sim.EventSimulator(int(frames.shape[1]), int(frames.shape[2]), args.c_pos, args.c_neg, sigma=args.sigma_c, seed=args.seed,
@@ -127,6 +166,36 @@ def main(argv=None):
         _write_stamps(os.path.join(args.out, "key_stamps.txt"), stamps[keys])
         print(f"{len(keys)} key frames -> {os.path.join(args.out, 'keys')}, {(len(keys) - 1) * (s - 1)} held-out frames -> "
               f"{os.path.join(args.out, 'gt')}")
+    if args.blur is not None:
+        from . import blur_synth
+        m, period = args.blur, args.blur + args.gap
+        try:
+            resident = frames if torch.is_tensor(frames) and frames.is_cuda else torch.as_tensor(np.ascontiguousarray(frames)).to("cuda")
+            keys, windows = blur_synth.synthesize(resident, m, args.gap, gamma=args.blur_gamma)
+        except RefidHipError as e:
+            raise SystemExit(f"--blur: {e}")
+        host, blurry = resident.cpu().numpy(), keys.cpu().numpy()
+        if args.bgr:
+            host, blurry = host[..., ::-1], blurry[..., ::-1]
+        k, mid = int(windows.shape[0]), m % 2 == 1
+        for d in ("keys", "gt") + (("gt_mid",) if mid else ()):
+            os.makedirs(os.path.join(args.out, d), exist_ok=True)
+        for i in range(k):
+            write_png(os.path.join(args.out, "keys", f"{i:06d}.png"), np.ascontiguousarray(blurry[i]))
+            if mid:
+                write_png(os.path.join(args.out, "gt_mid", f"{i:06d}.png"), np.ascontiguousarray(host[i * period + m // 2]))
+            if i + 1 < k:
+                for f in range(2 * m + args.gap):
+                    write_png(os.path.join(args.out, "gt", f"{i:06d}_{f:02d}.png"), np.ascontiguousarray(host[i * period + f]))
+        with open(os.path.join(args.out, "key_stamps.txt"), "w") as f:
+            for start, end in blur_synth.exposures(stamps, windows):
+                f.write(f"{float(start)!r} {float(end)!r}\n")
+        print(f"{k} blurry key frames of {m} frames -> {os.path.join(args.out, 'keys')}, {(k - 1) * (2 * m + args.gap)} sharp frames -> "
+              f"{os.path.join(args.out, 'gt')}")
+        if mid:
+            print(f"{k} mid-exposure frames -> {os.path.join(args.out, 'gt_mid')}")
+        else:
+            print(f"no gt_mid: --blur {m} is even, an exposure has no middle frame")
     return 0
 
 
