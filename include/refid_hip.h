@@ -1151,6 +1151,81 @@ typedef struct refid_blur_synth_desc {
 } refid_blur_synth_desc;
 int refid_blur_synth(const refid_blur_synth_desc* d, void* stream);
 
+/* ----------------------------------------------------------------------------------
+ * Double integral (csrc/edi.hip): latent sharp frames from key frames and events without a network, the event-based double
+ * integral of Pan et al. (CVPR 2019) and the model-based inverse of "Simulated events" + "Blur synthesis".  A pixel's log
+ * level moves by +c_pos or -c_neg per event, so the latent frame at an instant is the key frame times exp(level) divided by
+ * the mean of exp(level) over the key's exposure.  tests/edi_ref.py restates it and the device is compared bit for bit.
+ *
+ * Inputs.  frames uint8 (n_frames, height, width, 3), contiguous, any alignment; the three channels are treated alike.
+ *   The stream, packed once per sequence (refid_amd.edi.EdiStream): the rows [t, x, y, p] of a time-sorted float32 stream
+ *   with x and y truncated toward zero, rows outside the frame dropped, sorted stably by pixel y width + x:
+ *   ev_t float32 [n_events] stamps, ev_p int8 [n_events] signs (p > 0: +1, anything else: -1), seg int32 [height width + 1],
+ *   pixel q owns ev[seg[q] .. seg[q + 1]).  n_events may be 0 (ev_t and ev_p are then not read).
+ *   Items, each on the host (checked here) and on the device (read by the kernel): items int32 (n_items, 2) rows
+ *   [left, right], key-frame indices, right < 0: no right key (deblurring); bounds float32 (n_items, 4) rows
+ *   [s0, e0, s1, e1], the exposures of the two keys, s0 <= e0 <= s1 <= e1 (without a right key s1 and e1 are not read);
+ *   instants float32 (n_items, n_instants), ascending, inside [s0, e1] ([s0, e0] without a right key);
+ *   samples float32 (n_items, 2 m) in REFID_EDI_SAMPLES mode, null on both sides in REFID_EDI_CONTINUOUS mode: m ascending
+ *   instants inside [s0, e0], then m inside [s1, e1] (refid_amd.edi.sample_instants: fl32(s + ((e - s) j) / (m - 1)) in
+ *   float64, m = 1: s).  tables float64 [REFID_EDI_TABLE] on the device (refid_amd.edi.gain_tables): exp(i), i = -32 .. 32 |
+ *   exp(h / 256), h = 0 .. 255 | exp(l / 65536), l = 0 .. 255, built on the host: nothing transcendental runs on the device.
+ *   Level  e(tau) = the sum of (p > 0 ? +c_pos : -c_neg) over the pixel's events with s0 < t <= tau, compared in float32:
+ *          an exact integer in units of 2^-16 (thresholds 1 .. REFID_EDI_MAX_THRESHOLD).  An event at s0 is not the
+ *          item's, one at tau counts towards tau (the simulator stamps a crossing reached at a frame with that frame).
+ *   Gain   g(e): ec = e held inside +-REFID_EDI_CLAMP 2^16, ec = 65536 i + 256 h + l, g = (T0[i] T1[h]) T2[l] in float64.
+ *          A pixel of an item for which some gain was held counts once in the flag words.
+ *   S      of a key with exposure [s, e] and level e(s): 1 when s == e (a sharp key); SAMPLES: (sum_j g(e(sigma_j) - e(s))) / m
+ *          summed in j order from 0; CONTINUOUS: (sum_k g_k (t_{k+1} - t_k)) / (e - s) over the piecewise-constant level on
+ *          [s, e], its knots s, the events with s < t <= e, and e, float64 from the float32 stamps, in time order.
+ *   Latent L_key(tau)[c] = ((B_key[c] + eps255) g(e(tau) - e(s_key))) / S_key, eps255 = 255 eps (the simulator's eps: 1e-3).
+ *   Blend  w = 0 for tau <= e0, 1 for tau >= s1, else (tau - e0) / (s1 - e0);
+ *          out = clamp(rint(((1 - w) L_left + w L_right) - eps255), 0, 255), rint to even; without a right key L_left alone.
+ *   Every float64 operation is rounded once (no contraction), in the order written.
+ * Output: out uint8 (n_items, n_instants, height, width, 3), any alignment; clamped int32 [n_items ceil(height width /
+ * REFID_EDI_THREADS)]: every workgroup writes the count of its held pixels into its own word (no atomics); sum them.
+ *
+ * One launch for all items on `stream`; allocates nothing, does not synchronise.  Turned down with return 1 and a message
+ * that begins "edi:" and names the field, before any launch: a null or misaligned pointer (tables 8 bytes, the int32 and
+ * float arrays 4), one copy of samples without the other or samples in CONTINUOUS mode, n_items outside 1 ..
+ * REFID_EDI_MAX_ITEMS, n_instants outside 1 .. REFID_EDI_MAX_INSTANTS, m outside 1 .. REFID_BLUR_MAX_COUNT, height width
+ * outside 1 .. REFID_EDI_MAX_PIXELS, n_events outside 0 .. 2^31 - 1, an unknown exposure mode, a threshold outside 1 ..
+ * REFID_EDI_MAX_THRESHOLD, eps255 not finite or negative, a key index outside the frames, bounds, instants or samples that
+ * are not finite, not ordered or outside their range.  Nothing is retried and nothing falls back to the host.
+ * ---------------------------------------------------------------------------------- */
+#define REFID_EDI_SAMPLES 0
+#define REFID_EDI_CONTINUOUS 1
+#define REFID_EDI_THREADS 256
+#define REFID_EDI_CLAMP 32
+#define REFID_EDI_TABLE 577
+#define REFID_EDI_MAX_INSTANTS 256
+#define REFID_EDI_MAX_ITEMS 65535
+#define REFID_EDI_MAX_PIXELS 33554432
+#define REFID_EDI_MAX_THRESHOLD 1048576
+typedef struct refid_edi_desc {
+    const uint8_t* frames;                      /* device: n_frames * height * width * 3 bytes                      */
+    const float* ev_t;                          /* device: n_events stamps, by pixel, then by time                  */
+    const int8_t* ev_p;                         /* device: n_events signs, +1 or -1                                 */
+    const int32_t* seg;                         /* device: height * width + 1 segment starts                        */
+    const int32_t* items_host;                  /* host:   n_items rows [left, right] (checked here)                */
+    const int32_t* items;                       /* device: the same rows                                            */
+    const float* bounds_host;                   /* host:   n_items rows [s0, e0, s1, e1] (checked here)             */
+    const float* bounds;                        /* device: the same rows                                            */
+    const float* samples_host;                  /* host:   n_items rows of 2 m sample instants, or null             */
+    const float* samples;                       /* device: the same rows, or null                                   */
+    const float* instants_host;                 /* host:   n_items rows of n_instants output instants               */
+    const float* instants;                      /* device: the same rows                                            */
+    const double* tables;                       /* device: REFID_EDI_TABLE gains                                    */
+    uint8_t* out;                               /* device: n_items * n_instants * height * width * 3 bytes          */
+    int32_t* clamped;                           /* device: n_items * ceil(height width / REFID_EDI_THREADS) counts  */
+    double eps255;                              /* 255 eps                                                          */
+    int64_t n_events;
+    int32_t n_frames, height, width, n_items, n_instants;
+    int32_t m, exposure;                        /* samples per key (SAMPLES mode), REFID_EDI_SAMPLES / _CONTINUOUS  */
+    int32_t c_pos, c_neg;                       /* thresholds, units of 2^-16                                       */
+} refid_edi_desc;
+int refid_edi(const refid_edi_desc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

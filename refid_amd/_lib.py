@@ -218,6 +218,18 @@ class BlurSynthDesc(C.Structure):
     ]
 
 
+class EdiDesc(C.Structure):
+    """refid_edi_desc: key frames + the stream packed by pixel + items -> latent uint8 frames at instants (csrc/edi.hip)."""
+    _fields_ = [
+        ("frames", C.c_void_p), ("ev_t", C.c_void_p), ("ev_p", C.c_void_p), ("seg", C.c_void_p), ("items_host", C.c_void_p),
+        ("items", C.c_void_p), ("bounds_host", C.c_void_p), ("bounds", C.c_void_p), ("samples_host", C.c_void_p), ("samples", C.c_void_p),
+        ("instants_host", C.c_void_p), ("instants", C.c_void_p), ("tables", C.c_void_p), ("out", C.c_void_p), ("clamped", C.c_void_p),
+        ("eps255", C.c_double), ("n_events", C.c_int64),
+        ("n_frames", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("n_items", C.c_int32), ("n_instants", C.c_int32),
+        ("m", C.c_int32), ("exposure", C.c_int32), ("c_pos", C.c_int32), ("c_neg", C.c_int32),
+    ]
+
+
 LAYOUT_BLUR, LAYOUT_SHARP = 0, 1                # == REFID_LAYOUT_* in include/refid_hip.h
 ASSEMBLE_ZERO, ASSEMBLE_SCATTER, ASSEMBLE_FINISH, ASSEMBLE_FRAMES, ASSEMBLE_ALL = 1, 2, 4, 8, 15
 ASSEMBLE_STATS = 16                              # refid_assemble_single only: voxel_norm's statistics, between scatter and finish
@@ -241,6 +253,14 @@ EVENT_SIM_MAX_FRAMES = 512         # == REFID_EVENT_SIM_MAX_FRAMES in include/re
 EVENT_SIM_MAX_PIXELS = 1 << 25     # == REFID_EVENT_SIM_MAX_PIXELS in include/refid_hip.h
 EVENT_SIM_FLAG_OVERFLOW, EVENT_SIM_FLAG_SLOTS = 1, 2    # == REFID_EVENT_SIM_FLAG_* in include/refid_hip.h
 BLUR_MAX_COUNT = 64                # == REFID_BLUR_MAX_COUNT in include/refid_hip.h
+EDI_SAMPLES, EDI_CONTINUOUS = 0, 1 # == REFID_EDI_SAMPLES / REFID_EDI_CONTINUOUS in include/refid_hip.h
+EDI_THREADS = 256                  # == REFID_EDI_THREADS in include/refid_hip.h
+EDI_CLAMP = 32                     # == REFID_EDI_CLAMP in include/refid_hip.h
+EDI_TABLE = 577                    # == REFID_EDI_TABLE in include/refid_hip.h
+EDI_MAX_INSTANTS = 256             # == REFID_EDI_MAX_INSTANTS in include/refid_hip.h
+EDI_MAX_ITEMS = 65535              # == REFID_EDI_MAX_ITEMS in include/refid_hip.h
+EDI_MAX_PIXELS = 1 << 25           # == REFID_EDI_MAX_PIXELS in include/refid_hip.h
+EDI_MAX_THRESHOLD = 1 << 20        # == REFID_EDI_MAX_THRESHOLD in include/refid_hip.h
 ABI_VERSION = 9          # == REFID_ABI_VERSION in include/refid_hip.h
 _lib = None
 
@@ -395,6 +415,7 @@ def _bind_extra(L):
     L.refid_event_sim_min_threshold.argtypes = [C.c_int32, C.c_int32]
     L.refid_event_sim_min_threshold.restype = C.c_int32
     L.refid_blur_synth.argtypes = [C.POINTER(BlurSynthDesc), vp]
+    L.refid_edi.argtypes = [C.POINTER(EdiDesc), vp]
     L.refid_score_u8_parts.argtypes = [i, i, i, i]
     L.refid_score_u8_parts.restype = ll
     L.refid_score_u8.argtypes = [vp, vp, i, i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp]

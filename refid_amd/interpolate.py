@@ -13,7 +13,14 @@ RGB, or -- decoded on the GPU -- a directory of baseline JPEGs (``*.jpg`` / ``*.
 ``file score`` line per frame and a last ``mean`` line over the finite scores, which is printed too.  ``--gt DIR`` (PNGs
 named as the output frames) scores every output frame against ground truth while it is on the GPU: ``{out}/scores.txt``
 holds ``file psnr ssim`` per frame and a last ``mean`` line (``python -m refid_amd.score`` scores a finished directory, with
-``--crop-border`` and the Y-channel variants)."""
+``--crop-border`` and the Y-channel variants).
+
+``--method edi`` needs no checkpoint: the frames come from the event-based double integral (``refid_amd.edi``,
+csrc/edi.hip), at the instants the network's outputs stand for and under the same names, so ``--gt``, ``--niqe`` and
+``--video`` work as above.  Give ``--n`` (and ``--layout blur --m M`` for blurry key frames), the stream's thresholds
+``--c-pos`` / ``--c-neg`` (natural-log units, default 0.2), ``--edi-exposure samples`` (default: a key frame is the mean of M
+frames, as ``refid_amd.simulate --blur M`` writes it) or ``continuous`` (a real shutter), and ``--eps``.  ``--checkpoint`` and
+``--opt`` are refused.  A last line counts the pixels whose gain had to be clamped and the event rows outside the frame."""
 import argparse
 import glob
 import os
@@ -170,7 +177,58 @@ def parser(prog, doc, opt_help, frames_help, stamps_help):
     ap.add_argument("--video-fps", default="30", help="frames per second of --video: a number or a fraction such as 30000/1001")
     ap.add_argument("--video-quality", default="90", help="JPEG quality of --video, 1 .. 100")
     ap.add_argument("--video-subsampling", default="420", help="chroma subsampling of --video: 420 or 444")
+    ap.add_argument("--method", choices=("network", "edi"), default="network",
+                    help="network (default): the checkpoint's network; edi: the event-based double integral (refid_amd.edi), "
+                         "which needs no checkpoint")
+    ap.add_argument("--c-pos", type=float, help="--method edi: the stream's positive contrast threshold, natural-log units (default 0.2)")
+    ap.add_argument("--c-neg", type=float, help="--method edi: the negative contrast threshold (default 0.2)")
+    ap.add_argument("--edi-exposure", choices=("samples", "continuous"),
+                    help="--method edi: a blurry key frame is the mean of M frames (samples, the default: what simulate --blur M "
+                         "writes) or of a continuous shutter")
+    ap.add_argument("--eps", type=float, help="--method edi: the offset inside the logarithm (default 1e-3, the simulator's)")
     return ap
+
+
+EDI_FLAGS = ("c_pos", "c_neg", "edi_exposure", "eps")
+
+
+def edi_settings(args, network_only=()):
+    """None for ``--method network`` (a flag of the other method exits naming it); for ``--method edi`` the keywords of the
+    ``refid_amd.edi`` runners.  ``network_only``: the caller's own flags that only the network reads; under ``--method edi``
+    they are refused, not ignored.  A bad flag exits before anything is loaded."""
+    flag = lambda name: "--" + name.replace("_", "-")             # noqa: E731
+    if args.method != "edi":
+        for name in EDI_FLAGS:
+            if getattr(args, name) is not None:
+                raise SystemExit(f"{flag(name)}: needs --method edi")
+        return None
+    if args.checkpoint:
+        raise SystemExit("--checkpoint: --method edi runs no network and takes no checkpoint")
+    if args.opt:
+        raise SystemExit("--opt: --method edi runs no network: give its settings as flags (--c-pos, --c-neg, --edi-exposure, --eps)")
+    for name in network_only:
+        if getattr(args, name) is not None:
+            raise SystemExit(f"{flag(name)}: --method edi runs no network and does not read it (the exposure bounds of --stamps and "
+                             "the events between them are all it takes)")
+    out = dict(c_pos=0.2 if args.c_pos is None else args.c_pos, c_neg=0.2 if args.c_neg is None else args.c_neg,
+               exposure=args.edi_exposure or "samples", eps=1e-3 if args.eps is None else args.eps)
+    for name in ("c_pos", "c_neg"):
+        if not 2.0 ** -16 <= out[name] <= 16.0:                   # (a NaN fails both)
+            raise SystemExit(f"{flag(name)}: {out[name]} must be at least 2^-16 and at most 16")
+    if not 0.0 <= out["eps"] < float("inf"):
+        raise SystemExit(f"--eps: {out['eps']} must be finite and not negative")
+    return out
+
+
+def edi_needs_gpu(prog):
+    """The last check before anything is loaded: without a GPU ``--method edi`` says so and stops."""
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit(f"{prog} --method edi needs the GPU: the double integral runs in csrc/edi.hip and has no host fallback")
+
+
+def report_edi(runner):
+    print(f"edi: {runner.clamped} clamped pixels, {runner.dropped} dropped event rows")
 
 
 def video_settings(args):
@@ -274,9 +332,20 @@ def main(argv=None):
                     help="--video holds the interpolated frames only (default for sharp key frames: the key frames too, in place)")
     args = ap.parse_args(argv)
     video_settings(args)                      # a bad flag exits before anything is loaded
+    edi_opt = edi_settings(args)
 
     from . import sequence
-    net_opt, ckpt, m, n, layout = settings(args)
+    if edi_opt is None:
+        net_opt, ckpt, m, n, layout = settings(args)
+    else:
+        if args.n is None:
+            raise SystemExit("--method edi: give --n")
+        layout = args.layout or "sharp"
+        if layout == "blur" and edi_opt["exposure"] == "samples" and args.m is None:
+            raise SystemExit("--m: --method edi --layout blur with --edi-exposure samples needs the number of frames averaged into a "
+                             "blurry key frame (simulate --blur M); give --m M, or --edi-exposure continuous")
+        m, n = (1 if args.m is None else args.m), args.n
+        edi_needs_gpu("refid_amd.interpolate")
     niqe_model, frames, events, stamps = load_inputs(args, "key frames")
     if layout == "sharp":
         windows = sequence.sharp_windows(stamps[:, 0])
@@ -284,6 +353,18 @@ def main(argv=None):
         windows = sequence.exposure_windows(stamps[:, 0], stamps[:, 1])
     else:
         raise SystemExit("--stamps: the blur layout needs an exposure 'start end' per line")
+    if edi_opt is not None:
+        from . import edi
+        from ._lib import RefidHipError
+        pairs = sequence.make_pairs(events[:, 0], *windows, stamps="bounds") if layout == "sharp" else \
+            edi.exposure_pairs(stamps[:, 0], stamps[:, 1])
+        try:
+            runner = edi.EdiInterpolator(m, n, layout, max_minibatch=args.max_minibatch, **edi_opt)
+        except RefidHipError as ex:
+            raise SystemExit(f"--method edi: {ex}")
+        run_and_report(runner, args, frames, events, pairs, niqe_model, "pairs", "{name}_{f:02d}.png")
+        report_edi(runner)
+        return 0
     pairs = sequence.make_pairs(events[:, 0], *windows)
     runner = sequence.SequenceInterpolator(load_network(net_opt, ckpt), m, n, layout, args.max_minibatch)
     run_and_report(runner, args, frames, events, pairs, niqe_model, "pairs", "{name}_{f:02d}.png")

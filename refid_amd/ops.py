@@ -1471,3 +1471,81 @@ def blur_synth(frames_u8, windows, to_linear=None, out=None, max_groups=0):
                               n_frames=n, height=h, width=w, n_windows=k, max_groups=int(max_groups))
     check(lib().refid_blur_synth(C.byref(desc), _stream()), "refid_blur_synth")
     return out.view(k, h, w, 3)
+
+
+def edi(frames_u8, stream, items, bounds, instants, m=1, exposure="samples", c_pos=13107, c_neg=13107, eps=1e-3, out=None):
+    """refid_edi (csrc/edi.hip) on the current stream: the event-based double integral of include/refid_hip.h ("Double
+    integral").  ``frames_u8``: uint8 CUDA key frames (N, H, W, 3), a contiguous view of any alignment.  ``stream``: the
+    sequence's events packed by pixel (``edi.EdiStream``, same device, same (H, W)).  On the host: ``items`` int (P, 2) rows
+    [left, right] (right < 0: no right key), ``bounds`` (P, 4) rows [s0, e0, s1, e1], ``instants`` (P, T) ascending output
+    instants.  ``exposure``: 'samples' (a key frame is the mean of ``m`` frames at ``edi.sample_instants``) or 'continuous'
+    (a real shutter; ``m`` is not read).  ``c_pos`` / ``c_neg``: thresholds in units of 2^-16 (``event_sim.to_fixed``).
+    ``out``: a contiguous uint8 tensor of P*T*H*W*3 elements to write into (any alignment).  Returns ``(frames uint8
+    (P, T, H, W, 3), clamped)``; ``clamped.sum()`` is the number of (item, pixel) pairs whose gain was held at exp(+-32).  One
+    launch; does not synchronise."""
+    from . import edi as E
+    f = frames_u8
+    if not isinstance(f, torch.Tensor) or not f.is_cuda or f.dtype != torch.uint8 or f.dim() != 4 or f.shape[-1] != 3 or \
+            f.numel() == 0 or not f.is_contiguous():
+        raise _lib.RefidHipError("edi: frames must be a non-empty contiguous uint8 (N, H, W, 3) CUDA tensor (no CPU fallback), got "
+                                 + (f"{f.dtype} {tuple(f.shape)} on {f.device}" if isinstance(f, torch.Tensor) else type(f).__name__))
+    n, h, w = (int(v) for v in f.shape[:3])
+    if not isinstance(stream, E.EdiStream) or stream.t is None:
+        raise _lib.RefidHipError(f"edi: stream must be a loaded edi.EdiStream, got {type(stream).__name__}")
+    if (stream.height, stream.width) != (h, w) or stream.t.device != f.device:
+        raise _lib.RefidHipError(f"edi: stream is {stream.height}x{stream.width} on {stream.t.device}, frames are {h}x{w} on {f.device}")
+    if exposure not in E.EXPOSURES:
+        raise _lib.RefidHipError(f"edi: unknown exposure {exposure!r} ('samples' or 'continuous')")
+    sampled = exposure == "samples"
+    m = int(m)
+    if sampled and not 1 <= m <= _lib.BLUR_MAX_COUNT:
+        raise _lib.RefidHipError(f"edi: m {m} must be 1 .. {_lib.BLUR_MAX_COUNT}")
+    for name, c in (("c_pos", c_pos), ("c_neg", c_neg)):
+        if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 1 <= int(c) <= _lib.EDI_MAX_THRESHOLD:
+            raise _lib.RefidHipError(f"edi: {name} {c!r} must be an int 1 .. {_lib.EDI_MAX_THRESHOLD} in units of 2^-16 (event_sim.to_fixed)")
+    eps = float(eps)
+    if not (np.isfinite(eps) and eps >= 0.0):
+        raise _lib.RefidHipError(f"edi: eps {eps} must be finite and not negative")
+    try:
+        it = np.asarray(items)
+        bd = np.asarray(bounds, dtype=np.float32)
+        tau = np.asarray(instants, dtype=np.float32)
+    except (TypeError, ValueError):
+        raise _lib.RefidHipError("edi: items, bounds and instants must be arrays on the host") from None
+    if it.ndim != 2 or it.shape[1] != 2 or it.dtype.kind not in "iu" or not 1 <= it.shape[0] <= _lib.EDI_MAX_ITEMS:
+        raise _lib.RefidHipError(f"edi: items must be integer (P, 2) rows [left, right] with P = 1 .. {_lib.EDI_MAX_ITEMS}, got {it.dtype} "
+                                 f"{tuple(it.shape)}")
+    p = int(it.shape[0])
+    if bd.shape != (p, 4):
+        raise _lib.RefidHipError(f"edi: bounds must be ({p}, 4) rows [s0, e0, s1, e1], got {tuple(bd.shape)}")
+    if tau.ndim != 2 or tau.shape[0] != p or not 1 <= tau.shape[1] <= _lib.EDI_MAX_INSTANTS:
+        raise _lib.RefidHipError(f"edi: instants must be ({p}, T) with T = 1 .. {_lib.EDI_MAX_INSTANTS}, got {tuple(tau.shape)}")
+    t = int(tau.shape[1])
+    it = np.ascontiguousarray(np.clip(it, -1, 2 ** 31 - 1), dtype=np.int32)
+    bd, tau = np.ascontiguousarray(bd), np.ascontiguousarray(tau)
+    smp = None
+    if sampled:
+        smp = np.ascontiguousarray(np.stack([np.concatenate([E.sample_instants(b[0], b[1], m), E.sample_instants(b[2], b[3], m)])
+                                             for b in bd]), dtype=np.float32)
+    if out is None:
+        out = torch.empty((p, t, h, w, 3), dtype=torch.uint8, device=f.device)
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != f.device or out.numel() != p * t * h * w * 3 or \
+            not out.is_contiguous():
+        raise _lib.RefidHipError(f"edi: out must be a contiguous uint8 tensor of {p}*{t}*{h}*{w}*3 elements on {f.device}")
+    groups = (h * w + _lib.EDI_THREADS - 1) // _lib.EDI_THREADS
+    clamped = torch.empty((p * groups,), dtype=torch.int32, device=f.device)
+    host = np.concatenate([v.view(np.int32).reshape(-1) for v in (it, bd, tau) + (() if smp is None else (smp,))])
+    # one upload of the rows' bits, items | bounds | instants | samples, from pinned memory: it does not wait for the stream
+    dev = torch.from_numpy(host).pin_memory().to(f.device, non_blocking=True)
+    at = [0, 2 * p, 6 * p, 6 * p + p * t]
+    ptr = lambda k: dev.data_ptr() + 4 * at[k]                # noqa: E731
+    desc = _lib.EdiDesc(frames=f.data_ptr(), ev_t=stream.t.data_ptr() if stream.n_events else None,
+                        ev_p=stream.p.data_ptr() if stream.n_events else None, seg=stream.seg.data_ptr(),
+                        items_host=it.ctypes.data, items=ptr(0), bounds_host=bd.ctypes.data, bounds=ptr(1),
+                        samples_host=None if smp is None else smp.ctypes.data, samples=None if smp is None else ptr(3),
+                        instants_host=tau.ctypes.data, instants=ptr(2), tables=E.device_tables(f.device).data_ptr(),
+                        out=out.data_ptr(), clamped=clamped.data_ptr(), eps255=255.0 * eps, n_events=stream.n_events,
+                        n_frames=n, height=h, width=w, n_items=p, n_instants=t, m=m if sampled else 1,
+                        exposure=_lib.EDI_SAMPLES if sampled else _lib.EDI_CONTINUOUS, c_pos=int(c_pos), c_neg=int(c_neg))
+    check(lib().refid_edi(C.byref(desc), _stream()), "refid_edi")
+    return out.view(p, t, h, w, 3), clamped

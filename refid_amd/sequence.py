@@ -586,10 +586,7 @@ class _SequenceRunner:
             names = [f"{p[0]:06d}" for p in pairs]
         if len(names) != len(pairs):
             raise RefidHipError(f"{what}.run: {len(names)} names for {len(pairs)} pairs")
-        asm, side = self.assembler, self.stream
-        cur = torch.cuda.current_stream(self.device)
-        asm.load(frames, events, bgr=bgr)
-        side.wait_stream(cur)                 # the upload was issued on the current stream
+        self._load(frames, events, bgr)
         sinks = [None if out_dir is None else _PngSink(self, names, out_dir, png_filter, png_deflate),
                  None if video is None else _VideoSink(self, names, pairs, video_keys, video, video_fps, video_quality,
                                                        video_subsampling, jpeg_pitch),
@@ -599,6 +596,33 @@ class _SequenceRunner:
         if gt is None and score is not None:
             raise RefidHipError(f"{what}.run: score= needs gt=")
         chunks = [pairs[i:i + self.max_minibatch] for i in range(0, len(pairs), self.max_minibatch)]
+        kept = []
+        outputs = self._outputs(chunks)
+        try:
+            with torch.no_grad():
+                for k, u8 in enumerate(outputs):
+                    for sink in sinks:
+                        sink.add(u8, k * self.max_minibatch, len(chunks[k]))
+                    if keep:
+                        kept.append(u8)
+        finally:
+            outputs.close()                                # (the generator's own ``finally`` runs now, if it had started)
+            with contextlib.ExitStack() as closing:        # (last in, first out) in the sinks' order, each even if another raises
+                for sink in reversed(sinks):
+                    closing.callback(sink.close)
+        for sink in sinks:
+            sink.finish()
+        return torch.cat(kept, dim=0).cpu().numpy() if keep else None
+
+    def _load(self, frames, events, bgr):
+        """Makes the sequence resident; after it ``assembler`` has ``frames`` (device), ``bgr``, ``height``, ``width``, ``layout``."""
+        self.assembler.load(frames, events, bgr=bgr)
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))       # the upload was issued on the current stream
+
+    def _outputs(self, chunks):
+        """Yields the uint8 RGB frames (P, [T,] H, W, 3) of one chunk of items after the other, on the current stream."""
+        asm, side = self.assembler, self.stream
+        cur = torch.cuda.current_stream(self.device)
 
         def preload(k):
             if k >= len(chunks):
@@ -607,32 +631,20 @@ class _SequenceRunner:
                 return asm.assemble(chunks[k])
 
         was_training = self.net.training
-        kept = []
         self.net.eval()
         try:
-            with torch.no_grad():
-                nxt = preload(0)
-                for k, chunk in enumerate(chunks):
-                    cur.wait_stream(side)
-                    batch = nxt
-                    for v in batch.values():
-                        v.record_stream(cur)
-                    nxt = preload(k + 1)
-                    out = self._forward(batch)
-                    u8 = metrics.val_tail(out[..., :asm.height, :asm.width], bgr=False).pred_u8       # (P, [T,] H, W, 3)
-                    for sink in sinks:
-                        sink.add(u8, k * self.max_minibatch, len(chunk))
-                    if keep:
-                        kept.append(u8)
+            nxt = preload(0)
+            for k, chunk in enumerate(chunks):
+                cur.wait_stream(side)
+                batch = nxt
+                for v in batch.values():
+                    v.record_stream(cur)
+                nxt = preload(k + 1)
+                out = self._forward(batch)
+                yield metrics.val_tail(out[..., :asm.height, :asm.width], bgr=False).pred_u8       # (P, [T,] H, W, 3)
         finally:
             self.net.train(was_training)
             cur.wait_stream(side)
-            with contextlib.ExitStack() as closing:        # (last in, first out) in the sinks' order, each even if another raises
-                for sink in reversed(sinks):
-                    closing.callback(sink.close)
-        for sink in sinks:
-            sink.finish()
-        return torch.cat(kept, dim=0).cpu().numpy() if keep else None
 
 
 class SequenceInterpolator(_SequenceRunner):
